@@ -10,15 +10,17 @@ reference produces at integrator_threads = 1, bit for bit (the serial early-out 
 event-driven fix point on the device, csrc/ks_k_exact.h).  One step = one frame integrated into
 the GPU-resident map through the C ABI, inputs already resident in HBM.
 
-Timing.  The trajectory is a ring of EXACTLY K distinct frames.  Every context first integrates >= PRIME + W untimed
-frames (whole turns of the ring: one frame per frame slot and pipeline stage — per-slot graph capture and buffer growth
-happen there), then R >= 9 timed regions, each ONE turn of the ring = the same K frames in the same order, every region
-bracketed by barrier + synchronize.  The early-out sets are per frame and no update count depends on the map, so every
-region does exactly the same work: the spread over the regions measures the code and the machine, not the trajectory.
-The line reports the MEDIAN region (value, ms_per_step) and the spread.  All 640x480 sub-records replay the same ring.
+Timing.  The trajectory is a ring of min(K, RING_FRAMES) distinct frames.  The headline context first integrates
+>= PRIME + W untimed frames (whole turns of the ring: one frame per frame slot and pipeline stage — per-slot graph capture
+and buffer growth happen there) and one more untimed turn of the ring, then ONE timed region of EXACTLY K = --steps
+frames (the ring replayed from its first frame), bracketed by barrier + synchronize, with flush + synchronize inside it.
+value and ms_per_step are that region's.  With --full the sub-records keep their own repeats: R >= 5 regions of one turn
+of the ring each, the MEDIAN region reported with the spread.  All 640x480 sub-records replay the same ring.
 
-Prints ONE short JSON line (rank 0, < 4 KB); the full record (every sub-record, stage table) goes to
-profiles/bench_full_r05.json.
+A plain run measures the headline only and prints ONE short JSON line (rank 0, < 4 KB).  --full adds everything else
+(per-stage and k_apply event passes, early-out fidelity, CPU baseline, steady state, the sub-records, C5, the adapter)
+and writes the full record to profiles/bench_full_latest.json (git-ignored; KS_BENCH_FULL names another file).
+--dump-outputs DIR writes the map the timed path left after its last step (.npy, float32 / float64; see dump_outputs).
   value = voxel updates/s over the whole job, where a voxel update is one (ray, voxel) pair for which
           the reference runs updateTsdfVoxel + updateSemanticVoxel (semantic_tsdf_integrator_fast.cpp:128-140)
           and N_updates is the count the SERIAL REFERENCE ORDER (CPU oracle, one thread) gives for the timed
@@ -54,8 +56,9 @@ BYTES_PER_POINT = 17           # xyz 12 B + rgba 4 B + label 1 B
 PRIME = 20                     # untimed frames per context before the warm-up: >= frame slots (12) + pipeline_frames (8); with 12 or 16 calls of lag (24 slots) the whole untimed turns of the ring before t0 cover the rest
 MIN_REPEATS = 5
 MIN_REPEATS_PRIMARY = 9        # timed regions of the headline: the stretches of the trajectory differ by +-30 % (fix-point rounds), the median of nine moves less between runs than the median of five
-MIN_TIMED_FRAMES = 100
-C4_STEPS = 12                  # frames per C4 region = distinct C4 frames (ring), 1280x720 each
+RING_FRAMES = 40               # distinct frames of the ring at most (the default --steps): a larger --steps replays them more often
+DUMP_SAMPLE_BLOCKS = 96        # blocks dumped voxel for voxel by --dump-outputs (~44 MB); every block is dumped as a digest
+C4_STEPS = 12                 # frames per C4 region = distinct C4 frames (ring), 1280x720 each
 try:
     METRIC = json.load(open(os.path.join(ROOT, "BASELINE.json")))["metric"]
 except Exception:
@@ -72,8 +75,13 @@ WORKLOADS = {
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=40)
+    ap.add_argument("--steps", type=int, default=40, help="timed frames (one timed region)")
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-stage / k_apply passes, fidelity check, CPU baseline, steady state, sub-records, C5, adapter "
+                         "and the full record file (a plain run measures the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the map after the last timed step to DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--method", default="fast", choices=["fast", "merged"])
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
@@ -107,15 +115,37 @@ def make_frames(wl, indices):
             for k in indices]
 
 
-def oracle_counts(wl, frames):
+def oracle_counts(wl, frames, workers=1):
     """Voxel updates per frame in the SERIAL REFERENCE ORDER (CPU oracle, one thread, reference defaults).
     Neither integrator's update count depends on the map, and `fast`'s early-out sets are per frame, so the
-    counts of the timed frames do not need the frames before them."""
+    counts of the timed frames do not need the frames before them: with workers > 1 every frame goes through a
+    fresh oracle of its own, `workers` of them at a time (the same counts, sooner)."""
     from oracle import oracle_py as O
-    o = O.Oracle(O.default_config(integrator_threads=1, **integ_cfg(wl, early_out_phase_growth=0)))
+    cfg = lambda: O.default_config(integrator_threads=1, **integ_cfg(wl, early_out_phase_growth=0))   # noqa: E731
+    if workers > 1:
+        from concurrent.futures import ThreadPoolExecutor
+
+        def one(f):
+            o = O.Oracle(cfg())
+            try:
+                return int(o.integrate(f.T_G_C, f.xyz, f.rgba, f.labels).n_voxel_updates)
+            finally:
+                o.close()
+        with ThreadPoolExecutor(workers) as ex:
+            return list(ex.map(one, frames))
+    o = O.Oracle(cfg())
     out = [int(o.integrate(f.T_G_C, f.xyz, f.rgba, f.labels).n_voxel_updates) for f in frames]
     o.close()
     return out
+
+
+def host_workers():
+    """CPUs this process may use, at most 16."""
+    try:
+        n = len(os.sched_getaffinity(0))
+    except (AttributeError, OSError):
+        n = os.cpu_count() or 1
+    return max(1, min(16, n))
 
 
 def median_spread(xs):
@@ -207,9 +237,14 @@ class FrameRing:
         return self.dev_frames[i % len(self.frames)]
 
 
-def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, reduce_fn=None, entry="device", prime=None, **cfg_extra):
-    """Integrates the ring as a stream: PRIME + W untimed frames, then R regions of K timed frames.  Returns the
-    regions' wall times, the GPU's statistics per region (checked to cover EXACTLY its frames), HIP-event profiles."""
+def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, reduce_fn=None, entry="device", prime=None,
+            pre=None, profile="inside", after_timed=None, **cfg_extra):
+    """Integrates the ring as a stream: PRIME + W untimed frames, an untimed region of `pre` (default K) frames, then R
+    regions of K timed frames.  Returns the regions' wall times, the GPU's statistics per region (checked to cover EXACTLY
+    its frames), HIP-event profiles.  profile: "inside" = k_apply events inside the timed regions and a per-stage pass
+    after them; "after" = both as passes of their own after the timed regions (the timed frames carry no events); None =
+    neither.  after_timed(integ, regions) runs right after the last timed region, before any further frame."""
+    pre = K if pre is None else pre
     cfg = B.default_config(device_id=dev.index or 0, max_tiles=max_tiles, max_points=max(f.xyz.shape[0] for f in ring.frames),
                            pipeline_frames=pipeline, **integ_cfg(wl, **cfg_extra))
     integ = B.HipIntegrator(cfg)
@@ -258,15 +293,16 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
 
     prime = PRIME if prime is None else prime
     # whole turns of the ring before t0, so that every timed region is the ring's frames 0 .. K-1 in order
-    base = -(-(prime + W) // len(ring)) * len(ring) if K == len(ring) else prime + W
+    base = -(-(prime + W) // len(ring)) * len(ring) if K == len(ring) or pre == len(ring) else prime + W
     for i in range(base):
         step(i)
     integ.flush()             # completes the untimed frames AND hands their statistics over (discarded):
     integ.synchronize()       # nothing is pending or owed at t0
-    # level 2: only the k_apply dispatch of every 4th frame carries HIP events (per-stage events
-    # would put stream bubbles into every timed frame)
-    integ.profile_enable(2)
-    integ.profile(reset=True)
+    if profile == "inside":
+        # level 2: only the k_apply dispatch of every 4th frame carries HIP events (per-stage events
+        # would put stream bubbles into every timed frame)
+        integ.profile_enable(2)
+        integ.profile(reset=True)
     regions = []
 
     def eo_stats():   # (counters of the library: no synchronisation)
@@ -275,7 +311,7 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
         except Exception:
             return {}
 
-    # one UNTIMED region first, run exactly like the timed ones (K steps, flush, synchronize): the first region after the priming
+    # one UNTIMED region first, run exactly like the timed ones (`pre` steps, flush, synchronize): the first region after the priming
     # turns was 10 - 15 % slower than the rest in every run (clocks, the first replay of the graphs with the k_apply events attached)
     for r in range(-1, R):
         eo0 = eo_stats()
@@ -285,7 +321,8 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
         t0 = time.perf_counter()
         updates = points = rays = 0
         first = base + max(r, 0) * K
-        for i in range(first, first + K):
+        n_steps = pre if r < 0 else K
+        for i in range(first, first + n_steps):
             st = step(i)          # pipelined: statistics of the frame(s) completed by this call
             updates += st.n_voxel_updates
             points += st.n_points
@@ -300,7 +337,7 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
         if world > 1:
             dist.barrier()
         dt = time.perf_counter() - t0
-        want_points = sum(int(ring.host(i).xyz.shape[0]) for i in range(first, first + K))
+        want_points = sum(int(ring.host(i).xyz.shape[0]) for i in range(first, first + n_steps))
         assert points == want_points, f"statistics cover {points} points, the timed frames hold {want_points}"
         if r < 0:
             continue
@@ -308,14 +345,28 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
         regions.append(dict(dt=dt, updates=updates, points=points, rays=rays, reduce=reduce_stats,
                             frames=list(range(first, first + K)),
                             early_out={k: eo1[k] - eo0[k] for k in ("frames", "rounds", "fallbacks") if k in eo0 and k in eo1}))
-    prof = integ.profile(reset=True)
-    # per-stage breakdown: separate untimed pass over a few frames with events around every stage
-    integ.profile_enable(1)
-    for i in range(base, base + min(10, K)):
-        step(i)
-    integ.flush()
-    stage_prof = integ.profile()
-    integ.profile_enable(0)
+    if after_timed is not None:
+        after_timed(integ, regions)
+    prof = stage_prof = None
+    if profile == "inside":
+        prof = integ.profile(reset=True)
+    elif profile == "after":
+        # the k_apply events in an untimed pass of their own: the same frames as MIN_REPEATS_PRIMARY turns of the ring
+        integ.profile_enable(2)
+        integ.profile(reset=True)
+        for i in range(base, base + MIN_REPEATS_PRIMARY * len(ring)):
+            step(i)
+        integ.flush()
+        integ.synchronize()
+        prof = integ.profile(reset=True)
+    if profile:
+        # per-stage breakdown: separate untimed pass over a few frames with events around every stage
+        integ.profile_enable(1)
+        for i in range(base, base + min(10, K)):
+            step(i)
+        integ.flush()
+        stage_prof = integ.profile()
+        integ.profile_enable(0)
     n_tiles = len(integ.tile_keys())
     eo = integ.early_out_iterations()
     integ.close()
@@ -324,7 +375,42 @@ def measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, max_tiles, world, 
             for p, v in bufs:
                 del v
                 B.lib().ks_host_free(p)
-    return dict(regions=regions, prof=prof, stage_prof=stage_prof, tiles=n_tiles, early_out_iterations=eo)
+    return dict(regions=regions, prof=prof, stage_prof=stage_prof, tiles=n_tiles, early_out_iterations=eo, untimed_frames=base + pre)
+
+
+def dump_outputs(out_dir, integ, regions):
+    """--dump-outputs: the map the timed path leaves after its last step (what ks_download_blocks hands a caller), as .npy files.
+    Blocks sorted by index.  Every block as a digest; DUMP_SAMPLE_BLOCKS of them (a seeded choice) voxel for voxel:
+      block_indices        float64 [n, 3]
+      block_digest         float64 [n, 5]  per block: observed voxels (weight > 0), sum of weight, of distance, of label, of priors
+                                           (sums over the observed voxels, float64)
+      sample_indices       float64 [m, 3]  the sampled blocks
+      sample_tsdf          float32 [m, V, 6]  distance, weight, colour r g b a
+      sample_semantic      float32 [m, V, 1 + 21]  label, priors
+      timed_totals         float64 [3]     voxel updates, points, rays cast over the timed region (the frame statistics of the calls)"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    idx = integ.block_indices()
+    idx = idx[np.lexsort((idx[:, 2], idx[:, 1], idx[:, 0]))] if len(idx) else idx
+    digest = np.zeros((len(idx), 5), dtype=np.float64)
+    for s in range(0, len(idx), 256):
+        _, t, sem = integ.download(idx[s:s + 256])
+        seen = t["weight"] > 0
+        digest[s:s + 256, 0] = seen.sum(axis=1)
+        digest[s:s + 256, 1] = np.where(seen, t["weight"], 0).astype(np.float64).sum(axis=1)
+        digest[s:s + 256, 2] = np.where(seen, t["distance"], 0).astype(np.float64).sum(axis=1)
+        digest[s:s + 256, 3] = np.where(seen, sem["label"], 0).astype(np.float64).sum(axis=1)
+        digest[s:s + 256, 4] = np.where(seen[..., None], sem["priors"], 0).astype(np.float64).sum(axis=(1, 2))
+    pick = np.sort(np.random.default_rng(0).choice(len(idx), size=min(DUMP_SAMPLE_BLOCKS, len(idx)), replace=False))
+    _, t, sem = integ.download(idx[pick])
+    tsdf = np.concatenate([t["distance"][..., None], t["weight"][..., None], t["color"].astype(np.float32)], axis=-1)
+    semantic = np.concatenate([sem["label"].astype(np.float32)[..., None], sem["priors"]], axis=-1)
+    reg = regions[-1]
+    arrays = {"block_indices": idx.astype(np.float64), "block_digest": digest, "sample_indices": idx[pick].astype(np.float64),
+              "sample_tsdf": tsdf.astype(np.float32), "sample_semantic": semantic.astype(np.float32),
+              "timed_totals": np.array([reg["updates"], reg["points"], reg["rays"]], dtype=np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def gpu_counts(B, dev, wl, frames, max_tiles, **cfg_extra):
@@ -393,28 +479,12 @@ def roofline_of(m, region, K, upd_counted, world=1, pmc_name=None):
     frame_s = region["dt"] / K
     whole_bytes = (BYTES_PER_UPDATE * upd_counted + BYTES_PER_POINT * region["points"] / world) / K   # per GPU
     whole_gbs = whole_bytes / frame_s / 1e9
-    nfr = max(1, sp["frames"])
-    stage_ms = {k: v / nfr for k, v in sp["ms"].items()}
-    tot = sum(stage_ms.values()) or 1.0
-    upd_pf, pts_pf = sp["updates"] / nfr, sp["points"] / nfr
-    stage_bytes = {"points": BYTES_PER_POINT * pts_pf, "apply": BYTES_PER_UPDATE * upd_pf}  # the stages that move the algorithmic bytes
-    stages = {}
-    for k, v in stage_ms.items():
-        e = {"ms_per_frame": round(v, 4), "share_of_kernel_time": round(v / tot, 4)}
-        if k in stage_bytes and v > 0:
-            gbs = stage_bytes[k] / (v * 1e-3) / 1e9
-            e.update({"achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 5)})
-        stages[k] = e
-    dominant = max(stage_ms, key=lambda k: stage_ms[k])
-    apply_ms = prof["apply_kernel_ms"] / max(1, prof["apply_kernel_launches"])
-    upd_per_launch = prof["apply_kernel_updates"] / max(1, prof["apply_kernel_launches"])
-    a_gbs = BYTES_PER_UPDATE * upd_per_launch / (apply_ms * 1e-3) / 1e9 if apply_ms > 0 else 0.0
     pmc = pmc_traffic(pmc_name) if pmc_name else None
     # round 6: `traffic` is the WHOLE frame's HBM bytes (every kernel, per frame) — the scope of `kernel` / `achieved`; the update
     # kernel's own counter bytes sit with its figures under k_apply
     traffic = (pmc.get("whole_frame_hbm_bytes_per_frame") or None) if pmc else None
     k_apply_traffic = pmc.get("k_apply_hbm_bytes_per_launch") if pmc else None
-    return {
+    out = {
         "bound": "hbm", "kernel": "whole frame (all stages, wall clock of the median timed region)",
         "achieved": round(whole_gbs, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(whole_gbs / HBM_PEAK_GBS, 5),
         "traffic": traffic,
@@ -422,17 +492,34 @@ def roofline_of(m, region, K, upd_counted, world=1, pmc_name=None):
                          f"gfx950 correction applied; null = the committed pass predates round 6): {pmc.get('source', 'profiles/')}" if pmc else
                          "no committed PMC pass for this workload (profiles/r0N_pmc_*.json)"),
         "algorithmic_bytes_per_frame": int(whole_bytes),
-        "dominant_stage": dominant,
-        "stages": stages,
-        "stage_note": "HIP events around every stage: separate untimed pass over 10 frames (stages of one frame back to "
-                      "back); march = early-out phases + scan + pair emission, sort_* = radix sorts, apply(+_long) = per-voxel update",
-        "k_apply": {"achieved": round(a_gbs, 2), "frac": round(a_gbs / HBM_PEAK_GBS, 5), "avg_launch_ms": round(apply_ms, 5),
-                    "algorithmic_bytes_per_launch": int(BYTES_PER_UPDATE * upd_per_launch),
-                    "traffic": k_apply_traffic, "kernel": (pmc or {}).get("update_kernel", "k_apply"),
-                    "timed_launches": prof["apply_kernel_launches"],
-                    "note": "events attached to the k_apply dispatch of every 4th timed frame (GPU's own update count); other "
-                            "stages of neighbouring frames share the GPU (pipelined)"},
     }
+    if sp is not None:
+        nfr = max(1, sp["frames"])
+        stage_ms = {k: v / nfr for k, v in sp["ms"].items()}
+        tot = sum(stage_ms.values()) or 1.0
+        upd_pf, pts_pf = sp["updates"] / nfr, sp["points"] / nfr
+        stage_bytes = {"points": BYTES_PER_POINT * pts_pf, "apply": BYTES_PER_UPDATE * upd_pf}  # the stages that move the algorithmic bytes
+        stages = {}
+        for k, v in stage_ms.items():
+            e = {"ms_per_frame": round(v, 4), "share_of_kernel_time": round(v / tot, 4)}
+            if k in stage_bytes and v > 0:
+                gbs = stage_bytes[k] / (v * 1e-3) / 1e9
+                e.update({"achieved": round(gbs, 1), "frac": round(gbs / HBM_PEAK_GBS, 5)})
+            stages[k] = e
+        out.update({"dominant_stage": max(stage_ms, key=lambda k: stage_ms[k]), "stages": stages,
+                    "stage_note": "HIP events around every stage: separate untimed pass over 10 frames (stages of one frame back to "
+                                  "back); march = early-out phases + scan + pair emission, sort_* = radix sorts, apply(+_long) = per-voxel update"})
+    if prof is not None:
+        apply_ms = prof["apply_kernel_ms"] / max(1, prof["apply_kernel_launches"])
+        upd_per_launch = prof["apply_kernel_updates"] / max(1, prof["apply_kernel_launches"])
+        a_gbs = BYTES_PER_UPDATE * upd_per_launch / (apply_ms * 1e-3) / 1e9 if apply_ms > 0 else 0.0
+        out["k_apply"] = {"achieved": round(a_gbs, 2), "frac": round(a_gbs / HBM_PEAK_GBS, 5), "avg_launch_ms": round(apply_ms, 5),
+                          "algorithmic_bytes_per_launch": int(BYTES_PER_UPDATE * upd_per_launch),
+                          "traffic": k_apply_traffic, "kernel": (pmc or {}).get("update_kernel", "k_apply"),
+                          "timed_launches": prof["apply_kernel_launches"],
+                          "note": "events attached to the k_apply dispatch of every 4th frame (GPU's own update count); other "
+                                  "stages of neighbouring frames share the GPU (pipelined)"}
+    return out
 
 
 
@@ -673,7 +760,7 @@ def mapped_library():
     return None
 
 
-LINE_LIMIT = 4000   # bytes of the ONE stdout line; everything else goes to the full record (profiles/bench_full_r06.json)
+LINE_LIMIT = 4000   # bytes of the ONE stdout line; everything else goes to the full record (--full)
 
 
 def compact_line(out, full_path):
@@ -774,11 +861,12 @@ def main():
         assert dist.get_world_size() == args.gpus
 
     K, W = args.steps, args.warmup
-    R = max(MIN_REPEATS_PRIMARY, -(-MIN_TIMED_FRAMES // max(1, K)))
+    if K < 1:
+        raise SystemExit("bench.py --steps must be at least 1")
     wl = dict(WORKLOADS["C2"], w=args.width, h=args.height, method=args.method)
     # frame-sharded: rank r integrates trajectory frames r, r+world, ... (weak scaling: the same number of frames per GPU);
-    # a ring of exactly K frames per rank: every timed region is one turn of it
-    n_distinct = K
+    # a ring of min(K, RING_FRAMES) frames per rank: the timed region replays it from its first frame, K frames in all
+    n_distinct = min(K, RING_FRAMES)
     frames = make_frames(wl, [rank + world * k for k in range(n_distinct)])
     ring = FrameRing(frames, torch, dev)
     # bag replay = a stream of frames: frame pipelining on.  `fast` (the headline): 12 calls of lag = THREE batches of four frames in
@@ -789,7 +877,7 @@ def main():
 
     reduce_fn = None
     comm = None
-    if world > 1 or os.environ.get("KS_BENCH_C5") == "1":
+    if world > 1 or (args.full and os.environ.get("KS_BENCH_C5") == "1"):
         from kimera_semantics_amd import parallel as PAR
         if world == 1 and not dist.is_initialized():   # single-GPU self-test of this code path
             os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
@@ -828,10 +916,16 @@ def main():
             integ.synchronize()
             return st
 
-    m = measure(B, torch, dist, dev, wl, ring, W, K, R, pipeline, 1 << 13, world, reduce_fn=reduce_fn)
+    dump = None
+    if args.dump_outputs and rank == 0:
+        def dump(integ, regions):
+            dump_outputs(args.dump_outputs, integ, regions)
+    # ONE timed region of exactly K frames; with --full the k_apply and per-stage event passes follow it (untimed)
+    m = measure(B, torch, dist, dev, wl, ring, W, K, 1, pipeline, 1 << 13, world, reduce_fn=reduce_fn, pre=len(ring),
+                profile="after" if args.full else None, after_timed=dump)
 
-    # N_updates in the serial reference order for this rank's frames (outside the timed regions)
-    upd_serial = None if args.no_oracle_count else oracle_counts(wl, frames)
+    # N_updates in the serial reference order for this rank's frames (outside the timed region)
+    upd_serial = None if args.no_oracle_count else oracle_counts(wl, frames, workers=host_workers())
     count_of_frame = (lambda i: upd_serial[i % n_distinct]) if upd_serial is not None else None
     how = ("serial reference order (CPU oracle, 1 thread), every timed frame" if upd_serial is not None
            else "GPU's own count (oracle count skipped)")
@@ -856,7 +950,7 @@ def main():
             count_of_frame = lambda i: per_frame[i]   # noqa: E731  (only sums over whole regions are used)
 
     c5 = None
-    if world > 1 or os.environ.get("KS_BENCH_C5") == "1":
+    if args.full and (world > 1 or os.environ.get("KS_BENCH_C5") == "1"):
         try:
             c5 = c5_record(B, torch, dist, dev, rank, world, comm, ddev)
         except Exception as e:   # collective calls above are symmetric; a local failure must not take the line down
@@ -876,10 +970,10 @@ def main():
             "frames_per_s": rec["frames_per_s"],
             "gpu_counted_value": rec["gpu_counted_value"],
             "updates_counted_by": rec["updates_counted_by"],
-            "timing": {"untimed_frames_before_t0": -(-(PRIME + W) // K) * K + K, "timed_regions": R, "steps_per_region": K,
-                       "untimed": "whole turns of the ring covering PRIME + warm-up frames, then one more turn run exactly like a timed region",
-                       "every_region_integrates": "the same K frames, in the same order (one turn of the ring)",
-                       "reported": "median region", "spread_max_minus_min_over_median": rec["spread"],
+            "timing": {"untimed_frames_before_t0": m["untimed_frames"], "timed_regions": 1, "steps_per_region": K,
+                       "untimed": "whole turns of the ring covering PRIME + warm-up frames, then one more turn run exactly like the timed region",
+                       "timed_region_integrates": f"K = {K} frames: the ring of {n_distinct} distinct frames from its first frame, in order",
+                       "reported": "the timed region", "spread_max_minus_min_over_median": rec["spread"],
                        "ms_per_step_all_regions": rec["ms_per_step_all_regions"],
                        "early_out_all_regions": rec["early_out_all_regions"]},
             "config": {"workload": "bag-replay stand-in: " + rec["workload"],
@@ -895,10 +989,11 @@ def main():
                            f" + one exchange at the end of every timed region: {exchange}"
                            if world > 1 else "")},
             "roofline": rec["roofline"],
-            "host_ms_per_frame": {"in_call": round(m["prof"]["host_ms"] / max(1, m["prof"]["frames"]), 4),
-                                  "of_which_waiting_for_snapshot": round(m["prof"]["host_wait_ms"] / max(1, m["prof"]["frames"]), 4)},
         }
-        if world == 1 and not args.no_secondary:
+        if m["prof"] is not None:
+            out["host_ms_per_frame"] = {"in_call": round(m["prof"]["host_ms"] / max(1, m["prof"]["frames"]), 4),
+                                        "of_which_waiting_for_snapshot": round(m["prof"]["host_wait_ms"] / max(1, m["prof"]["frames"]), 4)}
+        if args.full and world == 1 and not args.no_secondary:
             try:
                 out["steady_state"] = steady_state(B, torch, dist, dev, wl, ring, 10 * len(ring), pipeline, 1 << 13)
             except Exception as e:
@@ -907,15 +1002,15 @@ def main():
             out["reduce"] = reg["reduce"]
         if c5 is not None:
             out.setdefault("secondary", []).append(c5)
-        if world == 1 and args.method == "fast" and upd_serial is not None:
+        if args.full and world == 1 and args.method == "fast" and upd_serial is not None:
             try:
                 out["early_out_fidelity"] = early_out_fidelity(B, dev, wl, [ring.host(i) for i in range(2)], 1 << 13)
             except Exception as e:
                 out["early_out_fidelity"] = {"error": f"{type(e).__name__}: {e}"}
-        if not args.no_cpu_baseline and world == 1 and upd_serial is not None:   # reported on rank 0 at N=1 only
+        if args.full and not args.no_cpu_baseline and world == 1 and upd_serial is not None:   # reported on rank 0 at N=1 only
             first = [i % n_distinct for i in range(min(args.cpu_frames, n_distinct))]
             out["cpu_baseline"] = cpu_baseline(args, wl, [frames[i] for i in first], [upd_serial[i] for i in first])
-        if world == 1 and not args.no_secondary:
+        if args.full and world == 1 and not args.no_secondary:
             sec = out.get("secondary", [])
             only = set(filter(None, args.only_secondary.split(",")))
 
@@ -935,7 +1030,7 @@ def main():
                 if not want(name) or args.method != "fast" or (args.width, args.height) != (640, 480):
                     continue
                 try:
-                    sK, sR = K, MIN_REPEATS
+                    sK, sR = len(sub_ring), MIN_REPEATS
                     sm = measure(B, torch, dist, dev, swl, sub_ring, 2, sK, sR, kw["pipe"], 1 << 13, 1,
                                  entry=kw.get("entry", "device"), **kw["cfg"])
                     cof, show = None, "GPU's own count (oracle count skipped)"
@@ -1038,15 +1133,17 @@ def main():
                                                       "buffers); frames_per_s_device_resident / value / ms_per_step: inputs resident in HBM")
         out["library"] = mapped_library()
         out["bench_seconds"] = round(time.time() - t_start, 1)
-        # the full record (every sub-record, stage table, A/B record) goes to a file; stdout carries ONE short line
-        full_path = os.environ.get("KS_BENCH_FULL") or os.path.join("profiles", "bench_full_r06.json" if world == 1 else f"bench_full_r06_n{world}.json")
-        try:
-            with open(os.path.join(ROOT, full_path) if not os.path.isabs(full_path) else full_path, "w") as fh:
-                json.dump(out, fh, indent=1)
-                fh.write("\n")
-        except OSError as e:
-            sys.stderr.write(f"bench: full record not written ({e})\n")
-            full_path = None
+        # --full: the full record (every sub-record, stage table, A/B record) goes to a file; stdout carries ONE short line
+        full_path = None
+        if args.full:
+            full_path = os.environ.get("KS_BENCH_FULL") or os.path.join("profiles", "bench_full_latest.json" if world == 1 else f"bench_full_latest_n{world}.json")
+            try:
+                with open(os.path.join(ROOT, full_path) if not os.path.isabs(full_path) else full_path, "w") as fh:
+                    json.dump(out, fh, indent=1)
+                    fh.write("\n")
+            except OSError as e:
+                sys.stderr.write(f"bench: full record not written ({e})\n")
+                full_path = None
         os.write(json_fd, (compact_line(out, full_path) + "\n").encode())
     if world > 1 or (dist.is_available() and dist.is_initialized()):
         dist.destroy_process_group()

@@ -203,7 +203,7 @@ def test_bench_gpus_2_spawns_its_ranks_and_reports_the_exchange(tmp_path):
     env.pop("WORLD_SIZE", None)
     env.pop("RANK", None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "1", "--no-cpu-baseline",
-                        "--no-secondary", "--width", "320", "--height", "240"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+                        "--no-secondary", "--width", "320", "--height", "240", "--full"], env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

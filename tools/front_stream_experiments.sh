@@ -6,7 +6,7 @@ S=${1:-steady}
 O=gpurun_out/front_$S; rm -rf $O; mkdir -p $O
 bench_rec() {  # tag, env... : C3 and C4-merged records of bench.py (regions of 40 / 12 frames)
   tag=$1; shift
-  env KS_DEBUG=1 "$@" timeout 900 python bench.py --only-secondary C3,C4-merged --no-cpu-baseline --no-oracle-count > $O/bench_$tag.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
+  env KS_DEBUG=1 "$@" timeout 900 python bench.py --full --only-secondary C3,C4-merged --no-cpu-baseline --no-oracle-count > $O/bench_$tag.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
   python - <<PY
 import json
 d = json.loads(open("$O/bench_$tag.json").read())

@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/lazy_marks; rm -rf $O; mkdir -p $O
 timeout 1500 python -m pytest tests/test_exact_early_out_gpu.py -m gpu -q -x 2>&1 | tail -4
-timeout 900 python bench.py --only-secondary C4-fast --no-cpu-baseline --no-oracle-count > $O/bench_c4fast.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
+timeout 900 python bench.py --full --only-secondary C4-fast --no-cpu-baseline --no-oracle-count > $O/bench_c4fast.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
 python - <<PY
 import json
 d = json.loads(open("gpurun_out/lazy_marks/bench_c4fast.json").read())

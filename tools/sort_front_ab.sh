@@ -1,7 +1,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/call_sf; rm -rf $O; mkdir -p $O
 for SF in 1 0; do
-KS_DEBUG=1 KS_SORT_FRONT=$SF timeout 900 python bench.py --only-secondary C4-merged,C3,C4-fast-ordered-phases --no-cpu-baseline --no-oracle-count > $O/bench_sf$SF.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
+KS_DEBUG=1 KS_SORT_FRONT=$SF timeout 900 python bench.py --full --only-secondary C4-merged,C3,C4-fast-ordered-phases --no-cpu-baseline --no-oracle-count > $O/bench_sf$SF.json 2> $O/bench.err; tail -c 300 $O/bench.err | grep -v amdgpu
 python - <<PY
 import json
 d = json.loads(open("gpurun_out/call_sf/bench_sf$SF.json").read())
