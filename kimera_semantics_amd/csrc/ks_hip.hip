@@ -152,14 +152,11 @@ struct FrameSlot {
   uint32_t* d_ray_list = nullptr;   // rays to march (written by stage A, read by B)
   HostSnap* h_snap = nullptr;       // pinned + device-visible: written by k_publish at the end of B
   hipEvent_t a_done = nullptr;      // stage A complete
-  hipEvent_t bl_fork = nullptr, bl_join = nullptr;   // merged: the long bundles' merge beside the bundle order (stream_bundles)
   hipEvent_t ready = nullptr;       // snapshot has landed
   hipEvent_t tail_done = nullptr;   // the tail has consumed this slot's buffers
   hipEvent_t fork = nullptr, join = nullptr;  // tail: pairs sorted and long runs listed | long runs applied
   hipEvent_t join_x = nullptr;                // the runs of more than kXLongRun updates applied (stream_xlong)
   hipEvent_t found = nullptr;                 // the long runs listed on the long-run stream (k_find_long beside k_apply_runs)
-  hipEvent_t applied = nullptr;               // k_apply_runs done (stream_apply); S.join waits for it
-  hipEvent_t sorted = nullptr;                // the pair sort done on the front stream (sort_on_front)
   bool tail_recorded = false;
   bool join_recorded = false;
   bool b_launched = false;    // stage B of the frame has been enqueued (with its batch)
@@ -200,10 +197,6 @@ struct ks_ctx {
   hipStream_t stream_tail = nullptr;   // stage T; == stream unless pipelined
   hipStream_t stream_long = nullptr;   // the long-run voxel update, beside k_apply (always its own stream)
   hipStream_t stream_xlong = nullptr;  // the runs of more than kXLongRun updates, beside both (k_apply_xlong)
-  hipStream_t stream_bundles = nullptr; // merged, pipelined: k_bundles_long beside k_bo_* / k_bundles (round 6); == stream_long unless KS_BUNDLE_STREAM=1
-  hipStream_t stream_bundles_own = nullptr;
-  std::vector<hipStream_t> stream_pad;
-  hipStream_t stream_apply = nullptr;  // k_apply_runs, so that the tail stream goes on with the NEXT frame's pair sort while it runs (round 6)
   bool xlong = true;
   float voxel_size_inv = 0.f, log_match = 0.f, log_non_match = 0.f;
   int vps_shift = 1;  // log2(vps / 8)
@@ -231,9 +224,7 @@ struct ks_ctx {
   bool tail_busy = false, tail_quit = false;
   int tail_rc = KS_OK;
   bool use_tail_thread = false;
-  double hp_a = 0, hp_b = 0, hp_t = 0, hp_sort = 0;   // KS_HOST_PROF=1: host seconds spent enqueueing stage A / B / T, radix sorts (of A+T)
-  bool host_prof = false;
-  bool use_graphs = true;                // stage B replayed as a hipGraph (KS_NO_GRAPH=1 or a capture failure: plain launches)
+  bool use_graphs = true;                // stage B replayed as a hipGraph (a capture failure: plain launches)
   bool test_overlap = true;              // k_test casts a long ray's next 64 voxels while the shared-set entries of the current 64 are in flight (KS_TEST_OVERLAP=0: one after the other, as measured until round 3)
   std::atomic<uint64_t> buffers_epoch{1};  // bumped whenever a buffer a captured graph points at is re-allocated
   uint8_t* d_color_lut = nullptr;   // 16 MiB rgb -> label
@@ -261,7 +252,6 @@ struct ks_ctx {
   uint64_t* d_key_overflow = nullptr;   // merged, compact grouping keys: the table of the end voxels outside the key window (k_points_merged)
   uint32_t key_overflow_mask = 0;
   uint32_t key_bits = 0;                // bits per axis of the key window; 0: the 64-bit keys are sorted (FrameParams::key_bits)
-  float* d_blong_merged = nullptr;     // k_bundles_long -> k_bundles_long_finish: kBundleLongRec floats per long bundle
   uint64_t *d_pkeys = nullptr, *d_pkeys2 = nullptr;
   uint32_t *d_pvals = nullptr, *d_pvals2 = nullptr;
   uint32_t* d_order = nullptr;
@@ -269,12 +259,6 @@ struct ks_ctx {
   uint32_t *d_okeys = nullptr, *d_okeys2 = nullptr, *d_ovals = nullptr;
   size_t cap_pairs = 0;
   uint64_t* d_pairs2_[2] = {nullptr, nullptr};
-  // no early-out, pipelined: stage B (scan + emission) of frames of fewer than emit_on_tail_max_pairs updates goes to the TAIL stream —
-  // at 640x480 `merged` the front stream is the one that is busy all the time (stage A 0.4 ms + emission 0.09 ms per frame) and the
-  // tail stream idles two thirds of it; at 1280x720 / 2 cm it is the other way round (round 6)
-  bool emit_on_tail = false;
-  unsigned long long emit_on_tail_max_pairs = 1ull << 23;
-  bool defer_join = false;               // k_apply_long of frame f overlaps the pair sort of frame f+1 (pipelined contexts)
   hipEvent_t pending_join = nullptr;     // recorded on stream_long; the next k_apply / k_apply_long wait for it
   ksrs::Workspace sort_ws, sort_ws_tail;
   // fast, early-out in the reference's serial order (ks_k_exact.h): marks (two sets for the sort), slot ranges,
@@ -293,10 +277,9 @@ struct ks_ctx {
   // ... event-driven (the default; KS_EXACT_HOST_LOOP=1: every frame through the host-driven loop above)
   bool eo_device = false;
   int eo_bulk_rounds = 6;                // rounds enqueued as launches before the one-workgroup finisher takes over
-  int eo_sweeps = 12;                    // long rays: sweeps enqueued at a time (they end themselves once one changes nothing); the host looks
+  static constexpr int eo_sweeps = 12;   // long rays: sweeps enqueued at a time (they end themselves once one changes nothing); the host looks
                                          // at the count once per such chunk (launch_batch) and enqueues more while rays still change
   int eo_sweep_chunks = 16;              // ... at most this many chunks, then the host-driven loop takes the frame
-  int eo_sweep_order = 1;                // 0: rays in integration order; 1: a wavefront per chain segment, its rays one after the other   // long rays: one entry per emission of the marks over the rays' views = the dense iterations that follow it (ks_k_exact.h)
   std::atomic<int> eo_want_bulk{0};      // ... as a frame whose finisher was handed too long a list asks for (applied by the caller's thread between frames)
   uint32_t* d_eo_committed = nullptr;    // frames [0, *d_eo_committed) of the exact path have entered d_eo_plain
   uint32_t eo_frame_no = 0;              // frames launched through the exact path
@@ -307,7 +290,6 @@ struct ks_ctx {
   uint64_t eo_fallbacks_seen = 0;        // ... as of the caller's last look
   std::atomic<int> eo_hopeless{0};       // consecutive frames the device loop gave up on for reasons growing a buffer does not cure
   bool eo_device_off = false;            // ... three of them: the context stays with the host-driven loop (one frame at a time)
-  bool eo_trace = false;                 // KS_EXACT_TRACE=1: a line on stderr for every frame the device loop gives up (diagnostics)
   // merged in the reference's bundle order (ks_k_bundle_order.h): scratch of the rank computation, one slab
   bool use_bundle_rank = false;
   BoCtx bo{};
@@ -377,14 +359,6 @@ struct ks_ctx {
   // the runs of 33 .. 1024 updates a lane per run, bucketed by length over the frame (k_apply_long_lanes); by parity, like the lists
   bool long_lanes = true;
   unsigned long long long_lanes_min_pairs = 1ull << 24;
-  bool long_min_lanes = false;
-  // k_apply_runs: 256 threads (tiles of 1024 pairs) or 512 (tiles of 2048).  Measured at 1280x720 / 2 cm beside the long-run kernels:
-  // 2.45 vs 3.08 ms, the frame 5.98 vs 6.26 ms (profiles/r06_c4_merged_ab.txt) — a workgroup of one wavefront per SIMD finds room
-  // where one of two per SIMD does not
-  uint32_t run_threads = 256u;
-  uint32_t lanes_depth = 6u;   // k_apply_long_lanes: rays in flight per lane
-  bool sort_on_front = false;          // the pair sort of pipelined contexts without an early-out on the front stream (frame_tail)
-  FrameSlot* last_tail_of_parity[2] = {nullptr, nullptr};   // (below: too few such runs to fill wavefronts with — k_apply_long takes them all)
   unsigned long long* d_long_sorted_[2] = {nullptr, nullptr};
   LongHdr* d_long_hdr_[2] = {nullptr, nullptr};
   unsigned long long* d_xl_fb = nullptr;
@@ -405,12 +379,6 @@ struct ks_ctx {
 
 namespace {
 
-struct HostTimer {
-  double* acc;
-  std::chrono::steady_clock::time_point t0;
-  explicit HostTimer(double* a) : acc(a), t0(std::chrono::steady_clock::now()) {}
-  ~HostTimer() { *acc += std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count(); }
-};
 inline hipStream_t march_stream(ks_ctx* c, uint64_t frame_no) { return c->stream_march_[frame_no % (uint64_t)c->n_march]; }
 inline uint64_t* observed_table(ks_ctx* c, uint64_t frame_no) { return c->d_observed_[frame_no % (uint64_t)c->n_obs]; }
 int sync_march(ks_ctx* c) {
@@ -582,7 +550,6 @@ int ensure_points(ks_ctx* c, size_t n) {
     if ((rc = dev_alloc(c, &c->d_glc, cap))) return rc;
     if ((rc = dev_alloc(c, &c->d_ray_keys, cap))) return rc;
     if ((rc = dev_alloc(c, &c->d_blong, cap / kLongRun + 64))) return rc;
-    if ((rc = dev_alloc(c, &c->d_blong_merged, (cap / kLongRun + 64) * (size_t)kBundleLongRec))) return rc;
     if (c->key_bits) {
       size_t slots = 1024;
       while (slots < 2 * cap) slots <<= 1;
@@ -618,8 +585,7 @@ int ensure_pairs_out(ks_ctx* c, size_t n) {
   if (n <= c->cap_pairs) return KS_OK;
   const size_t cap = std::max<size_t>(n + n / 4, 1 << 20);
   int rc;
-  if (c->stream_long) HIPCHK(c, hipStreamSynchronize(c->stream_long));  // long runs of the previous frame may still read them
-  if (c->sort_on_front && c->stream) HIPCHK(c, hipStreamSynchronize(c->stream));   // (the previous frame's pair sort may still write them)
+  HIPCHK(c, hipStreamSynchronize(c->stream_long));  // long runs of the previous frame may still read them
   if (c->stream_xlong) HIPCHK(c, hipStreamSynchronize(c->stream_xlong));
   if (c->stream_tail) HIPCHK(c, hipStreamSynchronize(c->stream_tail));
   for (int b = 0; b < 2; ++b) {
@@ -635,7 +601,6 @@ int ensure_pairs_out(ks_ctx* c, size_t n) {
 
 template <typename K>
 int sort_keys(ks_ctx* c, K* a, K* b, size_t n, unsigned end_bit, K** result, unsigned begin_bit = 0, bool tail = false) {
-  HostTimer ht(&c->hp_sort);
   HIPCHK(c, (ksrs::sort<K, false>(tail ? c->sort_ws_tail : c->sort_ws, a, b, nullptr, nullptr, n, end_bit,
                                   tail ? c->stream_tail : c->stream, result, nullptr, begin_bit)));
   return KS_OK;
@@ -643,7 +608,6 @@ int sort_keys(ks_ctx* c, K* a, K* b, size_t n, unsigned end_bit, K** result, uns
 template <typename K>
 int sort_pairs(ks_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, size_t n, unsigned end_bit, K** kres,
                uint32_t** vres) {
-  HostTimer ht(&c->hp_sort);
   HIPCHK(c, (ksrs::sort<K, true>(c->sort_ws, ka, kb, va, vb, n, end_bit, c->stream, kres, vres)));
   return KS_OK;
 }
@@ -982,16 +946,11 @@ EoView eo_view(ks_ctx* c, const FrameSlot& S) {
 // long rays: `count` sweeps (each ends at once when the one before it changed nothing), ks_k_exact.h
 void enqueue_sweeps(ks_ctx* c, const EoBatch& Bt, uint32_t nb, int count, hipStream_t st) {
   const size_t n = c->cap_points;
-  uint32_t grid;
-  if (c->eo_sweep_order == 0) {
-    grid = (uint32_t)std::min<size_t>((n + 3) / 4, 1 << 20);
-  } else {
-    const size_t waves = (size_t)order_chains_cap(c->cfg.integration_order_mode, n) *
-                         ((order_generations_cap(c->cfg.integration_order_mode, n) + kEoSweepSegment - 1) / kEoSweepSegment);
-    grid = (uint32_t)std::min<size_t>((waves + 3) / 4, 1 << 16);
-  }
+  const size_t waves = (size_t)order_chains_cap(c->cfg.integration_order_mode, n) *
+                       ((order_generations_cap(c->cfg.integration_order_mode, n) + kEoSweepSegment - 1) / kEoSweepSegment);
+  const uint32_t grid = (uint32_t)std::min<size_t>((waves + 3) / 4, 1 << 16);
   for (int i = 0; i < count; ++i) {
-    hipLaunchKernelGGL(k_eo2_sweep, dim3(grid, nb), dim3(256), 0, st, Bt, (uint32_t)c->eo_sweep_order);
+    hipLaunchKernelGGL(k_eo2_sweep, dim3(grid, nb), dim3(256), 0, st, Bt);
     hipLaunchKernelGGL(k_eo2_sweep_next, dim3(nb), dim3(64), 0, st, Bt);
   }
 }
@@ -1063,15 +1022,12 @@ void enqueue_exact_finish(ks_ctx* c, FrameSlot& S, hipStream_t st) {
 // stage A (graph capture and the helper thread's tail never meet on a stream).
 int launch_batch(ks_ctx* c) {
   if (c->batch_slots.empty()) return KS_OK;
-  HostTimer htb(&c->hp_b);
   std::vector<FrameSlot*> slots;
   slots.swap(c->batch_slots);
   const uint32_t nb = (uint32_t)slots.size();
   FrameSlot& S0 = *slots[0];
   hipStream_t st = c->stream;
   hipStream_t sm = c->batch > 1 ? c->stream_march_[(S0.frame_no / (uint64_t)c->batch) % (uint64_t)c->n_march] : march_stream(c, S0.frame_no);
-  const bool on_tail = c->emit_on_tail && c->profiling != 1 && (unsigned long long)c->pairs_hint.load(std::memory_order_relaxed) < c->emit_on_tail_max_pairs;
-  if (on_tail) sm = c->stream_tail;
   c->prof_march_stream = sm;
   if (sm != st) HIPCHK(c, hipStreamWaitEvent(sm, slots[nb - 1]->a_done, 0));  // stage A is one in-order stream: the last frame's event covers all
   const bool stage_events = nb == 1 && S0.prof_set >= 0 && c->pset[S0.prof_set].stages;
@@ -1080,7 +1036,7 @@ int launch_batch(ks_ctx* c) {
   // their launch sequence depends only on the capacity: it is captured once per group of slots and replayed.
   BatchView V{};
   size_t steps_max = 0;
-  ParamsBatch PB;
+  ParamsBatch PB{};
   for (uint32_t k = 0; k < nb; ++k) {
     FrameSlot& S = *slots[k];
     S.F.observed = observed_table(c, S.frame_no);
@@ -1183,12 +1139,10 @@ int launch_batch(ks_ctx* c) {
       G.g1 = nullptr;
       G.key = 0;
       hipGraph_t g = nullptr;
-      // (captured on a stream only this thread enqueues on: the tail stream is the helper thread's as well)
-      hipStream_t sc = on_tail ? st : sm;
-      bool ok = hipStreamBeginCapture(sc, hipStreamCaptureModeRelaxed) == hipSuccess;
+      bool ok = hipStreamBeginCapture(sm, hipStreamCaptureModeRelaxed) == hipSuccess;
       if (ok) {
-        enqueue_stage_b(c, V, nb, S0.wide, sc, steps_max);
-        ok = hipStreamEndCapture(sc, &g) == hipSuccess && g != nullptr;
+        enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max);
+        ok = hipStreamEndCapture(sm, &g) == hipSuccess && g != nullptr;
       }
       if (ok) ok = hipGraphInstantiate(&G.g1, g, nullptr, nullptr, 0) == hipSuccess;
       if (g) (void)hipGraphDestroy(g);
@@ -1217,7 +1171,6 @@ int launch_batch(ks_ctx* c) {
 // ---- front half: everything up to the counter snapshot --------------------------------------
 int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, const uint8_t* d_rgba,
                 const uint8_t* d_labels, size_t n, int freespace) {
-  HostTimer hta(&c->hp_a);
   const ks_config& cfg = c->cfg;
   int rc;
   FrameParams& F = S.F;
@@ -1359,17 +1312,6 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     hipLaunchKernelGGL(k_gather_sorted, dim3(nb), dim3(256), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
                        order_ptr, (const uint64_t*)sk, (const uint32_t*)sk32, sk, sv, c->d_gpw, c->d_glc, c->use_bundle_rank ? c->bo.flag : nullptr, c->d_blong,
                        c->d_key_overflow, S.d_counters);
-    // the bundles of kLongRun points and more: their merge is one serial chain per bundle (0.16 ms at 640x480 with a wall
-    // close to the sensor) that needs nothing of the bundle order — pipelined, it runs on a stream of its own beside k_bo_* and
-    // k_bundles, and only what needs the integration id (k_bundles_long_finish) waits for both
-    const uint32_t grid_bl = (uint32_t)std::min<size_t>(n / kLongRun + 1, 2048);
-    hipStream_t sb = c->stream_bundles ? c->stream_bundles : st;
-    if (sb != st) {
-      HIPCHK(c, hipEventRecord(S.bl_fork, st));
-      HIPCHK(c, hipStreamWaitEvent(sb, S.bl_fork, 0));
-      hipLaunchKernelGGL(k_bundles_long, dim3(grid_bl), dim3(128), 0, sb, F, sk, c->d_gpw, c->d_glc, c->d_blong, c->d_blong_merged, S.d_counters);
-      HIPCHK(c, hipEventRecord(S.bl_join, sb));
-    }
     if (c->use_bundle_rank) {
       // the bundles' ranks in the iteration order of the reference's unordered_map (ks_k_bundle_order.h):
       // insertion indices, then one walk + link launch per rehash epoch the slot capacity can reach
@@ -1402,18 +1344,11 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     // buffers while this frame's emission — or its repetition after a pair-buffer overflow — may still run)
     uint64_t* ray_keys = cfg.enable_anti_grazing ? S.d_rkeys : nullptr;
     if (cfg.enable_anti_grazing) HIPCHK(c, hipMemcpyAsync(S.d_gkeys, sk, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    if (sb != st) {
-      hipLaunchKernelGGL(k_bundles, dim3(nb), dim3(256), 0, st, F, sk, sv, c->d_gpw, c->d_glc, S.d_rays, S.d_deltas,
-                         S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters);
-      HIPCHK(c, hipStreamWaitEvent(st, S.bl_join, 0));
-      hipLaunchKernelGGL(k_bundles_long_finish, dim3(std::min<uint32_t>((grid_bl + 3) / 4, 64)), dim3(256), 0, st, F, sk, sv, c->d_blong, c->d_blong_merged,
-                         S.d_rays, S.d_deltas, S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters);
-    } else {
-      // one launch: the long bundles' serial chains in the first workgroups, the short bundles under them
-      const uint32_t n_long_blocks = std::min<uint32_t>(grid_bl, 512);
-      hipLaunchKernelGGL(k_bundles_all, dim3(n_long_blocks + (uint32_t)((n + 127) / 128)), dim3(128), 0, st, F, sk, sv, c->d_gpw, c->d_glc, c->d_blong,
-                         S.d_rays, S.d_deltas, S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters, n_long_blocks);
-    }
+    // one launch: the bundles of kLongRun points and more (one serial chain per bundle, 0.16 ms at 640x480 with a wall close
+    // to the sensor) in the first workgroups, the short bundles under them
+    const uint32_t n_long_blocks = (uint32_t)std::min<size_t>(n / kLongRun + 1, 512);
+    hipLaunchKernelGGL(k_bundles_all, dim3(n_long_blocks + (uint32_t)((n + 127) / 128)), dim3(128), 0, st, F, sk, sv, c->d_gpw, c->d_glc, c->d_blong,
+                       S.d_rays, S.d_deltas, S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters, n_long_blocks);
     if (cfg.enable_anti_grazing) {
       F.grazing_keys = S.d_gkeys;
       F.ray_keys = S.d_rkeys;
@@ -1421,7 +1356,7 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
   }
   stage_mark(c, S.prof_set, 3);
   // ---- stage B (early-out phases, scan, pair emission) is enqueued per BATCH of frames: launch_batch
-  if (c->stream_march_[0] != st || c->emit_on_tail) HIPCHK(c, hipEventRecord(S.a_done, st));
+  if (c->stream_march_[0] != st) HIPCHK(c, hipEventRecord(S.a_done, st));
   S.steps_max = steps_max;
   S.b_launched = false;
   S.pending = true;
@@ -1483,7 +1418,6 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     HIPCHK(c, hipEventSynchronize(S.ready));  // the frame's only host wait
     if (c->profiling) c->prof.host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   }
-  HostTimer htt(&c->hp_t);
   Counters cnt = S.counters();
   uint32_t new_tiles = std::min(S.n_tiles(), c->cfg.max_tiles);
   const uint32_t tiles_before = c->tiles_initialised;
@@ -1494,18 +1428,6 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     c->eo_iterations += S.h_snap->pad[2];   // rounds of the event-driven fix point (k_publish)
   }
   if (c->eo_device && !c->eo_device_off && !(cnt.err & kErrExact)) c->eo_hopeless.store(0, std::memory_order_relaxed);
-  if (c->eo_trace && c->eo_device && !c->eo_device_off && !(cnt.err & kErrExact) && S.d_eo_ctl) {   // KS_EXACT_TRACE=1 (diagnostics; a host wait)
-    EoCtl hctl;
-    (void)hipStreamSynchronize(st);
-    if (hipMemcpy(&hctl, S.d_eo_ctl, sizeof(hctl), hipMemcpyDeviceToHost) == hipSuccess) {
-      fprintf(stderr, "[ks exact] frame %llu on the device: marks %llu / cap %zu, X %u / cap %zu, rounds %u; lists:", (unsigned long long)S.frame_no,
-              (unsigned long long)hctl.st.n_marks, c->eo_cap_marks, hctl.n_x, c->eo_cap_x, hctl.rounds);
-      for (int r = 1; r <= c->eo_bulk_rounds + 1 && r < (int)kEoBulkMax + 2; ++r) fprintf(stderr, " %u", hctl.n_in[r]);
-      fprintf(stderr, "; sweeps (rays changed):");
-      for (int i = 0; i < 32; ++i) fprintf(stderr, " %u%s", hctl.dense_chg[i] & 0x7fffffffu, (hctl.dense_chg[i] >> 31) ? "F" : "");
-      fprintf(stderr, "\n");
-    }
-  }
   if ((cnt.err & kErrExact) && !(cnt.err & (kErrLabel | kErrIndex))) {
     // The device-driven fix point gave up (marks or X marks did not fit, the finisher ran out of rounds, or the frame
     // before this one fell back and had not entered its marks yet): the host-driven loop repeats the fix point from
@@ -1540,14 +1462,6 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     if (dense) c->eo_hopeless.fetch_add(1, std::memory_order_relaxed);
     else if (!(hctl.fail & kEoFailChain)) c->eo_hopeless.store(0, std::memory_order_relaxed);
     c->eo_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    if (c->eo_trace) {   // KS_EXACT_TRACE=1 (diagnostics): why the device loop gave this frame up
-      fprintf(stderr, "[ks exact] frame %llu falls back: fail %x (1 marks, 2 X marks, 4 rounds, 8 chain) marks %llu / cap %zu, X %u / cap %zu, rounds %u, dense %d; lists:",
-              (unsigned long long)S.frame_no, hctl.fail, (unsigned long long)hctl.st.n_marks, c->eo_cap_marks, hctl.n_x, c->eo_cap_x, hctl.rounds, (int)dense);
-      for (int r = 1; r <= c->eo_bulk_rounds + 1 && r < (int)kEoBulkMax + 2; ++r) fprintf(stderr, " %u", hctl.n_in[r]);
-      fprintf(stderr, "; sweeps (rays changed):");
-      for (int i = 0; i < 32; ++i) fprintf(stderr, " %u%s", hctl.dense_chg[i] & 0x7fffffffu, (hctl.dense_chg[i] >> 31) ? "F" : "");
-      fprintf(stderr, "\n");
-    }
     Counters rcnt{};
     rcnt.n_rays = cnt.n_rays;
     HIPCHK(c, hipMemcpyAsync(c->d_retry_counters, &rcnt, sizeof(rcnt), hipMemcpyHostToDevice, st));
@@ -1655,88 +1569,56 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     const int par = (int)(S.frame_no & 1u);
     uint64_t* const d_pairs2 = c->d_pairs2_[par];
     unsigned long long* const d_long_list = c->d_long_list_[par];
-    // Pipelined contexts without an early-out (stage B follows stage A on the front stream): the pair sort — bound by HBM — goes to
-    // the FRONT stream, the update — bound by resident workgroups — stays on the tail stream, so that the sort of frame f runs beside
-    // the update of frame f - 1 (on one stream they ran one after the other: the tail stream was the frame period).  The sort waits for
-    // the update that last read the buffer set it writes (frame f - 2: the sets alternate), the tail stream for the sort.
-    const bool sort_front = c->sort_on_front && st != c->stream && !c->uses_early_out && !(set >= 0 && c->pset[set].stages);
-    if (sort_front) {
-      hipStream_t ss = c->stream;
-      FrameSlot* prev = c->last_tail_of_parity[par];
-      if (prev && prev != &S) {
-        if (prev->tail_recorded) HIPCHK(c, hipStreamWaitEvent(ss, prev->tail_done, 0));
-        if (prev->join_recorded) HIPCHK(c, hipStreamWaitEvent(ss, prev->join, 0));
-      }
-      HostTimer ht(&c->hp_sort);
-      HIPCHK(c, (ksrs::sort<uint64_t, false>(c->sort_ws_tail, S.d_pairs, d_pairs2, nullptr, nullptr, (size_t)n_pairs, std::min(56u, end_bit), ss, &sp,
-                                             nullptr, F.seq_bits)));
-      HIPCHK(c, hipEventRecord(S.sorted, ss));
-      HIPCHK(c, hipStreamWaitEvent(st, S.sorted, 0));
-    } else if ((rc = sort_keys(c, S.d_pairs, d_pairs2, n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) {
-      return rc;
-    }
-    c->last_tail_of_parity[par] = &S;
+    if ((rc = sort_keys(c, S.d_pairs, d_pairs2, n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
     stage_mark(c, set, 8);
     const uint32_t ab = (uint32_t)((n_pairs + 255) / 256);
-    const uint32_t run_tile = kRunPer * c->run_threads;
-    const uint32_t rb = (uint32_t)((n_pairs + run_tile - 1) / run_tile);
+    // k_apply_runs: 256 threads (tiles of 1024 pairs), not 512 (tiles of 2048).  Measured at 1280x720 / 2 cm beside the long-run
+    // kernels: 2.45 vs 3.08 ms, the frame 5.98 vs 6.26 ms (profiles/r06_c4_merged_ab.txt) — a workgroup of one wavefront per SIMD
+    // finds room where one of two per SIMD does not
+    const uint32_t rb = (uint32_t)((n_pairs + kRunPer * 256u - 1) / (kRunPer * 256u));
     const bool by_runs = n_pairs >= c->apply_runs_min_pairs;
     const uint32_t lb = (uint32_t)std::min<unsigned long long>(n_pairs / kLongRun + 1, 4096);
     const bool time_apply = set >= 0 && c->pset[set].apply;
     if (time_apply) c->pset[set].applied = true;
     // long runs (voxels next to the sensor) are listed first; then the two update kernels run side by side:
     // k_apply on the tail stream, k_apply_long on its own stream (disjoint voxels)
-    hipStream_t sl = c->stream_long ? c->stream_long : st;
-    hipStream_t sx = (sl != st && c->stream_xlong) ? c->stream_xlong : nullptr;
+    hipStream_t sl = c->stream_long;
+    hipStream_t sx = c->stream_xlong;
     unsigned long long* const d_xlong_list = sx ? d_long_list + (c->cap_pairs / kLongRunLanes + 64) : nullptr;
-    const bool lanes_on = by_runs && sl != st && sx && c->long_lanes && n_pairs >= c->long_lanes_min_pairs;
+    const bool lanes_on = by_runs && sx && c->long_lanes && n_pairs >= c->long_lanes_min_pairs;
     // ("long" could begin at kLongRunLanes = 17 updates where the lanes kernel takes the long runs — k_find_long, k_long_measure and
     // k_apply_runs take the threshold as an argument — but measured at 1280x720 / 2 cm it buys nothing: k_apply_runs 2.83 vs 2.79 ms,
-    // the lanes kernel 1.47 vs 0.93 ms, the frame 6.42 vs 6.24 ms: profiles/r06_c4_merged_ab.txt.  KS_LONG_MIN=16 selects it.)
-    const uint32_t long_min = (lanes_on && c->long_min_lanes) ? kLongRunLanes : kLongRun;
+    // the lanes kernel 1.47 vs 0.93 ms, the frame 6.42 vs 6.24 ms: profiles/r06_c4_merged_ab.txt.)
     // k_apply_runs decides which runs are its own by itself: the listing of the long runs (a pass over all pairs, 0.3 ms at
     // 1280x720 / 2 cm) then runs BESIDE it, on the long-run stream, instead of in front of it
-    const bool find_beside = by_runs && sl != st && sx;
+    const bool find_beside = by_runs && sx;
     const dim3 find_grid((uint32_t)((n_pairs + 256 * kFindLongItems - 1) / (256 * kFindLongItems)));
     if (!find_beside)
       hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, st, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
-                         S.d_counters, long_min);
+                         S.d_counters, kLongRun);
     const uint32_t xb = (uint32_t)std::min<unsigned long long>(n_pairs / kXLongRun + 1, 512);
-    if (sl != st) {
-      // the previous frame's long runs end before any voxel of this frame is touched
-      if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
-      c->pending_join = nullptr;
-      HIPCHK(c, hipEventRecord(S.fork, st));
-      HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
-      if (lanes_on) HIPCHK(c, hipMemsetAsync(c->d_long_hdr_[par], 0, sizeof(LongHdr), sl));
-      if (find_beside) {
-        hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
-                           S.d_counters, long_min);
-        HIPCHK(c, hipEventRecord(S.found, sl));
-        HIPCHK(c, hipStreamWaitEvent(sx, S.found, 0));
-      } else if (sx) {
-        HIPCHK(c, hipStreamWaitEvent(sx, S.fork, 0));
-      }
+    // the previous frame's long runs end before any voxel of this frame is touched
+    if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
+    c->pending_join = nullptr;
+    HIPCHK(c, hipEventRecord(S.fork, st));
+    HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
+    if (lanes_on) HIPCHK(c, hipMemsetAsync(c->d_long_hdr_[par], 0, sizeof(LongHdr), sl));
+    if (find_beside) {
+      hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
+                         S.d_counters, kLongRun);
+      HIPCHK(c, hipEventRecord(S.found, sl));
+      HIPCHK(c, hipStreamWaitEvent(sx, S.found, 0));
+    } else if (sx) {
+      HIPCHK(c, hipStreamWaitEvent(sx, S.fork, 0));
     }
-    // k_apply_runs on a stream of its own (pipelined contexts with the long-run streams; not while the stages are being timed):
-    // the sort is bound by HBM, this kernel by resident workgroups — the next frame's sort runs beside it instead of behind it.
-    // It is ordered like the long-run kernels: after this frame's fork, before S.join (which the next frame's fork waits for).
-    const bool apply_beside = find_beside && c->stream_apply && c->defer_join && !(set >= 0 && c->pset[set].stages);
-    hipStream_t sa = apply_beside ? c->stream_apply : st;
-    if (apply_beside) HIPCHK(c, hipStreamWaitEvent(sa, S.fork, 0));
-#define KS_LAUNCH_RUNS(MODE, MERGED, TH)                                                                              \
-  if (time_apply)                                                                                                     \
-    hipExtLaunchKernelGGL((k_apply_runs<MODE, MERGED, TH>), dim3(rb), dim3(TH), 0, sa, c->pset[set].k0, c->pset[set].k1, \
-                          0, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut, long_min);       \
-  else                                                                                                                \
-    hipLaunchKernelGGL((k_apply_runs<MODE, MERGED, TH>), dim3(rb), dim3(TH), 0, sa, F, n_pairs, sp, S.d_rays,          \
-                       S.d_deltas, c->table, c->pool, c->d_label_lut, long_min)
 #define KS_LAUNCH_APPLY_M(MODE, MERGED)                                                                              \
-  if (by_runs && c->run_threads == 256u) {                                                                           \
-    KS_LAUNCH_RUNS(MODE, MERGED, 256u);                                                                              \
-  } else if (by_runs) {                                                                                              \
-    KS_LAUNCH_RUNS(MODE, MERGED, 512u);                                                                              \
-  }                                                                                                                  \
+  if (by_runs && time_apply)                                                                                         \
+    hipExtLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, c->pset[set].k0,           \
+                          c->pset[set].k1, 0, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut, \
+                          kLongRun);                                                                                  \
+  else if (by_runs)                                                                                                  \
+    hipLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, F, n_pairs, sp, S.d_rays,     \
+                       S.d_deltas, c->table, c->pool, c->d_label_lut, kLongRun);                                      \
   else if (time_apply)                                                                                               \
     hipExtLaunchKernelGGL((k_apply<MODE, MERGED>), dim3(ab), dim3(256), 0, st, c->pset[set].k0, c->pset[set].k1, 0,   \
                           F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut, d_long_list,       \
@@ -1772,22 +1654,16 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     hipLaunchKernelGGL(k_apply_xlong<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, sp, S.d_rays, S.d_deltas,            \
                        c->table, c->pool, c->d_label_lut, d_xlong_list, (const uint32_t*)&S.d_counters->n_xlong);      \
   if (lanes_on) {                                                                                                    \
-    const uint32_t cap_long = (uint32_t)(n_pairs / (long_min + 1) + 1);                                               \
+    const uint32_t cap_long = (uint32_t)(n_pairs / (kLongRun + 1) + 1);                                               \
     hipLaunchKernelGGL(k_long_measure, dim3((cap_long + 255) / 256), dim3(256), 0, sl, F.seq_bits, n_pairs,           \
-                       (const uint64_t*)sp, d_long_list, (const Counters*)S.d_counters, c->d_long_hdr_[par], long_min); \
+                       (const uint64_t*)sp, d_long_list, (const Counters*)S.d_counters, c->d_long_hdr_[par], kLongRun); \
     hipLaunchKernelGGL(k_long_bucket, dim3((cap_long + 255) / 256), dim3(256), 0, sl,                                 \
                        (const unsigned long long*)d_long_list, (const Counters*)S.d_counters, c->d_long_hdr_[par],    \
                        c->d_long_sorted_[par]);                                                                        \
-    if (c->lanes_depth == 4u)                                                                                        \
-      hipLaunchKernelGGL((k_apply_long_lanes<MODE, 4u>), dim3((cap_long / 64 + kLongClasses + 3) / 4), dim3(256), 0, sl, F, \
-                         (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas, c->table, c->pool,   \
-                         (const uint32_t*)c->d_label_lut, (const LongHdr*)c->d_long_hdr_[par],                         \
-                         (const unsigned long long*)c->d_long_sorted_[par]);                                           \
-    else                                                                                                             \
-      hipLaunchKernelGGL((k_apply_long_lanes<MODE, 6u>), dim3((cap_long / 64 + kLongClasses + 3) / 4), dim3(256), 0, sl, F, \
-                         (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas, c->table, c->pool,   \
-                         (const uint32_t*)c->d_label_lut, (const LongHdr*)c->d_long_hdr_[par],                         \
-                         (const unsigned long long*)c->d_long_sorted_[par]);                                           \
+    hipLaunchKernelGGL((k_apply_long_lanes<MODE, 6u>), dim3((cap_long / 64 + kLongClasses + 3) / 4), dim3(256), 0, sl, F,   \
+                       (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas, c->table, c->pool,     \
+                       (const uint32_t*)c->d_label_lut, (const LongHdr*)c->d_long_hdr_[par],                           \
+                       (const unsigned long long*)c->d_long_sorted_[par]);                                             \
     hipLaunchKernelGGL(k_apply_long<MODE>, dim3(std::min<uint32_t>(lb, 1024u)), dim3(128), 0, sl, F, n_pairs, sp,     \
                        S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut,                                        \
                        (const unsigned long long*)c->d_long_sorted_[par], (const Counters*)S.d_counters,               \
@@ -1802,23 +1678,16 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     }
 #undef KS_LAUNCH_APPLY
 #undef KS_LAUNCH_APPLY_M
-#undef KS_LAUNCH_RUNS
-    if (sl != st) {
-      if (sx) {  // S.join stands for both lists
-        HIPCHK(c, hipEventRecord(S.join_x, sx));
-        HIPCHK(c, hipStreamWaitEvent(sl, S.join_x, 0));
-      }
-      if (apply_beside) {  // ... and for k_apply_runs
-        HIPCHK(c, hipEventRecord(S.applied, sa));
-        HIPCHK(c, hipStreamWaitEvent(sl, S.applied, 0));
-      }
-      HIPCHK(c, hipEventRecord(S.join, sl));
-      S.join_recorded = true;
-      // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
-      // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
-      if (c->defer_join && !(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
-      else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
+    if (sx) {  // S.join stands for both lists
+      HIPCHK(c, hipEventRecord(S.join_x, sx));
+      HIPCHK(c, hipStreamWaitEvent(sl, S.join_x, 0));
     }
+    HIPCHK(c, hipEventRecord(S.join, sl));
+    S.join_recorded = true;
+    // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
+    // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
+    if (!(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
+    else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
   } else {
     stage_mark(c, set, 7);
     stage_mark(c, set, 8);
@@ -1875,7 +1744,7 @@ int ensure_exchange(ks_ctx* c, size_t n) {
 int quiesce(ks_ctx* c) {
   const int rc = flush_pending(c);
   if (c->stream_tail != c->stream) HIPCHK(c, hipStreamSynchronize(c->stream_tail));
-  if (c->stream_long) HIPCHK(c, hipStreamSynchronize(c->stream_long));
+  HIPCHK(c, hipStreamSynchronize(c->stream_long));
   c->pending_join = nullptr;
   if (int rc2 = sync_march(c)) return rc2;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2270,7 +2139,6 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // 24: 0.541 / 0.461, 22 (23 phases): 0.523 / 0.465, 20: 0.525 / 0.484, 18: 0.558 / 0.544; coarser ones lose more (64: +12 %),
     // and so does a longest phase of 64 / 96 / 128 generations on top of any of them (equal steps at the end: +1 ... +8 %).
     c->cfg.early_out_phase_growth = 22;
-    if (const char* sg = dbg_env("KS_EXACT_SEED_GROWTH")) c->cfg.early_out_phase_growth = std::min(4096, std::max(16, atoi(sg)));   // tuning runs
   }
   {
     const char* hl = dbg_env("KS_EXACT_HOST_LOOP");   // diagnostics / A-B: the host-driven fix-point loop of round 3 for every frame
@@ -2288,10 +2156,6 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // place costs ~0.1 ms: measured on a ring of 40 frames, 8 rounds as launches 0.681 ms/frame, 14 rounds 0.569
     // (profiles/r05_bulk_rounds_ab.txt).  A finisher that is handed too long a list asks for more: eo_want_bulk.)
     c->eo_bulk_rounds = wide_rays ? 32 : 20;
-    if (const char* br = dbg_env("KS_EXACT_BULK_ROUNDS")) c->eo_bulk_rounds = std::min((int)kEoBulkMax, std::max(1, atoi(br)));
-    if (const char* tr = dbg_env("KS_EXACT_TRACE")) c->eo_trace = tr[0] == '1';
-    if (const char* sw = dbg_env("KS_EXACT_SWEEPS")) c->eo_sweeps = std::min(64, std::max(1, atoi(sw)));   // (tuning runs: any value gives the same map)
-    if (const char* so = dbg_env("KS_EXACT_SWEEP_ORDER")) c->eo_sweep_order = so[0] == '0' ? 0 : 1;
   }
   c->uses_early_out = uses_early_out;
   c->use_bundle_rank = cfg->method == KS_METHOD_MERGED && cfg->bundle_order == KS_BUNDLE_ORDER_REFERENCE;
@@ -2309,13 +2173,6 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     if (const char* kb = dbg_env("KS_KEY_WINDOW_BITS")) w = (unsigned)std::max(0, atoi(kb));   // tests: 1..10 = a window that small (the overflow path), 0 = 64-bit keys
     c->key_bits = (w >= 1 && w <= 10) ? w : 0;
   }
-  {
-    const char* hpf = dbg_env("KS_HOST_PROF");
-    c->host_prof = hpf && hpf[0] == '1';
-    const char* ng = dbg_env("KS_NO_GRAPH");
-    c->use_graphs = !(ng && ng[0] == '1');
-    c->defer_join = true;
-  }
   c->log_match = lm;
   c->log_non_match = lnm;
   c->voxel_size_inv = (float)(1.0 / cfg->voxel_size);  // TsdfIntegratorBase::setLayer
@@ -2330,14 +2187,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     }                                                                      \
   } while (0)
   CRCHK(hipSetDevice(cfg->device_id));
-  {
-    // (experiment, KS_FRONT_PRIO = 1 / 2: the front stream at the runtime's high / low priority)
-    const char* fp = dbg_env("KS_FRONT_PRIO");
-    int lo = 0, hi = 0;
-    (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-    if (fp && (fp[0] == '1' || fp[0] == '2')) CRCHK(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, fp[0] == '1' ? hi : lo));
-    else CRCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-  }
+  CRCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   // Frames in flight share nothing in stage B when a frame's early-out marks can never be seen by the next frame
   // (every frame bumps the set offset).  Then either (pipeline_frames < 8) every frame's stage B is its own launch
   // sequence and up to four of them run side by side on four streams, or (pipeline_frames = 8) stage B of four
@@ -2350,7 +2200,6 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // (measured, 640x480: a batch of 4 behind 8 frames of lag ~ four single-frame sequences on four streams behind 4
     // frames of lag; batches of 2 or 3 lose to both: DESIGN.md)
     c->batch = c->cfg.pipeline_frames >= 16 ? 8 : c->cfg.pipeline_frames >= 8 ? 4 : 1;
-    if (const char* bs = dbg_env("KS_BATCH")) c->batch = std::min(kBatchMax, std::max(1, atoi(bs)));  // diagnostics
   }
   // slots: the lag plus one batch being filled, a multiple of the batch (a batch then always starts on the same slots: its
   // captured launch sequence is found again)
@@ -2363,29 +2212,15 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // the four frames of a batch, and two batches alternate over two streams.)
     if (c->exact_early_out && c->n_march > 4) c->n_march = 4;
     if (c->exact_early_out && c->batch > 1) c->n_march = 2;
-    if (const char* ms = dbg_env("KS_MARCH_STREAMS")) c->n_march = std::min(kMarchStreams, std::max(1, atoi(ms)));  // diagnostics
-    {
-      auto mk = [&](hipStream_t* st, char) { return hipStreamCreateWithFlags(st, hipStreamNonBlocking); };
-      // without an early-out stage B is short (scan + emission): it follows stage A on the same stream, and the three
-      // streams that remain (A+B, T, long runs) map onto hardware queues of their own
-      if (!uses_early_out) {
-        c->n_march = 1;
-        c->stream_march_[0] = c->stream;
-        const char* et = dbg_env("KS_EMIT_ON_TAIL");   // A/B: 0 = always after stage A on the front stream, 1 = always on the tail stream
-        c->emit_on_tail = et && et[0] != '0';
-        if (et && et[0] == '1') c->emit_on_tail_max_pairs = ~0ull;
-      } else {
-        for (int i = 0; i < c->n_march; ++i) CRCHK(mk(&c->stream_march_[i], 'm'));
-      }
-      {
-        // (experiment, KS_TAIL_PRIO = 1 / 2: the tail stream at the runtime's high / low priority)
-        const char* tp = dbg_env("KS_TAIL_PRIO");
-        int lo = 0, hi = 0;
-        (void)hipDeviceGetStreamPriorityRange(&lo, &hi);
-        if (tp && (tp[0] == '1' || tp[0] == '2')) CRCHK(hipStreamCreateWithPriority(&c->stream_tail, hipStreamNonBlocking, tp[0] == '1' ? hi : lo));
-        else CRCHK(mk(&c->stream_tail, 't'));
-      }
+    // without an early-out stage B is short (scan + emission): it follows stage A on the same stream, and the three
+    // streams that remain (A+B, T, long runs) map onto hardware queues of their own
+    if (!uses_early_out) {
+      c->n_march = 1;
+      c->stream_march_[0] = c->stream;
+    } else {
+      for (int i = 0; i < c->n_march; ++i) CRCHK(hipStreamCreateWithFlags(&c->stream_march_[i], hipStreamNonBlocking));
     }
+    CRCHK(hipStreamCreateWithFlags(&c->stream_tail, hipStreamNonBlocking));
   } else {
     c->stream_march_[0] = c->stream_tail = c->stream;
   }
@@ -2394,61 +2229,19 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // share a hardware queue run one after the other: the heavy chains (stage B, stage T) must not share one.  With
     // the default of four hardware queues — one of which other streams of the process use — stage A and the long
     // runs (the two lightest: ~90 + ~65 us per 640x480 frame) are the pair that shares.
-    const char* nl = dbg_env("KS_NO_LONG_STREAM");   // diagnostics: long runs on the tail stream, after k_apply
-    if (nl && nl[0] == '1') c->stream_long = nullptr;
-    else CRCHK(hipStreamCreateWithFlags(&c->stream_long, hipStreamNonBlocking));
+    CRCHK(hipStreamCreateWithFlags(&c->stream_long, hipStreamNonBlocking));
     // the runs of more than kXLongRun updates (the voxels next to the sensor) on a stream of their own, four waves per run
     // (k_apply_xlong).  Same arithmetic, same order: the map does not change.  KS_XLONG=0 (diagnostics): one list, k_apply_long.
     if (const char* ar = dbg_env("KS_APPLY_RUNS")) c->apply_runs_min_pairs = atoi(ar) ? 0ull : ~0ull;   // tests / A-B: always / never
     const char* xp = dbg_env("KS_XLONG");
     c->xlong = xp ? atoi(xp) != 0 : true;
-    if (c->xlong && c->stream_long) CRCHK(hipStreamCreateWithFlags(&c->stream_xlong, hipStreamNonBlocking));
-    {
-      // A/B only (KS_APPLY_STREAM=1): measured, it LOSES — C4-merged 6.12 vs 6.00 ms/frame, C3 0.75 vs 0.60 (one more stream for the
-      // runtime's hardware queues to share) — so k_apply_runs stays on the tail stream
-      const char* as = dbg_env("KS_APPLY_STREAM");
-      if (c->stream_xlong && as && as[0] == '1') {
-        // (experiment: which hardware queue / pipe the stream lands on — streams created and never used in front of it)
-        if (const char* pad = dbg_env("KS_STREAM_PAD"))
-          for (int i = 0; i < atoi(pad) && i < 8; ++i) {
-            hipStream_t dummy = nullptr;
-            CRCHK(hipStreamCreateWithFlags(&dummy, hipStreamNonBlocking));
-            c->stream_pad.push_back(dummy);
-          }
-        CRCHK(hipStreamCreateWithFlags(&c->stream_apply, hipStreamNonBlocking));
-      }
-    }
+    if (c->xlong) CRCHK(hipStreamCreateWithFlags(&c->stream_xlong, hipStreamNonBlocking));
     if (const char* ll = dbg_env("KS_LONG_LANES")) {   // A/B: 0 = k_apply_long (two wavefronts per run) for all of them, 2 = lanes for frames of any size (tests)
       c->long_lanes = atoi(ll) != 0;
       if (atoi(ll) == 2) c->long_lanes_min_pairs = 0ull;
     }
-    if (c->stream_long && c->long_lanes)
+    if (c->long_lanes)
       for (int b = 0; b < 2; ++b) CRCHK(hipMalloc((void**)&c->d_long_hdr_[b], sizeof(LongHdr)));
-    if (const char* lm = dbg_env("KS_LONG_MIN")) c->long_min_lanes = atoi(lm) == 16;
-    {
-      // merged, pipelined: the long bundles' merge beside the bundle order (integrate_device_impl) — on the stream of the long
-      // voxel runs, which is idle four fifths of a 640x480 frame.  NOT on a stream of its own: a fifth active hardware queue
-      // costs every other kernel of the front stream ~40 us (measured: C3 1.24 ms/frame instead of 0.62; the kernel trace shows
-      // the bumps, with GPU_MAX_HW_QUEUES = 8 as with 4 — profiles/r06_bundle_stream_ab.txt).
-      // KS_BUNDLE_STREAM = 0: in line, 1: its own stream (the A/B above)
-      const char* bs = dbg_env("KS_BUNDLE_STREAM");
-      const int mode = bs ? atoi(bs) : 0;
-      if (c->cfg.method == KS_METHOD_MERGED && c->cfg.pipeline_frames && mode == 1) {
-        // (experiment: which hardware queue / pipe the stream lands on — streams created and never used in front of it)
-        if (const char* pad = dbg_env("KS_STREAM_PAD"))
-          for (int i = 0; i < atoi(pad) && i < 8 && !c->stream_apply; ++i) {
-            hipStream_t dummy = nullptr;
-            CRCHK(hipStreamCreateWithFlags(&dummy, hipStreamNonBlocking));
-            c->stream_pad.push_back(dummy);
-          }
-        CRCHK(hipStreamCreateWithFlags(&c->stream_bundles_own, hipStreamNonBlocking));
-      }
-      if (c->cfg.method == KS_METHOD_MERGED && c->cfg.pipeline_frames && mode != 0)
-        c->stream_bundles = c->stream_bundles_own ? c->stream_bundles_own : c->stream_long;
-    }
-    if (const char* sf = dbg_env("KS_SORT_FRONT")) c->sort_on_front = atoi(sf) != 0;
-    if (const char* ld = dbg_env("KS_LANES_DEPTH")) c->lanes_depth = atoi(ld) == 4 ? 4u : 6u;
-    if (const char* rt = dbg_env("KS_RUN_THREADS")) c->run_threads = atoi(rt) == 512 ? 512u : 256u;
     if (const char* xl = dbg_env("KS_XL_PARALLEL")) {   // A/B: 0 = every such run through k_apply_xlong, 2 = the integer-sum path for frames of any size (tests)
       c->xl_parallel = atoi(xl) != 0;
       if (atoi(xl) == 2) c->xl_min_pairs = 0ull;
@@ -2514,16 +2307,12 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     CRCHK(hipMalloc((void**)&S.d_F, sizeof(FrameParams)));
     std::memset(S.h_snap, 0, sizeof(HostSnap));
     CRCHK(hipEventCreateWithFlags(&S.a_done, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.bl_fork, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.bl_join, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.join, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.join_x, hipEventDisableTiming));
     CRCHK(hipEventCreateWithFlags(&S.found, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.applied, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.sorted, hipEventDisableTiming));
   }
 #undef CRCHK
   // pair buffers start at 4 updates per point of the largest cloud (a frame that needs more grows its buffer and
@@ -2547,11 +2336,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     ks_destroy(c);
     return KS_ERR_HIP;
   }
-  {
-    const char* nt = dbg_env("KS_NO_TAIL_THREAD");
-    c->use_tail_thread = c->cfg.pipeline_frames > 0 && !(nt && nt[0] == '1');
-    if (c->use_tail_thread) c->tail_thread = std::thread(tail_worker, c);
-  }
+  c->use_tail_thread = c->cfg.pipeline_frames > 0;
+  if (c->use_tail_thread) c->tail_thread = std::thread(tail_worker, c);
   *out = c;
   return KS_OK;
 }
@@ -2566,18 +2352,13 @@ void ks_destroy(ks_ctx* c) {
     c->tail_cv.notify_all();
     c->tail_thread.join();
   }
-  if (c->host_prof && c->frame_no)
-    fprintf(stderr, "[ks host prof] frames %llu: per frame us  A %.1f  B %.1f  T %.1f  (radix sort launches inside A+T: %.1f)\n",
-            (unsigned long long)c->frame_no, 1e6 * (c->hp_a - c->hp_b) / c->frame_no, 1e6 * c->hp_b / c->frame_no,
-            1e6 * c->hp_t / c->frame_no, 1e6 * c->hp_sort / c->frame_no);
   if (c->stream_tail && c->stream_tail != c->stream) (void)hipStreamSynchronize(c->stream_tail);
   for (auto sm : c->stream_march_)
     if (sm && sm != c->stream) (void)hipStreamSynchronize(sm);
   if (c->stream_long) (void)hipStreamSynchronize(c->stream_long);
-  if (c->stream_bundles_own) (void)hipStreamSynchronize(c->stream_bundles_own);
   if (c->stream) (void)hipStreamSynchronize(c->stream);
   void* ptrs[] = {c->table.ent, c->table.slot_keys, c->pool.vox, c->pool.updated, c->pool.dirty, c->d_start_set, c->d_observed_[0], c->d_observed_[1], c->d_observed_[2], c->d_observed_[3], c->d_observed_[4], c->d_observed_[5], c->d_observed_[6], c->d_observed_[7], c->d_observed_[8], c->d_observed_[9], c->d_observed_[10], c->d_observed_[11], c->d_observed_[12], c->d_observed_[13], c->d_observed_[14], c->d_observed_[15], c->d_color_lut,
-                  c->d_label_lut, c->d_xyz, c->d_rgba, c->d_labels, c->d_hash, c->d_skeys32, c->d_skeys32b, c->d_gpw, c->d_glc, c->d_ray_keys, c->d_long_list_[0], c->d_long_list_[1], c->d_blong, c->d_blong_merged, c->d_key_overflow, c->d_pkeys,
+                  c->d_label_lut, c->d_xyz, c->d_rgba, c->d_labels, c->d_hash, c->d_skeys32, c->d_skeys32b, c->d_gpw, c->d_glc, c->d_ray_keys, c->d_long_list_[0], c->d_long_list_[1], c->d_blong, c->d_key_overflow, c->d_pkeys,
                   c->d_pkeys2, c->d_pvals, c->d_pvals2, c->d_order, c->d_inv_order, c->d_okeys, c->d_okeys2, c->d_ovals,
                   c->d_pairs2_[0], c->d_pairs2_[1], c->d_state, c->d_xchg_u32, c->d_xchg_u64, c->d_retry_counters,
                   c->d_block_idx, c->d_tsdf_out, c->d_sem_out, c->d_vox_out, c->d_depth_blocks, c->d_img_depth, c->d_img_aux, c->d_bo_slab,
@@ -2609,11 +2390,7 @@ void ks_destroy(ks_ctx* c) {
     if (S.join) (void)hipEventDestroy(S.join);
     if (S.join_x) (void)hipEventDestroy(S.join_x);
     if (S.found) (void)hipEventDestroy(S.found);
-    if (S.applied) (void)hipEventDestroy(S.applied);
-    if (S.sorted) (void)hipEventDestroy(S.sorted);
     if (S.a_done) (void)hipEventDestroy(S.a_done);
-    if (S.bl_fork) (void)hipEventDestroy(S.bl_fork);
-    if (S.bl_join) (void)hipEventDestroy(S.bl_join);
   }
   for (auto& P : c->pset) {
     for (auto& e : P.ev)
@@ -2626,9 +2403,6 @@ void ks_destroy(ks_ctx* c) {
     if (sm && sm != c->stream) (void)hipStreamDestroy(sm);
   if (c->stream_long) (void)hipStreamDestroy(c->stream_long);
   if (c->stream_xlong) (void)hipStreamDestroy(c->stream_xlong);
-  if (c->stream_apply) (void)hipStreamDestroy(c->stream_apply);
-  if (c->stream_bundles_own) (void)hipStreamDestroy(c->stream_bundles_own);
-  for (hipStream_t d : c->stream_pad) (void)hipStreamDestroy(d);
   if (c->stream) (void)hipStreamDestroy(c->stream);
   delete c;
 }
@@ -3464,7 +3238,7 @@ static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   c->batch_slots.clear();
   c->owed = ks_frame_stats{};
   if (c->stream_tail != c->stream) HIPCHK(c, hipStreamSynchronize(c->stream_tail));
-  if (c->stream_long) HIPCHK(c, hipStreamSynchronize(c->stream_long));  // (long runs of the last frame: deferred join)
+  HIPCHK(c, hipStreamSynchronize(c->stream_long));  // (long runs of the last frame: deferred join)
   c->pending_join = nullptr;
   if (int rc = sync_march(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));

@@ -821,23 +821,16 @@ __device__ __forceinline__ bool eo2_sweep_ray(const EoView& E, EoCtl* ctl, const
   return changed;
 }
 
-// order 0: rays in integration order, a wavefront per ray (grid-stride).  order 1: a wavefront per (chain, segment of
-// kEoSweepSegment generations): it takes ITS rays one after the other, generation by generation, waiting for its own bit
-// flips before the next one — the reference's loop along a chain of neighbouring pixels, which is the direction changes
-// travel in (ks_k_march.h: the chains of the "mixed" order); chains and segments run side by side.
+// A wavefront per (chain, segment of kEoSweepSegment generations): it takes ITS rays one after the other, generation by
+// generation, waiting for its own bit flips before the next one — the reference's loop along a chain of neighbouring pixels,
+// which is the direction changes travel in (ks_k_march.h: the chains of the "mixed" order); chains and segments run side by
+// side.  (Sweeps in integration order, a wavefront per ray, lost to it: DESIGN.md 3.8.1.)
 // ctl->sw_prev = rays the previous sweep changed (k_eo2_sweep_next rotates the counters between two sweeps).
 constexpr uint32_t kEoSweepSegment = 128;
 // FULL and FILTERED sweeps: a full sweep looks at every ray (the first one, and the one that CONFIRMS the fixed point: nothing
 // else ends the iteration); a filtered sweep only at the rays flagged since they were last looked at (E.dirty: hints, see
 // eo2_sweep_ray) — after the first few sweeps a few thousand of 6.5e5.  ctl->sw_full says which kind runs (k_eo2_sweep_next).
-__device__ __forceinline__ bool eo2_sweep_wants(const EoView& E, uint32_t pos, bool full, uint32_t lane) {
-  // (the flag goes down before the ray is looked at: a change that lands meanwhile flags it again)
-  uint32_t d = 0u;
-  if (lane == 0) d = atomicExch(&E.dirty[pos], 0u);
-  d = (uint32_t)__shfl((int)d, 0);
-  return full || d != 0u;
-}
-__global__ void __launch_bounds__(256) k_eo2_sweep(EoBatch Bt, uint32_t order) {
+__global__ void __launch_bounds__(256) k_eo2_sweep(EoBatch Bt) {
   const EoView& E = Bt.v[blockIdx.y];
   EoCtl* ctl = E.ctl;
   if (ctl->fail || ctl->sw_prev == 0u) return;   // a full sweep changed nothing: the fixed point
@@ -845,51 +838,43 @@ __global__ void __launch_bounds__(256) k_eo2_sweep(EoBatch Bt, uint32_t order) {
   const FrameParams& F = *E.F;
   const uint32_t lane = lane_id(), w0 = blockIdx.x * 4u + (threadIdx.x >> 6), nw = gridDim.x * 4u;
   uint32_t changed = 0;
-  if (order == 0u) {
-    const uint32_t n = E.C->n_rays;
-    for (uint32_t r = w0; r < n; r += nw) {
-      const uint32_t pos = E.ray_list[r];
-      if (eo2_sweep_wants(E, pos, full, lane)) changed += eo2_sweep_ray(E, ctl, F, pos, lane) ? 1u : 0u;
-    }
-  } else {
-    const uint32_t n_chains = F.chains, n_gen = (F.n + n_chains - 1u) / n_chains;
-    const uint32_t n_seg = (n_gen + kEoSweepSegment - 1u) / kEoSweepSegment;
-    for (uint32_t w = w0; w < n_chains * n_seg; w += nw) {
-      // (segment-major: the workgroups that start first hold the chains' first segments)
-      const uint32_t chain = w % n_chains, seg = w / n_chains;
-      const uint32_t g1 = (seg + 1u) * kEoSweepSegment < n_gen ? (seg + 1u) * kEoSweepSegment : n_gen;
-      for (uint32_t g0 = seg * kEoSweepSegment; g0 < g1; g0 += 64u) {
-        const uint32_t g = g0 + lane;
-        const uint64_t p = (uint64_t)g * n_chains + chain;
-        // The flags of the segment's next 64 rays, all lanes at once (one atomic per ray, one after the other, is what a
-        // filtered sweep with a handful of flagged rays would otherwise consist of); a flagged ray's flag goes down BEFORE the
-        // rays are looked at, so a change that lands while the wavefront is on its way flags the ray again for the next sweep.
-        // A ray that CHANGES is what flags the rays behind it — most of all its own chain's next ray: that one is looked at
-        // whatever its flag says, and the flags of the rest of the group are read again (measured: reading them once per group
-        // lets a change travel one group per sweep along its chain — 45 sweeps per frame instead of 36).
-        const bool mine = g < g1 && p < F.n && E.live[p < F.n ? p : 0u] != 0;
-        auto take_flags = [&](uint32_t from) -> unsigned long long {   // the flags of the group's rays of generation >= from
-          bool want = false;
-          if (mine && g >= from && __hip_atomic_load(&E.dirty[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-            (void)atomicExch(&E.dirty[p], 0u);
-            want = true;
-          }
-          const unsigned long long m = __ballot(want);
-          if (m != 0ull) KS_WAIT_VMEM();
-          return m;
-        };
-        unsigned long long todo = full ? __ballot(mine) : 0ull;
-        todo |= take_flags(g0);
-        bool prev_changed = false;
-        for (unsigned long long rest = __ballot(mine); rest != 0ull; rest &= rest - 1ull) {
-          const uint32_t bit = (uint32_t)(__ffsll((long long)rest) - 1), gi = g0 + bit;
-          if (!((todo >> bit) & 1ull) && !prev_changed) continue;
-          prev_changed = eo2_sweep_ray(E, ctl, F, gi * n_chains + chain, lane);
-          if (prev_changed) {
-            ++changed;
-            KS_WAIT_VMEM();   // the bits of this ray's marks are in place before the chain's next ray looks
-            todo |= take_flags(gi + 1u);
-          }
+  const uint32_t n_chains = F.chains, n_gen = (F.n + n_chains - 1u) / n_chains;
+  const uint32_t n_seg = (n_gen + kEoSweepSegment - 1u) / kEoSweepSegment;
+  for (uint32_t w = w0; w < n_chains * n_seg; w += nw) {
+    // (segment-major: the workgroups that start first hold the chains' first segments)
+    const uint32_t chain = w % n_chains, seg = w / n_chains;
+    const uint32_t g1 = (seg + 1u) * kEoSweepSegment < n_gen ? (seg + 1u) * kEoSweepSegment : n_gen;
+    for (uint32_t g0 = seg * kEoSweepSegment; g0 < g1; g0 += 64u) {
+      const uint32_t g = g0 + lane;
+      const uint64_t p = (uint64_t)g * n_chains + chain;
+      // The flags of the segment's next 64 rays, all lanes at once (one atomic per ray, one after the other, is what a
+      // filtered sweep with a handful of flagged rays would otherwise consist of); a flagged ray's flag goes down BEFORE the
+      // rays are looked at, so a change that lands while the wavefront is on its way flags the ray again for the next sweep.
+      // A ray that CHANGES is what flags the rays behind it — most of all its own chain's next ray: that one is looked at
+      // whatever its flag says, and the flags of the rest of the group are read again (measured: reading them once per group
+      // lets a change travel one group per sweep along its chain — 45 sweeps per frame instead of 36).
+      const bool mine = g < g1 && p < F.n && E.live[p < F.n ? p : 0u] != 0;
+      auto take_flags = [&](uint32_t from) -> unsigned long long {   // the flags of the group's rays of generation >= from
+        bool want = false;
+        if (mine && g >= from && __hip_atomic_load(&E.dirty[p], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
+          (void)atomicExch(&E.dirty[p], 0u);
+          want = true;
+        }
+        const unsigned long long m = __ballot(want);
+        if (m != 0ull) KS_WAIT_VMEM();
+        return m;
+      };
+      unsigned long long todo = full ? __ballot(mine) : 0ull;
+      todo |= take_flags(g0);
+      bool prev_changed = false;
+      for (unsigned long long rest = __ballot(mine); rest != 0ull; rest &= rest - 1ull) {
+        const uint32_t bit = (uint32_t)(__ffsll((long long)rest) - 1), gi = g0 + bit;
+        if (!((todo >> bit) & 1ull) && !prev_changed) continue;
+        prev_changed = eo2_sweep_ray(E, ctl, F, gi * n_chains + chain, lane);
+        if (prev_changed) {
+          ++changed;
+          KS_WAIT_VMEM();   // the bits of this ray's marks are in place before the chain's next ray looks
+          todo |= take_flags(gi + 1u);
         }
       }
     }
@@ -901,7 +886,7 @@ __global__ void __launch_bounds__(64) k_eo2_sweep_next(EoBatch Bt) {
   EoCtl* ctl = Bt.v[blockIdx.x].ctl;
   if (threadIdx.x != 0 || ctl->fail || ctl->sw_prev == 0u) return;
   const uint32_t i = ctl->rounds, chg = ctl->sw_cur;
-  ctl->dense_chg[i & 31u] = chg | (ctl->sw_full ? 0x80000000u : 0u);   // (statistics: KS_EXACT_TRACE; bit 31: a full sweep)
+  ctl->dense_chg[i & 31u] = chg | (ctl->sw_full ? 0x80000000u : 0u);   // (statistics; bit 31: a full sweep)
   ctl->rounds = i + 1u;
   // a full sweep that changed nothing ends the iteration; a filtered one that changed nothing asks for the full one
   if (ctl->sw_full) {

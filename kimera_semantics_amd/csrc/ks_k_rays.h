@@ -244,8 +244,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(FrameParams F, const floa
   if (head) {
     // a bundle's first point in integration order: its insertion
     if (bo_flag) bo_flag[svals[i] + (uint32_t)(key >> 63) * F.n] = 1u;
-    // the bundles of >= kLongRun points (a handful per frame), listed here so that their merge can start before the
-    // bundle order is known (k_bundles_long beside k_bo_* and k_bundles)
+    // the bundles of >= kLongRun points (a handful per frame), listed here for the long-bundle workgroups of k_bundles_all
     if (is_long) long_list[atomicAdd(&C->n_long_bundles, 1u)] = i;
   }
   const uint32_t idx = point_order(F, order, svals[i]);
@@ -261,7 +260,7 @@ __global__ void __launch_bounds__(256) k_gather_sorted(FrameParams F, const floa
 // K5 (merged): bundle merge — running weighted mean of point_C, colour blend, label histogram,
 // log-likelihood increment.  [K:src/semantic_tsdf_integrator_merged.cpp:248-287]
 //   k_bundles      : one lane per bundle of < kLongRun points
-//   k_bundles_long : one wavefront per larger bundle (a surface close to the sensor puts
+//   k_bundles_all  : the same, plus two wavefronts per larger bundle (a surface close to the sensor puts
 //                    thousands of pixels into one 5 cm voxel)
 __device__ __forceinline__ void finish_bundle(const FrameParams& F, f3 mp, float mw, uint32_t merged_color,
                                               bool clearing, int n_labels, int the_label, float c, RayDesc* out,
@@ -307,7 +306,7 @@ __device__ __forceinline__ void bundles_body(const FrameParams& F, const uint64_
     head = (key != kEmpty64) && (i == 0 || skeys[i - 1] != key);
     if (head) is_long = (i + kLongRun < F.n) && (skeys[i + kLongRun] == key);
   }
-  const bool work = head && !is_long;   // (the long ones: listed by k_gather_sorted, merged by k_bundles_long)
+  const bool work = head && !is_long;   // (the long ones: listed by k_gather_sorted, merged by bundles_long_body)
   if (work) {
     const bool clearing = (key >> 63) != 0;
     uint32_t merged_color = 0;
@@ -396,8 +395,6 @@ __device__ __forceinline__ void bundle_long_finish(const FrameParams& F, uint64_
   }
 }
 
-constexpr uint32_t kBundleLongRec = 32;   // floats per merged long bundle between k_bundles_long and k_bundles_long_finish
-
 // Two wavefronts per long bundle (>= kLongRun points in one voxel: thousands when a wall is close).  The merge is the
 // reference's serial recurrence [K:src/semantic_tsdf_integrator_merged.cpp:231-262 via voxblox's weighted mean]:
 //     den = w + pw;  mean = (mean * w + p * pw) / den;  w = den           (per point, in input order, f32, no FMA)
@@ -409,11 +406,10 @@ constexpr uint32_t kBundleLongRec = 32;   // floats per merged long bundle betwe
 //           4-byte read per point, requested eight points ahead, then five dependent operations per point (multiply, add,
 //           and the three of the division by a known reciprocal).  The exponent-window test of that division is taken
 //           off the chain: eight points are applied without it, and repeated one by one if any of them fell outside.
-template <bool FINISH>
 __device__ __forceinline__ void bundles_long_body(const FrameParams& F, const uint64_t* __restrict__ skeys,
                                                   const uint32_t* __restrict__ svals, const float4* __restrict__ g_pw,
                                                   const uint2* __restrict__ g_lc, const uint32_t* __restrict__ long_list,
-                                                  float* __restrict__ merged, RayDesc* __restrict__ rays,
+                                                  RayDesc* __restrict__ rays,
                                                   float* __restrict__ deltas, uint32_t* __restrict__ ray_list,
                                                   uint64_t* __restrict__ ray_keys, uint32_t* __restrict__ cnt, const BoCtx& X,
                                                   bool use_rank, Counters* C, uint32_t block, uint32_t n_blocks) {
@@ -574,25 +570,11 @@ __device__ __forceinline__ void bundles_long_body(const FrameParams& F, const ui
       }
     }
     __syncthreads();  // wave 1 has the merged point
-    if (FINISH) {
-      // (the bundle order is known: k_bundles_all, after k_bo_*)
-      const f3 mp = {s_mp[0], s_mp[1], s_mp[2]};
-      bundle_long_finish(F, skeys[start], start, freq, mp, __float_as_uint(s_mp[3]), mw, svals, rays, deltas, ray_list, ray_keys, cnt, X, use_rank, C);
-    } else {
-      // the merged bundle for k_bundles_long_finish: label counts in lanes 0..20, then the point, the weight, the colour
-      float v = freq;
-      if (lane >= kNumLabels) v = (lane < kNumLabels + 4) ? s_mp[lane - kNumLabels] : mw;
-      if (lane <= kNumLabels + 4) merged[(size_t)run * kBundleLongRec + (uint32_t)lane] = v;
-    }
+    // (the bundle order is known: k_bundles_all, after k_bo_*)
+    const f3 mp = {s_mp[0], s_mp[1], s_mp[2]};
+    bundle_long_finish(F, skeys[start], start, freq, mp, __float_as_uint(s_mp[3]), mw, svals, rays, deltas, ray_list, ray_keys, cnt, X, use_rank, C);
     __syncthreads();  // LDS free for the next bundle
   }
-}
-__global__ void __launch_bounds__(128) k_bundles_long(FrameParams F, const uint64_t* __restrict__ skeys,
-                                                      const float4* __restrict__ g_pw, const uint2* __restrict__ g_lc,
-                                                      const uint32_t* __restrict__ long_list, float* __restrict__ merged,
-                                                      Counters* C) {
-  bundles_long_body<false>(F, skeys, nullptr, g_pw, g_lc, long_list, merged, nullptr, nullptr, nullptr, nullptr, nullptr, BoCtx{}, false, C,
-                           blockIdx.x, gridDim.x);
 }
 
 // Both in one launch, after the bundle order: the first n_long_blocks workgroups walk the long bundles (a serial chain each,
@@ -605,30 +587,10 @@ __global__ void __launch_bounds__(128) k_bundles_all(FrameParams F, const uint64
                                                      uint32_t* __restrict__ cnt, BoCtx X, bool use_rank, Counters* C,
                                                      uint32_t n_long_blocks) {
   if (blockIdx.x < n_long_blocks)
-    bundles_long_body<true>(F, skeys, svals, g_pw, g_lc, long_list, nullptr, rays, deltas, ray_list, ray_keys, cnt, X, use_rank, C, blockIdx.x,
-                            n_long_blocks);
+    bundles_long_body(F, skeys, svals, g_pw, g_lc, long_list, rays, deltas, ray_list, ray_keys, cnt, X, use_rank, C, blockIdx.x,
+                      n_long_blocks);
   else
     bundles_body(F, skeys, svals, g_pw, g_lc, rays, deltas, ray_list, ray_keys, cnt, X, use_rank, C, blockIdx.x - n_long_blocks);
-}
-
-// ... and what needs the bundle's integration id (k_bo_*): the ray descriptor, the increments, the lists.  A wavefront per bundle.
-__global__ void __launch_bounds__(256) k_bundles_long_finish(FrameParams F, const uint64_t* __restrict__ skeys,
-                                                             const uint32_t* __restrict__ svals,
-                                                             const uint32_t* __restrict__ long_list,
-                                                             const float* __restrict__ merged, RayDesc* __restrict__ rays,
-                                                             float* __restrict__ deltas, uint32_t* __restrict__ ray_list,
-                                                             uint64_t* __restrict__ ray_keys, uint32_t* __restrict__ cnt,
-                                                             BoCtx X, bool use_rank, Counters* C) {
-  const uint32_t n_long = C->n_long_bundles;
-  const int lane = (int)lane_id();
-  for (uint32_t run = blockIdx.x * 4u + (threadIdx.x >> 6); run < n_long; run += gridDim.x * 4u) {
-    const uint32_t start = long_list[run];
-    const float* rec = merged + (size_t)run * kBundleLongRec;
-    const float freq = lane < kNumLabels ? rec[lane] : 0.0f;
-    const f3 mp = {rec[kNumLabels], rec[kNumLabels + 1], rec[kNumLabels + 2]};
-    bundle_long_finish(F, skeys[start], start, freq, mp, __float_as_uint(rec[kNumLabels + 3]), rec[kNumLabels + 4], svals, rays, deltas, ray_list,
-                       ray_keys, cnt, X, use_rank, C);
-  }
 }
 
 }  // namespace ksk

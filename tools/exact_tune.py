@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Times the exact early-out mode (event-driven fix point) at a bench workload for a list of settings, on the GPU:
-   python tools/exact_tune.py [C2|C4-fast] "pipe=8" "pipe=8,KS_EXACT_BULK_ROUNDS=10" "pipe=4,KS_EXACT_SEED_GROWTH=64" "pipe=0,growth=32" ...
-growth=<n>: the ordered-phase schedule alone (early_out_phase_growth = n), for comparison."""
+   python tools/exact_tune.py [C2|C4-fast] "pipe=8" "pipe=4" "pipe=0,growth=32" "pipe=0,KS_DEBUG=1,KS_EXACT_HOST_LOOP=1" ...
+growth=<n>: the ordered-phase schedule alone (early_out_phase_growth = n), for comparison; any other key=value is set in the
+environment while the context is created."""
 import os
 import sys
 import time

@@ -1,5 +1,4 @@
-"""Wall time of every integrate call of a pipelined stream (C2, default mode): which calls wait, and for how long.
-KS_HOST_PROF=1 adds the library's own account of the host time spent enqueueing stage A / B / T."""
+"""Wall time of every integrate call of a pipelined stream (C2, default mode): which calls wait, and for how long."""
 import os
 import sys
 import time
@@ -7,8 +6,6 @@ import time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-os.environ.setdefault("KS_DEBUG", "1")
-os.environ.setdefault("KS_HOST_PROF", "1")
 
 
 def main():
