@@ -35,7 +35,8 @@ enum {
   KS_ERR_POOL_FULL = -5,     /* voxel-tile pool exhausted (raise ks_config.max_tiles) */
   KS_ERR_INDEX_RANGE = -6,   /* a voxel index left the +-2^23 range the device packs */
   KS_ERR_NO_DEVICE = -7,
-  KS_ERR_UNSUPPORTED = -8
+  KS_ERR_UNSUPPORTED = -8,
+  KS_ERR_PEER_FAILED = -9    /* a collective call: another rank failed (the text names it); nothing was applied on this rank */
 };
 
 enum { KS_METHOD_FAST = 0, KS_METHOD_MERGED = 1 };          /* factory names "fast"/"merged", semantic_tsdf_integrator_factory.h:49-54 */
@@ -295,19 +296,41 @@ typedef struct ks_reduce_stats {
 } ks_reduce_stats;
 int ks_reduce(ks_ctx* ctx, void* rccl_comm, int rank, int world, ks_reduce_stats* stats);
 
-/* EXACT frame-sharded integration of `fast` — one ROUND: `world` consecutive frames, frame first_frame + r marched by rank r.
- * COLLECTIVE: every rank calls it once per round (a rank without a frame passes n = 0), rounds in frame order.
- * `marcher` casts this rank's frame — stage A, the early-out, the emission, with the approximate sets' offsets of that GLOBAL
- * frame number — against a slot numbering of its own and evaluates the state-independent half of every update; each update
- * travels to the rank that owns its voxel's tile (ks_tile_owner) as 20 bytes { tile key << 9 | voxel in tile, info byte <<
- * 24 | integration position, sdf, update weight }; `owner` applies the frames of the round in frame order.  The tiles a rank
- * owns are then, bit for bit, what ONE context integrating all frames in order holds for them (new: the reference is a
- * single process; replaces merging per-rank maps with ks_reduce, which is a different arithmetic — SURVEY.md par. 8e).
- * Both contexts: method fast, colours from the labels, pipeline_frames = 0, "mixed" order, clear_checks_every_n_frames = 1 (or the
- * early-out off); same configuration on every rank; `marcher` is used for nothing else (its map stays empty of data).
- * origin_voxel_touched: a frame of the round updated the voxel whose index hashes to 0 (the world origin) — the one place
- * where the reference's approximate sets couple frames (their zero-initialised slots "contain" hash 0), i.e. where the
- * result may differ from the sequential one.  world = 1 needs no communicator. */
+/* EXACT frame-sharded integration of `fast` or `merged` — one ROUND: `world` consecutive frames, frame first_frame + r marched
+ * by rank r.  COLLECTIVE: every rank calls it once per round (a rank without a frame passes n = 0), rounds in frame order.
+ * `marcher` casts this rank's frame against a slot numbering of its own and evaluates the state-independent half of every
+ * update; each update travels to the rank that owns its voxel's tile (ks_tile_owner) as a 20-byte record; `owner` applies the
+ * frames of the round in frame order.  The tiles a rank owns are then, bit for bit, what ONE context integrating all frames in
+ * order holds for them (new: the reference is a single process; replaces merging per-rank maps with ks_reduce, which is a
+ * different arithmetic — SURVEY.md par. 8e).  Both contexts are created with the same method and the same configuration on every
+ * rank; `marcher` is used for nothing else (its map stays empty of data).  world = 1 needs no communicator.
+ *   method fast    stage A, the early-out, the emission, with the approximate sets' offsets of that GLOBAL frame number (the
+ *                  frames of the other ranks advance the marcher's bookkeeping like empty clouds).
+ *                  record = { tile key << 9 | voxel in tile, info byte << 24 | integration position, sdf, update weight }.
+ *                  Colours from the labels, pipeline_frames = 0, "mixed" order, clear_checks_every_n_frames = 1 (or the early-out
+ *                  off).  origin_voxel_touched: a frame of the round updated the voxel whose index hashes to 0 (the world
+ *                  origin) — the one place where the reference's approximate sets couple frames (their zero-initialised slots
+ *                  "contain" hash 0), i.e. where the result may differ from the sequential one.
+ *   method merged  bundling, bundle order (either ks_config.bundle_order), bundle merge, ray casting, anti-grazing and the
+ *                  clearing pass depend on nothing but the frame: no empty frames are marched for the other ranks, and
+ *                  origin_voxel_touched is always 0.  sdf and update weight come from the bundle's MERGED point and weight.
+ *                  record = { tile key << 9 | voxel in tile, info byte << 24 | bundle number, sdf, update weight }, where the
+ *                  marcher numbers the frame's bundles that have an update 0 .. B-1 (info byte: label | kind << 5 | clearing
+ *                  << 7; kind 1 = pure-label, 2 = mixed-label bundle).  The semantic increments travel as the marcher computed
+ *                  them, in two tables per frame that go, whole, to every peer that receives a record of the frame:
+ *                    bundle table  B x 8 bytes { d_match, d_non }; a mixed-label bundle: { its row in the mixed table (u32), - }
+ *                    mixed table   84 bytes (21 f32) per mixed-label bundle
+ *                  Colours from the labels (KS_COLOR_MODE_COLOR blends by the voxel's weight at each update, which a record does
+ *                  not carry: KS_ERR_UNSUPPORTED), pipeline_frames = 0; every integration_order_mode.  rays_cast = bundles.
+ * bytes_sent counts every byte that leaves the rank: records and, for `merged`, the tables once per receiving peer.
+ * A cloud of 2^24 points or more does not fit the record's 24-bit field: KS_ERR_INVALID_ARG (both methods).
+ * FAILURES.  What is the same on every rank by contract (the configuration, a missing librccl) is refused before anything is
+ * exchanged.  What can differ from rank to rank — a label >= 21, a cloud too large, rounds out of order, a context retired by an
+ * earlier failure — is carried in the round's count exchange: no rank is left waiting, the failing rank returns its own code,
+ * every other rank KS_ERR_PEER_FAILED with a text naming the rank and its code, and NO rank applies anything of the round.  A
+ * `merged` marcher is put back where it was (the round can be repeated by every rank); a `fast` marcher whose per-call state has
+ * already advanced cannot be, and is retired (every later call on it returns KS_ERR_INVALID_ARG).  A HIP / RCCL failure inside the
+ * exchange itself cannot be told to the peers (as with ks_reduce and any RCCL collective). */
 typedef struct ks_round_stats {
   uint64_t updates_marched, updates_applied, bytes_sent, origin_voxel_touched, rays_cast;
 } ks_round_stats;

@@ -22,6 +22,7 @@ KS_ORDER_MIXED, KS_ORDER_SORTED, KS_ORDER_MIXED_1024_GROUPS = 0, 1, 2   # includ
 KS_BUNDLE_ORDER_REFERENCE, KS_BUNDLE_ORDER_CANONICAL = 0, 1
 KS_EARLY_OUT_EXACT = 1   # value of KsConfig.early_out_phase_growth: the reference's serial early-out result
 KS_ERR_LABEL_RANGE, KS_ERR_PROBABILITY, KS_ERR_POOL_FULL, KS_ERR_NO_DEVICE, KS_ERR_UNSUPPORTED = -2, -3, -5, -7, -8
+KS_ERR_INVALID_ARG, KS_ERR_PEER_FAILED = -1, -9
 
 STAGES = ["points", "sort_points", "rays", "march", "emit", "sort_pairs", "apply", "apply_long"]
 
@@ -85,7 +86,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_io.h", "ks_device_math.h", "ks_radix_sort.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_device_math.h", "ks_radix_sort.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -382,7 +383,10 @@ class HipIntegrator:
 
     def integrate_round_exact(self, marcher: "HipIntegrator", rccl_comm, rank: int, world: int, first_frame: int, T_G_C, xyz, rgba, labels,
                               freespace=False) -> dict:
-        """self = the OWNER context of this rank; `marcher` casts this rank's frame of the round (ks_integrate_round_exact)."""
+        """self = the OWNER context of this rank; `marcher` casts this rank's frame of the round (ks_integrate_round_exact).
+        Both contexts `fast` or both `merged` (colours from the labels, pipeline_frames = 0).  COLLECTIVE: a rank whose frame fails
+        (a label >= 21, a cloud of 2^24 points or more, rounds out of order) tells its peers in the count exchange; it raises its own
+        error, the others KS_ERR_PEER_FAILED naming it, and no rank applies anything of that round."""
         T = np.ascontiguousarray(T_G_C, dtype=np.float32)
         n = 0 if xyz is None else len(xyz)
         x = None if xyz is None else np.ascontiguousarray(xyz, dtype=np.float32)

@@ -64,6 +64,7 @@ using namespace ksd;
 #include "ks_k_apply.h"
 #include "ks_k_apply_xl.h"
 #include "ks_k_shard.h"
+#include "ks_k_shard_merged.h"
 #include "ks_k_io.h"
 
 using namespace ksk;
@@ -356,6 +357,23 @@ struct ks_ctx {
   uint64_t* d_sh_pairs[2] = {nullptr, nullptr};
   uint32_t* d_sh_vals[2] = {nullptr, nullptr};
   size_t cap_sh_rx = 0;
+  // ... of `merged` (ks_k_shard_merged.h).  Marcher: bundle number by position, the frame's bundle table, its mixed-label rows
+  uint32_t* d_shm_bno = nullptr;
+  float2* d_shm_btab = nullptr;
+  uint32_t* d_shm_mpos = nullptr;
+  uint32_t* d_shm_cnt = nullptr;         // [0] bundles, [1] mixed-label bundles
+  size_t cap_shm_n = 0;
+  float* d_shm_mixed = nullptr;
+  size_t cap_shm_mixed = 0;
+  uint32_t shm_counts[2] = {0, 0};       // the last exported frame's
+  // owner: the tables received from the peers (one after the other, by source rank), the staged operands, the long runs
+  float2* d_shm_rx_btab = nullptr;
+  size_t cap_shm_rx_btab = 0;
+  float* d_shm_rx_mixed = nullptr;
+  size_t cap_shm_rx_mixed = 0;
+  float4* d_shm_ops = nullptr;
+  uint32_t* d_shm_long = nullptr;        // [cap / (kLongRun + 1) + 1] heads of the long runs, then the count
+  size_t cap_shm_ops = 0;
   // the runs of 33 .. 1024 updates a lane per run, bucketed by length over the frame (k_apply_long_lanes); by parity, like the lists
   bool long_lanes = true;
   unsigned long long long_lanes_min_pairs = 1ull << 24;
@@ -1382,6 +1400,16 @@ int shard_export_frame(ks_ctx* c, FrameSlot& S, unsigned long long n_pairs, hipS
     c->cap_sh = cap;
   }
   if (!c->d_sh_counts && (rc = dev_alloc(c, &c->d_sh_counts, 128))) return rc;
+  const bool merged = c->cfg.method == KS_METHOD_MERGED;
+  c->shm_counts[0] = c->shm_counts[1] = 0;
+  if (merged && (S.n > c->cap_shm_n || !c->d_shm_cnt)) {
+    const size_t cap = std::max<size_t>(S.n, 1 << 16);
+    if ((rc = dev_alloc(c, &c->d_shm_bno, cap))) return rc;
+    if ((rc = dev_alloc(c, &c->d_shm_btab, cap))) return rc;
+    if ((rc = dev_alloc(c, &c->d_shm_mpos, cap))) return rc;
+    if ((rc = dev_alloc(c, &c->d_shm_cnt, 2))) return rc;
+    c->cap_shm_n = cap;
+  }
   HIPCHK(c, hipMemsetAsync(c->d_sh_counts, 0, 128 * sizeof(uint32_t), st));
   std::memset(c->sh_counts, 0, sizeof(c->sh_counts));
   c->sh_exported = n_pairs;
@@ -1393,12 +1421,36 @@ int shard_export_frame(ks_ctx* c, FrameSlot& S, unsigned long long n_pairs, hipS
     uint64_t* sorted = nullptr;
     HIPCHK(c, (ksrs::sort<uint64_t, false>(c->sort_ws_tail, c->d_sh_okey[0], c->d_sh_okey[1], nullptr, nullptr, (size_t)n_pairs, 64, st,
                                            &sorted, nullptr, 56)));
-    hipLaunchKernelGGL(k_shard_gather, dim3(nb), dim3(256), 0, st, n_pairs, (const uint64_t*)sorted, (const uint64_t*)c->d_sh_gkey[0],
-                       (const uint32_t*)c->d_sh_seq[0], (const float*)c->d_sh_sdf[0], (const float*)c->d_sh_uw[0], c->d_sh_gkey[1],
-                       c->d_sh_seq[1], c->d_sh_sdf[1], c->d_sh_uw[1]);
+    if (merged) {
+      // the bundles that have an update are numbered; the records name the number, the two tables carry the increments
+      HIPCHK(c, hipMemsetAsync(c->d_shm_bno, 0, (size_t)S.n * sizeof(uint32_t), st));
+      HIPCHK(c, hipMemsetAsync(c->d_shm_cnt, 0, 2 * sizeof(uint32_t), st));
+      hipLaunchKernelGGL(k_shard_mark_bundles, dim3(nb), dim3(256), 0, st, n_pairs, (const uint32_t*)c->d_sh_seq[0], c->d_shm_bno);
+      hipLaunchKernelGGL(k_shard_bundle_table, dim3((uint32_t)((S.n + 255) / 256)), dim3(256), 0, st, (uint32_t)S.n, (const RayDesc*)S.d_rays,
+                         c->d_shm_bno, c->d_shm_btab, c->d_shm_mpos, c->d_shm_cnt);
+      hipLaunchKernelGGL(k_shard_gather_merged, dim3(nb), dim3(256), 0, st, n_pairs, (const uint64_t*)sorted, (const uint64_t*)c->d_sh_gkey[0],
+                         (const uint32_t*)c->d_sh_seq[0], (const float*)c->d_sh_sdf[0], (const float*)c->d_sh_uw[0], (const uint32_t*)c->d_shm_bno,
+                         c->d_sh_gkey[1], c->d_sh_seq[1], c->d_sh_sdf[1], c->d_sh_uw[1]);
+      HIPCHK(c, hipMemcpyAsync(c->shm_counts, c->d_shm_cnt, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    } else {
+      hipLaunchKernelGGL(k_shard_gather, dim3(nb), dim3(256), 0, st, n_pairs, (const uint64_t*)sorted, (const uint64_t*)c->d_sh_gkey[0],
+                         (const uint32_t*)c->d_sh_seq[0], (const float*)c->d_sh_sdf[0], (const float*)c->d_sh_uw[0], c->d_sh_gkey[1],
+                         c->d_sh_seq[1], c->d_sh_sdf[1], c->d_sh_uw[1]);
+    }
     HIPCHK(c, hipMemcpyAsync(c->sh_counts, c->d_sh_counts, 65 * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   }
   HIPCHK(c, hipStreamSynchronize(st));
+  if (merged && c->shm_counts[1]) {
+    const size_t nm = c->shm_counts[1];
+    if (nm > c->cap_shm_mixed) {
+      const size_t cap = std::max<size_t>(nm + nm / 2, 1024);
+      if ((rc = dev_alloc(c, &c->d_shm_mixed, cap * kNumLabels))) return rc;
+      c->cap_shm_mixed = cap;
+    }
+    hipLaunchKernelGGL(k_shard_mixed_rows, dim3((uint32_t)((nm * kNumLabels + 255) / 256)), dim3(256), 0, st, (uint32_t)nm,
+                       (const uint32_t*)c->d_shm_mpos, (const float*)S.d_deltas, c->d_shm_mixed);
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
   return KS_OK;
 }
 
@@ -2363,7 +2415,7 @@ void ks_destroy(ks_ctx* c) {
                   c->d_pairs2_[0], c->d_pairs2_[1], c->d_state, c->d_xchg_u32, c->d_xchg_u64, c->d_retry_counters,
                   c->d_block_idx, c->d_tsdf_out, c->d_sem_out, c->d_vox_out, c->d_depth_blocks, c->d_img_depth, c->d_img_aux, c->d_bo_slab,
                   c->d_eo_keys[0], c->d_eo_keys[1], c->d_eo_vals[0], c->d_eo_vals[1], c->d_eo_range, c->d_eo_plain, c->d_eo_lp, c->d_eo_bt,
-                  c->d_eo_state, c->d_xl_runs, c->d_xl_hdr, c->d_xl_chunks, c->d_xl_idx, c->d_xl_fb, c->d_long_sorted_[0], c->d_long_sorted_[1], c->d_long_hdr_[0], c->d_long_hdr_[1], c->d_sh_okey[0], c->d_sh_okey[1], c->d_sh_gkey[0], c->d_sh_gkey[1], c->d_sh_seq[0], c->d_sh_seq[1], c->d_sh_sdf[0], c->d_sh_sdf[1], c->d_sh_uw[0], c->d_sh_uw[1], c->d_sh_counts, c->d_sh_tk, c->d_sh_pairs[0], c->d_sh_pairs[1], c->d_sh_vals[0], c->d_sh_vals[1], c->d_rx_counts, c->d_tx_keys, c->d_rx_keys, c->d_tx_slots, c->d_tx_payload, c->d_rx_payload};
+                  c->d_eo_state, c->d_xl_runs, c->d_xl_hdr, c->d_xl_chunks, c->d_xl_idx, c->d_xl_fb, c->d_long_sorted_[0], c->d_long_sorted_[1], c->d_long_hdr_[0], c->d_long_hdr_[1], c->d_sh_okey[0], c->d_sh_okey[1], c->d_sh_gkey[0], c->d_sh_gkey[1], c->d_sh_seq[0], c->d_sh_seq[1], c->d_sh_sdf[0], c->d_sh_sdf[1], c->d_sh_uw[0], c->d_sh_uw[1], c->d_sh_counts, c->d_sh_tk, c->d_sh_pairs[0], c->d_sh_pairs[1], c->d_sh_vals[0], c->d_sh_vals[1], c->d_shm_bno, c->d_shm_btab, c->d_shm_mpos, c->d_shm_cnt, c->d_shm_mixed, c->d_shm_rx_btab, c->d_shm_rx_mixed, c->d_shm_ops, c->d_shm_long, c->d_rx_counts, c->d_tx_keys, c->d_rx_keys, c->d_tx_slots, c->d_tx_payload, c->d_rx_payload};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& S : c->slot) {
@@ -3044,9 +3096,16 @@ int ks_reduce(ks_ctx* c, void* rccl_comm, int rank, int world, ks_reduce_stats* 
   return KS_OK;
 }
 
-// Owner: one frame's records (of the tiles this rank owns, in integration order) into the map.
+// Owner: one frame's records (of the tiles this rank owns, in integration order) into the map.  `merged`: the frame's two
+// tables come with them (ks_k_shard_merged.h).
+struct ShardTables {
+  const float2* btab;
+  uint32_t n_bundles;
+  const float* mixed;
+  uint32_t n_mixed;
+};
 static int shard_apply_segment(ks_ctx* o, const uint64_t* d_gkey, const uint32_t* d_seq, const float* d_sdf, const float* d_uw, size_t n,
-                               size_t tiles_at_most) {
+                               size_t tiles_at_most, const ShardTables* mt = nullptr) {
   if (n == 0) return KS_OK;
   if (n >= (size_t)1 << 31) { o->err = "ks_integrate_round_exact: more than 2^31 updates of one frame for one owner"; return KS_ERR_INVALID_ARG; }
   int rc;
@@ -3058,6 +3117,12 @@ static int shard_apply_segment(ks_ctx* o, const uint64_t* d_gkey, const uint32_t
       if ((rc = dev_alloc(o, &o->d_sh_vals[b], cap))) return rc;
     }
     o->cap_sh_rx = cap;
+  }
+  if (mt && n > o->cap_shm_ops) {
+    const size_t cap = std::max<size_t>(n + n / 4, 1 << 18);
+    if ((rc = dev_alloc(o, &o->d_shm_ops, cap))) return rc;
+    if ((rc = dev_alloc(o, &o->d_shm_long, cap / (kLongRun + 1) + 2))) return rc;   // a long run has more than kLongRun updates
+    o->cap_shm_ops = cap;
   }
   hipStream_t st = o->stream;
   const uint32_t nb = (uint32_t)((n + 255) / 256);
@@ -3083,7 +3148,26 @@ static int shard_apply_segment(ks_ctx* o, const uint64_t* d_gkey, const uint32_t
   F.tsdf.sparsity_factor = cfg.sparsity_compensation_factor;
   F.tsdf.use_dropoff = cfg.use_weight_dropoff;
   F.tsdf.use_sparsity = cfg.use_sparsity_compensation_factor;
-  if (cfg.color_mode == KS_COLOR_MODE_SEMANTIC)
+  if (mt) {
+    // the operands in run order and the long runs' heads; then short runs a lane each, long runs two wavefronts each
+    uint32_t* const d_n_long = o->d_shm_long + (o->cap_shm_ops / (kLongRun + 1) + 1);
+    HIPCHK(o, hipMemsetAsync(d_n_long, 0, sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_shard_stage_merged, dim3(nb), dim3(256), 0, st, (uint32_t)n, mt->n_bundles, (const uint64_t*)kres, (const uint32_t*)vres, d_sdf,
+                       d_uw, mt->btab, o->d_shm_ops, o->d_shm_long, d_n_long);
+    const uint32_t lb = (uint32_t)std::min<size_t>(2 * (n / (kLongRun + 1) + 1), 4096);
+#define KS_LAUNCH_SHARD_MERGED(MODE)                                                                                                         \
+  hipLaunchKernelGGL(k_shard_apply_merged<MODE>, dim3(nb), dim3(256), 0, st, F.tsdf, (uint32_t)n, mt->n_mixed, (const uint64_t*)kres,         \
+                     (const float4*)o->d_shm_ops, mt->mixed, o->pool, (const uint32_t*)o->d_label_lut);                                      \
+  hipLaunchKernelGGL(k_shard_apply_merged_long<MODE>, dim3(lb), dim3(64), 0, st, F.tsdf, (uint32_t)n, mt->n_mixed, (const uint64_t*)kres,     \
+                     (const float4*)o->d_shm_ops, mt->mixed, o->pool, (const uint32_t*)o->d_label_lut, (const uint32_t*)o->d_shm_long,       \
+                     (const uint32_t*)d_n_long)
+    if (cfg.color_mode == KS_COLOR_MODE_SEMANTIC) {
+      KS_LAUNCH_SHARD_MERGED(KS_COLOR_MODE_SEMANTIC);
+    } else {
+      KS_LAUNCH_SHARD_MERGED(KS_COLOR_MODE_SEMANTIC_PROBABILITY);
+    }
+#undef KS_LAUNCH_SHARD_MERGED
+  } else if (cfg.color_mode == KS_COLOR_MODE_SEMANTIC)
     hipLaunchKernelGGL(k_shard_apply<KS_COLOR_MODE_SEMANTIC>, dim3(nb), dim3(256), 0, st, F, (uint32_t)n, (const uint64_t*)kres, (const uint32_t*)vres, d_sdf,
                        d_uw, o->pool, (const uint32_t*)o->d_label_lut);
   else
@@ -3094,82 +3178,157 @@ static int shard_apply_segment(ks_ctx* o, const uint64_t* d_gkey, const uint32_t
   return KS_OK;
 }
 
+// The text goes to both contexts: the caller may ask either for it.
+static int round_fail(ks_ctx* m, ks_ctx* o, int rc, const std::string& why) {
+  m->err = why;
+  o->err = why;
+  return rc;
+}
+
 int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, int world, uint64_t first_frame, const float T[7],
                              const float* xyz, const uint8_t* rgba, const uint8_t* labels, size_t n, int freespace, ks_round_stats* stats) {
   if (!m || !o || m == o || !T || world < 1 || world > 64 || rank < 0 || rank >= world || (world > 1 && !rccl_comm) || (n && !xyz))
     return KS_ERR_INVALID_ARG;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (m->fatal || o->fatal) return KS_ERR_INVALID_ARG;
+  // ---- what is the same on every rank (the configuration, by contract): refused before anything is exchanged ----
+  if (m->cfg.method != o->cfg.method)
+    return round_fail(m, o, KS_ERR_UNSUPPORTED, "ks_integrate_round_exact: marcher and owner must be created with the same method");
+  const bool merged = m->cfg.method == KS_METHOD_MERGED;
   for (ks_ctx* c : {m, o}) {
     const ks_config& k = c->cfg;
+    if (merged) {
+      if (k.color_mode == KS_COLOR_MODE_COLOR)
+        return round_fail(m, o, KS_ERR_UNSUPPORTED,
+                          "ks_integrate_round_exact: color_mode = KS_COLOR_MODE_COLOR blends the voxel's colour with the bundle's by the voxel's "
+                          "weight at that update, which an update record does not carry: colours from the labels only (anything else: integrate "
+                          "per rank and ks_reduce)");
+      if (k.pipeline_frames != 0)
+        return round_fail(m, o, KS_ERR_UNSUPPORTED, "ks_integrate_round_exact: one frame at a time (pipeline_frames = 0)");
+      continue;
+    }
     const bool frames_independent = !c->uses_early_out || k.clear_checks_every_n_frames <= 1;
     if (k.method != KS_METHOD_FAST || k.color_mode == KS_COLOR_MODE_COLOR || k.pipeline_frames != 0 || !frames_independent ||
-        k.integration_order_mode == KS_ORDER_SORTED) {
-      c->err = "ks_integrate_round_exact: `fast`, colours from the labels, one frame at a time, mixed order, clear_checks_every_n_frames = 1 "
-               "(anything else: integrate per rank and ks_reduce)";
-      return KS_ERR_UNSUPPORTED;
-    }
+        k.integration_order_mode == KS_ORDER_SORTED)
+      return round_fail(m, o, KS_ERR_UNSUPPORTED,
+                        "ks_integrate_round_exact: `fast`, colours from the labels, one frame at a time, mixed order, clear_checks_every_n_frames = 1 "
+                        "(anything else: integrate per rank and ks_reduce)");
   }
-  int rc;
-  const uint64_t my_frame = first_frame + (uint64_t)rank;
-  if (m->shard_frames_seen > my_frame) {
-    m->err = "ks_integrate_round_exact: rounds must come in frame order";
-    return KS_ERR_INVALID_ARG;
+  if (world > 1) {
+    std::string why;
+    if (!g_rccl.load(&why)) return round_fail(m, o, KS_ERR_UNSUPPORTED, why);   // (no library, no exchange: nothing a peer could be told through)
   }
-  m->shard_export = true;
-  m->shard_world = world;
-  // the frames other ranks march in between advance this marcher's set offsets and frame counters like empty clouds
-  // ([K:src/semantic_tsdf_integrator_fast.cpp:165-170]: the bookkeeping is per call)
-  static const uint8_t no_label = 0;
-  const float T0[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (; m->shard_frames_seen < my_frame; ++m->shard_frames_seen)
-    if ((rc = ks_integrate_points(m, T0, nullptr, nullptr, &no_label, 0, 0, nullptr))) return rc;
-  std::memset(m->sh_counts, 0, sizeof(m->sh_counts));
-  m->sh_exported = 0;
+  // ---- what can differ from rank to rank: a failure here is CARRIED to the peers in the count exchange below, no rank is left
+  //      waiting, every rank returns an error and nothing of the round is applied anywhere ----
+  const uint64_t seen_before = m->shard_frames_seen;
+  bool marcher_moved = false;   // the marcher's per-call state (the approximate sets' offsets of `fast`) has advanced
   ks_frame_stats fst{};
-  if ((rc = ks_integrate_points(m, T, xyz, rgba, labels ? labels : (rgba ? nullptr : &no_label), n, freespace, &fst))) return rc;
-  ++m->shard_frames_seen;
+  auto march = [&]() -> int {
+    int rc;
+    if (m->fatal || o->fatal)
+      return round_fail(m, o, KS_ERR_INVALID_ARG, "ks_integrate_round_exact: a context is unusable after an earlier failure (destroy it)");
+    if (n >= ((size_t)1 << kShardSeqBits))
+      return round_fail(m, o, KS_ERR_INVALID_ARG, "ks_integrate_round_exact: a cloud of 2^24 points or more does not fit the update record's position field");
+    const uint64_t my_frame = first_frame + (uint64_t)rank;
+    if (m->shard_frames_seen > my_frame) return round_fail(m, o, KS_ERR_INVALID_ARG, "ks_integrate_round_exact: rounds must come in frame order");
+    m->shard_export = true;
+    m->shard_world = world;
+    static const uint8_t no_label = 0;
+    if (merged) {
+      // nothing of `merged` outlives a frame (ks_k_shard_merged.h): the frames of the other ranks are only counted
+      m->shard_frames_seen = my_frame;
+    } else {
+      // the frames other ranks march in between advance this marcher's set offsets and frame counters like empty clouds
+      // ([K:src/semantic_tsdf_integrator_fast.cpp:165-170]: the bookkeeping is per call)
+      const float T0[7] = {1.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (; m->shard_frames_seen < my_frame; ++m->shard_frames_seen) {
+        marcher_moved = true;
+        if ((rc = ks_integrate_points(m, T0, nullptr, nullptr, &no_label, 0, 0, nullptr))) return rc;
+      }
+    }
+    std::memset(m->sh_counts, 0, sizeof(m->sh_counts));
+    m->sh_exported = 0;
+    m->shm_counts[0] = m->shm_counts[1] = 0;
+    marcher_moved = marcher_moved || !merged;
+    if ((rc = ks_integrate_points(m, T, xyz, rgba, labels ? labels : (rgba ? nullptr : &no_label), n, freespace, &fst))) return rc;
+    ++m->shard_frames_seen;
+    uint64_t sum = 0;
+    for (int p = 0; p < world; ++p) sum += m->sh_counts[p];
+    if (sum != m->sh_exported) return round_fail(m, o, KS_ERR_HIP, "ks_integrate_round_exact: the per-owner counts do not add up to the frame's updates");
+    return KS_OK;
+  };
+  // a round that failed has to be repeated by every rank: the marcher is put back where it was, or, where its state cannot be
+  // (`fast`: the sets' offsets have moved), retired
+  auto undo = [&]() {
+    if (marcher_moved) {
+      m->fatal = true;
+    } else {
+      m->shard_frames_seen = seen_before;
+    }
+  };
+  int rc = march();
+  if (rc) {  // nothing leaves this rank but its error code
+    std::memset(m->sh_counts, 0, sizeof(m->sh_counts));
+    m->sh_exported = 0;
+    m->shm_counts[0] = m->shm_counts[1] = 0;
+    o->err = m->err;
+  }
   // where this frame's records sit, by owner
   std::vector<size_t> send_counts(world), send_off(world + 1, 0);
   for (int p = 0; p < world; ++p) {
     send_counts[p] = m->sh_counts[p];
     send_off[p + 1] = send_off[p] + send_counts[p];
   }
-  if (send_off[world] != m->sh_exported) {
-    m->err = "ks_integrate_round_exact: the per-owner counts do not add up to the frame's updates";
-    return KS_ERR_HIP;
-  }
-  uint64_t applied = 0, origin = m->sh_counts[world];
+  const ShardTables own_tables{m->d_shm_btab, m->shm_counts[0], m->d_shm_mixed, m->shm_counts[1]};
+  uint64_t applied = 0, origin = merged ? 0 : m->sh_counts[world];
   if (world == 1) {
-    if ((rc = shard_apply_segment(o, m->d_sh_gkey[1], m->d_sh_seq[1], m->d_sh_sdf[1], m->d_sh_uw[1], send_counts[0], m->tiles_initialised))) return rc;
+    if (rc) {
+      undo();
+      return rc;
+    }
+    if ((rc = shard_apply_segment(o, m->d_sh_gkey[1], m->d_sh_seq[1], m->d_sh_sdf[1], m->d_sh_uw[1], send_counts[0], m->tiles_initialised,
+                                  merged ? &own_tables : nullptr)))
+      return rc;
     applied = send_counts[0];
   } else {
-    std::string why;
-    if (!g_rccl.load(&why)) {
-      o->err = why;
-      return KS_ERR_UNSUPPORTED;
-    }
     ncclComm_t comm = (ncclComm_t)rccl_comm;
     hipStream_t st = o->stream;
-    // 1) everybody's counts, origin-voxel flags and marchers' tile counts: (world + 2) x world
-    const int W2 = world + 2;
-    if ((rc = ensure_reduce_scratch(o, 0, 0, W2))) return rc;
+    // 1) everybody's row: [world] counts | origin-voxel flag | marcher's tile count | bundles | mixed-label bundles | error code
+    const int W2 = world + 5;
+    int arc;
+    if ((arc = ensure_reduce_scratch(o, 0, 0, W2))) return arc;
     int32_t* d_own = o->d_rx_counts;
     int32_t* d_all = d_own + W2;
     std::vector<int32_t> own(W2);
     for (int p = 0; p < world; ++p) own[p] = (int32_t)send_counts[p];
-    own[world] = (int32_t)m->sh_counts[world];
+    own[world] = (int32_t)origin;
     own[world + 1] = (int32_t)m->tiles_initialised;
+    own[world + 2] = (int32_t)m->shm_counts[0];
+    own[world + 3] = (int32_t)m->shm_counts[1];
+    own[world + 4] = (int32_t)rc;
     HIPCHK(o, hipMemcpyAsync(d_own, own.data(), own.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
     NCCLCHK(o, g_rccl.all_gather(d_own, d_all, (size_t)W2, ncclInt32, comm, st));
     std::vector<int32_t> all((size_t)W2 * world);
     HIPCHK(o, hipMemcpyAsync(all.data(), d_all, all.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
     HIPCHK(o, hipStreamSynchronize(st));
-    std::vector<size_t> recv_counts(world), recv_off(world + 1, 0);
     for (int p = 0; p < world; ++p) {
-      recv_counts[p] = p == rank ? 0 : (size_t)all[(size_t)p * W2 + rank];
+      const int prc = all[(size_t)p * W2 + world + 4];
+      if (!prc) continue;
+      // every rank sees the same rows: all of them leave here, before the exchange
+      undo();
+      if (rc) return rc;   // (this rank's own failure: its code, its text)
+      return round_fail(m, o, KS_ERR_PEER_FAILED,
+                        "ks_integrate_round_exact: rank " + std::to_string(p) + " failed with code " + std::to_string(prc) +
+                            " (its ks_last_error says why); nothing of this round was applied on any rank");
+    }
+    std::vector<size_t> recv_counts(world), recv_off(world + 1, 0), rb_off(world + 1, 0), rm_off(world + 1, 0);
+    for (int p = 0; p < world; ++p) {
+      const int32_t* row = &all[(size_t)p * W2];
+      recv_counts[p] = p == rank ? 0 : (size_t)row[rank];
       recv_off[p + 1] = recv_off[p] + recv_counts[p];
-      origin |= (uint64_t)all[(size_t)p * W2 + world];
+      // (a peer's tables travel only with records)
+      rb_off[p + 1] = rb_off[p] + (merged && recv_counts[p] ? (size_t)row[world + 2] : 0);
+      rm_off[p + 1] = rm_off[p] + (merged && recv_counts[p] ? (size_t)row[world + 3] : 0);
+      origin |= (uint64_t)row[world];
     }
     const size_t n_recv = recv_off[world];
     // 2) receive buffers on the owner context (its own d_sh_*[0]: an owner context never exports)
@@ -3181,7 +3340,18 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
       if ((rc = dev_alloc(o, &o->d_sh_uw[0], cap))) return rc;
       o->cap_sh = cap;
     }
+    if (rb_off[world] > o->cap_shm_rx_btab) {
+      const size_t cap = std::max<size_t>(rb_off[world] + rb_off[world] / 4, 1 << 14);
+      if ((rc = dev_alloc(o, &o->d_shm_rx_btab, cap))) return rc;
+      o->cap_shm_rx_btab = cap;
+    }
+    if (rm_off[world] > o->cap_shm_rx_mixed) {
+      const size_t cap = std::max<size_t>(rm_off[world] + rm_off[world] / 4, 1 << 10);
+      if ((rc = dev_alloc(o, &o->d_shm_rx_mixed, cap * kNumLabels))) return rc;
+      o->cap_shm_rx_mixed = cap;
+    }
     // 3) one grouped exchange: every rank talks to all its peers at once (xGMI is point to point)
+    uint64_t bytes = 0;
     NCCLCHK(o, g_rccl.group_start());
     for (int peer = 0; peer < world; ++peer) {
       if (peer == rank) continue;
@@ -3190,12 +3360,26 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
         NCCLCHK(o, g_rccl.send(m->d_sh_seq[1] + send_off[peer], send_counts[peer], ncclUint32, peer, comm, st));
         NCCLCHK(o, g_rccl.send(m->d_sh_sdf[1] + send_off[peer], send_counts[peer], ncclFloat32, peer, comm, st));
         NCCLCHK(o, g_rccl.send(m->d_sh_uw[1] + send_off[peer], send_counts[peer], ncclFloat32, peer, comm, st));
+        bytes += send_counts[peer] * 20ull;
+        if (merged && own_tables.n_bundles) {
+          NCCLCHK(o, g_rccl.send(own_tables.btab, (size_t)own_tables.n_bundles * 2, ncclFloat32, peer, comm, st));
+          bytes += own_tables.n_bundles * 8ull;
+        }
+        if (merged && own_tables.n_mixed) {
+          NCCLCHK(o, g_rccl.send(own_tables.mixed, (size_t)own_tables.n_mixed * kNumLabels, ncclFloat32, peer, comm, st));
+          bytes += own_tables.n_mixed * (uint64_t)(kNumLabels * sizeof(float));
+        }
       }
       if (recv_counts[peer]) {
         NCCLCHK(o, g_rccl.recv(o->d_sh_gkey[0] + recv_off[peer], recv_counts[peer], ncclUint64, peer, comm, st));
         NCCLCHK(o, g_rccl.recv(o->d_sh_seq[0] + recv_off[peer], recv_counts[peer], ncclUint32, peer, comm, st));
         NCCLCHK(o, g_rccl.recv(o->d_sh_sdf[0] + recv_off[peer], recv_counts[peer], ncclFloat32, peer, comm, st));
         NCCLCHK(o, g_rccl.recv(o->d_sh_uw[0] + recv_off[peer], recv_counts[peer], ncclFloat32, peer, comm, st));
+        if (rb_off[peer + 1] > rb_off[peer])
+          NCCLCHK(o, g_rccl.recv(o->d_shm_rx_btab + rb_off[peer], (rb_off[peer + 1] - rb_off[peer]) * 2, ncclFloat32, peer, comm, st));
+        if (rm_off[peer + 1] > rm_off[peer])
+          NCCLCHK(o, g_rccl.recv(o->d_shm_rx_mixed + rm_off[peer] * kNumLabels, (rm_off[peer + 1] - rm_off[peer]) * kNumLabels, ncclFloat32, peer,
+                                 comm, st));
       }
     }
     NCCLCHK(o, g_rccl.group_end());
@@ -3204,17 +3388,20 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
     for (int src = 0; src < world; ++src) {
       if (src == rank) {
         if ((rc = shard_apply_segment(o, m->d_sh_gkey[1] + send_off[rank], m->d_sh_seq[1] + send_off[rank], m->d_sh_sdf[1] + send_off[rank],
-                                      m->d_sh_uw[1] + send_off[rank], send_counts[rank], m->tiles_initialised)))
+                                      m->d_sh_uw[1] + send_off[rank], send_counts[rank], m->tiles_initialised, merged ? &own_tables : nullptr)))
           return rc;
         applied += send_counts[rank];
       } else {
+        const int32_t* row = &all[(size_t)src * W2];
+        const ShardTables rx{o->d_shm_rx_btab + rb_off[src], (uint32_t)(rb_off[src + 1] - rb_off[src]),
+                             o->d_shm_rx_mixed + rm_off[src] * kNumLabels, (uint32_t)(rm_off[src + 1] - rm_off[src])};
         if ((rc = shard_apply_segment(o, o->d_sh_gkey[0] + recv_off[src], o->d_sh_seq[0] + recv_off[src], o->d_sh_sdf[0] + recv_off[src],
-                                      o->d_sh_uw[0] + recv_off[src], recv_counts[src], (size_t)all[(size_t)src * W2 + world + 1])))
+                                      o->d_sh_uw[0] + recv_off[src], recv_counts[src], (size_t)row[world + 1], merged ? &rx : nullptr)))
           return rc;
         applied += recv_counts[src];
       }
     }
-    if (stats) stats->bytes_sent = (m->sh_exported - send_counts[rank]) * 20ull;
+    if (stats) stats->bytes_sent = bytes;
   }
   if (stats) {
     stats->updates_marched = m->sh_exported;
@@ -3224,6 +3411,7 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
   }
   return KS_OK;
 }
+
 
 // keep_integrator_state: only the MAP goes (tile table, pool flags); the two approximate sets, their offsets, the
 // frame counters and the early-out table stay as the frames so far left them — what vxb::TsdfServer::clear() does to the
