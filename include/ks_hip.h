@@ -256,6 +256,44 @@ int ks_download_updated_voxels(ks_ctx* ctx, void* out, size_t cap_records, size_
 void* ks_host_alloc(size_t bytes);
 void ks_host_free(void* p);
 
+/* ---- semantic mesh on the device (new: the reference meshes the host layers with Voxblox's MeshIntegrator after a layer
+ * sync, kimera_semantics_rosbag.cpp:147-167; here the mesh is made where the voxels are and only triangles travel) ----
+ * Marching cubes over the resident tiles; the contract is DESIGN.md, section "Semantic mesh" (no parity with Voxblox's
+ * mesher is claimed: it is not part of the reference tree).  In short: a cube belongs to the voxel at its lowest corner
+ * and to that voxel's host-layout block (border cubes read the +x / +y / +z neighbours); it is meshed iff all eight
+ * corners have weight >= min_weight; a corner is inside iff distance < 0; vertices lie on the edges between voxel CENTRES,
+ * t = da / (da - db) from the lower-numbered corner; three vertices per triangle, no sharing; the normal (repeated for
+ * the three vertices) points towards positive distance; a triangle of zero area is dropped and counted.  Every vertex
+ * carries the colour (TsdfVoxel colour, as the context's color_mode wrote it) and the arg-max LABEL of the voxel whose
+ * cell contains it.  ORDER (part of the ABI): blocks ascending by (x, y, z) like ks_get_block_indices; inside a block
+ * cubes by x + vps * (y + vps * z); inside a cube triangles in table order.  Two calls on the same map give the same bytes.
+ * ks_mesh_update   extracts (only_stale = 0) or refreshes (only_stale = 1) the mesh the context keeps on the device.  A
+ *                  refresh re-meshes the blocks with a tile written since the last update (integrate, upload, merge, reduce,
+ *                  round, reset — a per-tile flag of its own, independent of both host syncs) and the up to seven blocks at
+ *                  -x / -y / -z offsets whose border cubes read them; after any sequence of calls the stored mesh is bit
+ *                  for bit what a from-scratch extraction gives.  The first call, and a call with another min_weight than
+ *                  the stored mesh was made with, mesh everything.  Completes the frames in flight first.
+ *                  stats: blocks_meshed of blocks_total, triangles_total in the mesh, triangles_changed = triangles in the
+ *                  re-meshed blocks' new segments, degenerate_dropped by this call.
+ * ks_mesh_size / ks_mesh_download   the stored mesh: blocks with n_vertices > 0 in order, their segments back to back
+ *                  (first_vertex / n_vertices index the four vertex arrays; xyz and normals 3 floats, rgba 4 bytes, labels
+ *                  1 byte per vertex; any of the four may be NULL).  Page-locked buffers (ks_host_alloc) copy at link rate.
+ * ks_mesh_changed_blocks   the blocks whose segment the LAST ks_mesh_update replaced (including ones that are empty now).
+ * ks_clear / ks_clear_voxels empty the mesh too.  Errors: KS_ERR_INVALID_ARG (capacity too small; min_weight not a finite
+ * positive number), KS_ERR_HIP, KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact holds no voxel data).
+ * Multi-GPU: each context meshes the tiles it holds; seams between the tiles of different owners are not handled. */
+typedef struct ks_mesh_config { float min_weight; int32_t only_stale; } ks_mesh_config;
+typedef struct ks_mesh_stats {
+  uint64_t blocks_meshed, blocks_total, triangles_total, triangles_changed, degenerate_dropped;
+} ks_mesh_stats;
+typedef struct ks_mesh_block { int32_t block[3]; uint32_t first_vertex, n_vertices; } ks_mesh_block;
+int ks_mesh_default_config(ks_mesh_config* cfg); /* min_weight 1e-4, only_stale 0 */
+int ks_mesh_update(ks_ctx* ctx, const ks_mesh_config* cfg, ks_mesh_stats* stats /* may be NULL */);
+int ks_mesh_size(ks_ctx* ctx, size_t* n_blocks, size_t* n_vertices);
+int ks_mesh_download(ks_ctx* ctx, ks_mesh_block* blocks, size_t cap_blocks, float* xyz, float* normals, uint8_t* rgba,
+                     uint8_t* labels, size_t cap_vertices);
+int ks_mesh_changed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "ks_get_updated_block_indices", "ks_count_updated_voxels", "ks_download_updated_voxels", "ks_download_blocks", "ks_upload_blocks", "ks_host_alloc", "ks_host_free", "ks_get_tile_keys", "ks_export_tiles_device", "ks_merge_tiles_device", "ks_clear", "ks_clear_voxels", "ks_reset_tiles", "ks_tile_owner", "ks_reduce",
     "ks_debug_radix_sort", "ks_synchronize", "ks_flush", "ks_stream",
     "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_update_stats", "ks_integrate_round_exact",
+    "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
 ]
 
 
@@ -75,6 +76,18 @@ class KsReduceStats(C.Structure):
                 ("bytes_sent", C.c_uint64)]
 
 
+class KsMeshConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("only_stale", C.c_int32)]
+
+
+class KsMeshStats(C.Structure):
+    _fields_ = [("blocks_meshed", C.c_uint64), ("blocks_total", C.c_uint64), ("triangles_total", C.c_uint64),
+                ("triangles_changed", C.c_uint64), ("degenerate_dropped", C.c_uint64)]
+
+
+MESH_BLOCK_DTYPE = np.dtype([("block", "<i4", (3,)), ("first_vertex", "<u4"), ("n_vertices", "<u4")])
+
+
 class KsProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("frames", C.c_uint64),
                 ("updates", C.c_uint64), ("points", C.c_uint64), ("apply_kernel_ms", C.c_double),
@@ -86,7 +99,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_device_math.h", "ks_radix_sort.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -149,6 +162,11 @@ def lib():
         L.ks_pipeline_shape.argtypes = [vp, C.POINTER(C.c_int32)]
         L.ks_update_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ks_integrate_round_exact.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(KsRoundStats)]
+        L.ks_mesh_default_config.argtypes = [C.POINTER(KsMeshConfig)]
+        L.ks_mesh_update.argtypes = [vp, C.POINTER(KsMeshConfig), C.POINTER(KsMeshStats)]
+        L.ks_mesh_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.ks_mesh_download.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
+        L.ks_mesh_changed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -297,6 +315,30 @@ class HipIntegrator:
             sem = np.ascontiguousarray(sem, dtype=SEM_DTYPE).reshape(len(indices), nv)
             sp = _ptr(sem)
         self._chk(lib().ks_upload_blocks(self._h, _ptr(indices), len(indices), tp, sp))
+
+    def mesh(self, only_stale=False, min_weight=1e-4):
+        """Extracts (or, only_stale, refreshes) the semantic mesh on the device and fetches it: kimera_semantics_amd.mesh.Mesh
+        with blocks (MESH_BLOCK_DTYPE, ascending), xyz / normals (N, 3) f32, rgba (N, 4) u8, labels (N,) u8, stats (dict).
+        Three vertices per triangle; the order is part of the ABI (ks_mesh_update in include/ks_hip.h)."""
+        from .mesh import Mesh
+        mc, st = KsMeshConfig(float(min_weight), int(bool(only_stale))), KsMeshStats()
+        self._chk(lib().ks_mesh_update(self._h, C.byref(mc), C.byref(st)))
+        nb, nv = C.c_size_t(), C.c_size_t()
+        self._chk(lib().ks_mesh_size(self._h, C.byref(nb), C.byref(nv)))
+        blocks = np.zeros(nb.value, dtype=MESH_BLOCK_DTYPE)
+        xyz, normals = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32)
+        rgba, labels = np.zeros((nv.value, 4), np.uint8), np.zeros(nv.value, np.uint8)
+        self._chk(lib().ks_mesh_download(self._h, _ptr(blocks), nb.value, _ptr(xyz), _ptr(normals), _ptr(rgba), _ptr(labels), nv.value))
+        return Mesh(blocks, xyz, normals, rgba, labels, {k: int(getattr(st, k)) for k, _ in KsMeshStats._fields_})
+
+    def mesh_changed_blocks(self) -> np.ndarray:
+        """Blocks whose segment the last mesh() replaced (including ones that are empty now), ascending."""
+        n = C.c_size_t()
+        self._chk(lib().ks_mesh_changed_blocks(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            self._chk(lib().ks_mesh_changed_blocks(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----
     TILE_BYTES = 65536

@@ -41,6 +41,7 @@
 #include <rccl/rccl.h>
 
 #include <algorithm>
+#include <iterator>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -66,6 +67,7 @@ using namespace ksd;
 #include "ks_k_shard.h"
 #include "ks_k_shard_merged.h"
 #include "ks_k_io.h"
+#include "ks_k_mesh.h"
 
 using namespace ksk;
 
@@ -381,6 +383,20 @@ struct ks_ctx {
   LongHdr* d_long_hdr_[2] = {nullptr, nullptr};
   unsigned long long* d_xl_fb = nullptr;
   uint32_t cap_xl_chunks = 1u << 17;   // 8 M updates in such runs per frame (more: the serial kernel takes the rest)
+  // ks_mesh_update (ks_k_mesh.h).  The mesh lives in one of two arenas as per-block segments back to back; a call writes the
+  // other arena (re-meshed blocks from the kernels, kept ones copied) and swaps.  The host keeps the directory and the
+  // sorted block list (tiles only ever join a map, so the list is extended by the tiles that are new since the last call).
+  MeshArena mesh_arena[2] = {};
+  size_t mesh_cap[2] = {0, 0};
+  int mesh_cur = 0;
+  bool mesh_valid = false;                 // false: the next call meshes everything, whatever only_stale says
+  float mesh_min_weight = 0.f;             // ... as does a call with another min_weight than the stored mesh was made with
+  std::vector<uint64_t> mesh_blocks;       // packed (x, y, z) of every block of the map, ascending
+  uint32_t mesh_tiles_seen = 0;            // tiles [0, seen) have entered mesh_blocks
+  std::vector<ks_mesh_block> mesh_dir;     // one entry per element of mesh_blocks as of the last update (n_vertices may be 0)
+  std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
+  uint8_t* d_mesh_buf[10] = {};            // grow-only scratch of the passes (mesh_scratch)
+  size_t cap_mesh_buf[10] = {};
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -1860,17 +1876,19 @@ int grow_pool(ks_ctx* c) {
   // (a failure part-way leaves the old pool in place and frees what was allocated for the new one)
   auto fill = [&]() -> hipError_t {
     hipError_t e;
-    if ((e = hipMalloc((void**)&upd, new_max)) != hipSuccess) return e;
+    if ((e = hipMalloc((void**)&upd, kFlagPlane + new_max)) != hipSuccess) return e;   // two planes: updated | mesh_stale
     if ((e = hipMalloc((void**)&dirty, new_max)) != hipSuccess) return e;
     if ((e = hipMalloc((void**)&skeys, new_max * sizeof(uint64_t))) != hipSuccess) return e;
     if ((e = hipMalloc((void**)&ent, (size_t)cap * sizeof(TileEntry))) != hipSuccess) return e;
     if ((e = hipMemset(upd, 0, new_max)) != hipSuccess) return e;
     if ((e = hipMemset(dirty, 0, new_max)) != hipSuccess) return e;
+    if ((e = hipMemset(upd + kFlagPlane, 0, new_max)) != hipSuccess) return e;
     if ((e = hipMemset(ent, 0xff, (size_t)cap * sizeof(TileEntry))) != hipSuccess) return e;
     if (nt) {
       if ((e = hipMemcpy(vox, c->pool.vox, (size_t)nt * kTileVoxels * 8 * sizeof(uint4), hipMemcpyDeviceToDevice)) != hipSuccess) return e;
       if ((e = hipMemcpy(upd, c->pool.updated, nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
       if ((e = hipMemcpy(dirty, c->pool.dirty, nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
+      if ((e = hipMemcpy(upd + kFlagPlane, c->pool.mesh_stale(), nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
       if ((e = hipMemcpy(skeys, c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToDevice)) != hipSuccess) return e;
     }
     return hipSuccess;
@@ -2320,10 +2338,11 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   CRCHK(hipMalloc((void**)&c->table.slot_keys, mt * sizeof(uint64_t)));
   CRCHK(hipMemset(c->table.ent, 0xff, cap * sizeof(TileEntry)));  // key = empty, val = kSlotPending
   CRCHK(hipMalloc((void**)&c->pool.vox, mt * kTileVoxels * 8 * sizeof(uint4)));
-  CRCHK(hipMalloc((void**)&c->pool.updated, mt));
+  CRCHK(hipMalloc((void**)&c->pool.updated, kFlagPlane + mt));   // two planes: updated | mesh_stale (ks_types.h: Pool)
   CRCHK(hipMemset(c->pool.updated, 0, mt));
   CRCHK(hipMalloc((void**)&c->pool.dirty, mt));
   CRCHK(hipMemset(c->pool.dirty, 0, mt));
+  CRCHK(hipMemset(c->pool.mesh_stale(), 0, mt));
   CRCHK(hipMalloc((void**)&c->d_start_set, sizeof(uint64_t) << kSetBits));
   c->n_obs = (uses_early_out && frames_independent) ? std::min(kObsTables, std::max(c->n_march, c->batch * c->n_march)) : 1;
   for (int t = 0; t < c->n_obs; ++t) {
@@ -2418,6 +2437,11 @@ void ks_destroy(ks_ctx* c) {
                   c->d_eo_state, c->d_xl_runs, c->d_xl_hdr, c->d_xl_chunks, c->d_xl_idx, c->d_xl_fb, c->d_long_sorted_[0], c->d_long_sorted_[1], c->d_long_hdr_[0], c->d_long_hdr_[1], c->d_sh_okey[0], c->d_sh_okey[1], c->d_sh_gkey[0], c->d_sh_gkey[1], c->d_sh_seq[0], c->d_sh_seq[1], c->d_sh_sdf[0], c->d_sh_sdf[1], c->d_sh_uw[0], c->d_sh_uw[1], c->d_sh_counts, c->d_sh_tk, c->d_sh_pairs[0], c->d_sh_pairs[1], c->d_sh_vals[0], c->d_sh_vals[1], c->d_shm_bno, c->d_shm_btab, c->d_shm_mpos, c->d_shm_cnt, c->d_shm_mixed, c->d_shm_rx_btab, c->d_shm_rx_mixed, c->d_shm_ops, c->d_shm_long, c->d_rx_counts, c->d_tx_keys, c->d_rx_keys, c->d_tx_slots, c->d_tx_payload, c->d_rx_payload};
   for (void* p : ptrs)
     if (p) (void)hipFree(p);
+  for (void* p : c->d_mesh_buf)
+    if (p) (void)hipFree(p);
+  for (auto& A : c->mesh_arena)
+    for (void* p : {(void*)A.xyz, (void*)A.nrm, (void*)A.rgba, (void*)A.label})
+      if (p) (void)hipFree(p);
   for (auto& S : c->slot) {
     for (void* p : {(void*)S.d_rays, (void*)S.d_deltas, (void*)S.d_ray_list, (void*)S.d_pairs, (void*)S.d_cnt, (void*)S.d_lp,
                     (void*)S.d_bt, (void*)S.d_live, (void*)S.d_F, (void*)S.d_gkeys, (void*)S.d_rkeys,
@@ -2713,6 +2737,263 @@ int ks_upload_blocks(ks_ctx* c, const int32_t* idx, size_t n, const void* tsdf_i
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+// ---- semantic mesh (ks_k_mesh.h) -------------------------------------------------------------------------
+static int mesh_scratch(ks_ctx* c, int i, size_t bytes) {
+  if (bytes <= c->cap_mesh_buf[i]) return KS_OK;
+  const size_t cap = std::max<size_t>(bytes + bytes / 2, 256);
+  if (int rc = dev_alloc(c, &c->d_mesh_buf[i], cap)) return rc;
+  c->cap_mesh_buf[i] = cap;
+  return KS_OK;
+}
+static int mesh_arena_reserve(ks_ctx* c, int a, size_t n_vertices) {
+  if (n_vertices <= c->mesh_cap[a]) return KS_OK;
+  const size_t cap = std::max<size_t>(n_vertices + n_vertices / 2, 4096);
+  MeshArena& A = c->mesh_arena[a];
+  int rc;
+  if ((rc = dev_alloc(c, &A.xyz, 3 * cap))) return rc;
+  if ((rc = dev_alloc(c, &A.nrm, 3 * cap))) return rc;
+  if ((rc = dev_alloc(c, &A.rgba, cap))) return rc;
+  if ((rc = dev_alloc(c, &A.label, cap))) return rc;
+  c->mesh_cap[a] = cap;
+  return KS_OK;
+}
+// block index <-> one sortable word (ascending word = ascending (x, y, z))
+static inline uint64_t mesh_block_key(int x, int y, int z) {
+  return ((uint64_t)(uint32_t)(x + kCoordBias) << 42) | ((uint64_t)(uint32_t)(y + kCoordBias) << 21) | (uint64_t)(uint32_t)(z + kCoordBias);
+}
+static inline void mesh_block_of(uint64_t k, int32_t out[3]) {
+  out[0] = (int32_t)((k >> 42) & 0x1fffffu) - kCoordBias;
+  out[1] = (int32_t)((k >> 21) & 0x1fffffu) - kCoordBias;
+  out[2] = (int32_t)(k & 0x1fffffu) - kCoordBias;
+}
+
+int ks_mesh_default_config(ks_mesh_config* m) {
+  if (!m) return KS_ERR_INVALID_ARG;
+  m->min_weight = 1e-4f;
+  m->only_stale = 0;
+  return KS_OK;
+}
+
+int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
+  if (!c || !m) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!(m->min_weight > 0.0f) || !std::isfinite(m->min_weight)) {
+    c->err = "ks_mesh_update: min_weight must be a finite positive number";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (c->shard_export) {
+    c->err = "ks_mesh_update: a marcher context of ks_integrate_round_exact holds no voxel data";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->tiles_initialised;
+  const int sh = c->vps_shift;
+  // 1) the block list grows by the tiles that joined the map since the last call
+  std::vector<uint64_t> keys(nt > c->mesh_tiles_seen ? nt : 0);   // (slot -> tile key; only read when something is new or stale)
+  std::vector<uint8_t> stale(nt);
+  if (nt) {
+    HIPCHK(c, hipMemcpy(stale.data(), c->pool.mesh_stale(), nt, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemsetAsync(c->pool.mesh_stale(), 0, nt, st));
+  }
+  auto tile_block = [&](uint64_t k) {
+    const int tx = (int)((k >> 36) & 0x3ffffu) - kTileBias, ty = (int)((k >> 18) & 0x3ffffu) - kTileBias, tz = (int)(k & 0x3ffffu) - kTileBias;
+    return mesh_block_key(tx >> sh, ty >> sh, tz >> sh);
+  };
+  if (nt > c->mesh_tiles_seen) {
+    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    std::vector<uint64_t> fresh;
+    for (uint32_t s = c->mesh_tiles_seen; s < nt; ++s) fresh.push_back(tile_block(keys[s]));
+    std::sort(fresh.begin(), fresh.end());
+    fresh.erase(std::unique(fresh.begin(), fresh.end()), fresh.end());
+    std::vector<uint64_t> all;
+    std::set_union(c->mesh_blocks.begin(), c->mesh_blocks.end(), fresh.begin(), fresh.end(), std::back_inserter(all));
+    c->mesh_blocks.swap(all);
+    c->mesh_tiles_seen = nt;
+  }
+  const std::vector<uint64_t>& B = c->mesh_blocks;
+  const size_t nb = B.size();
+  // 2) what to mesh: everything, or the blocks with a stale tile plus the up to seven blocks at -x / -y / -z offsets whose
+  //    border cubes read it
+  const bool full = !m->only_stale || !c->mesh_valid || m->min_weight != c->mesh_min_weight;
+  c->mesh_valid = false;   // (a failure below leaves flags cleared that nothing has meshed: the next call starts over)
+  std::vector<uint64_t> R;
+  if (full) {
+    R = B;
+  } else {
+    bool any = false;
+    for (uint32_t s = 0; s < nt && !any; ++s) any = stale[s] != 0;
+    if (any && keys.empty()) {
+      keys.resize(nt);
+      HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    }
+    std::vector<uint64_t> cand;
+    for (uint32_t s = 0; s < nt; ++s) {
+      if (!stale[s]) continue;
+      int32_t b[3];
+      mesh_block_of(tile_block(keys[s]), b);
+      for (int o = 0; o < 8; ++o) cand.push_back(mesh_block_key(b[0] - (o & 1), b[1] - ((o >> 1) & 1), b[2] - (o >> 2)));
+    }
+    std::sort(cand.begin(), cand.end());
+    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
+    std::set_intersection(cand.begin(), cand.end(), B.begin(), B.end(), std::back_inserter(R));
+  }
+  const size_t nr = R.size();
+  // 3) the new directory: re-meshed blocks by their number in R, kept ones with the segment they have
+  std::vector<ks_mesh_block> dir(nb);
+  std::vector<uint32_t> dir_in(2 * nb);
+  std::vector<uint32_t> old_first(nb, 0u);
+  {
+    size_t ir = 0, io = 0;
+    for (size_t i = 0; i < nb; ++i) {
+      mesh_block_of(B[i], dir[i].block);
+      dir[i].first_vertex = dir[i].n_vertices = 0;
+      while (ir < nr && R[ir] < B[i]) ++ir;
+      if (ir < nr && R[ir] == B[i]) {
+        dir_in[2 * i] = (uint32_t)ir;
+        dir_in[2 * i + 1] = 0;
+        continue;
+      }
+      dir_in[2 * i] = 0xffffffffu;
+      dir_in[2 * i + 1] = 0;
+      while (io < c->mesh_dir.size() && mesh_block_key(c->mesh_dir[io].block[0], c->mesh_dir[io].block[1], c->mesh_dir[io].block[2]) < B[i]) ++io;
+      if (!full && io < c->mesh_dir.size() && mesh_block_key(c->mesh_dir[io].block[0], c->mesh_dir[io].block[1], c->mesh_dir[io].block[2]) == B[i]) {
+        dir_in[2 * i + 1] = c->mesh_dir[io].n_vertices;
+        old_first[i] = c->mesh_dir[io].first_vertex;
+      }
+    }
+  }
+  c->mesh_changed.resize(3 * nr);
+  for (size_t r = 0; r < nr; ++r) mesh_block_of(R[r], &c->mesh_changed[3 * r]);
+  unsigned long long degenerate = 0;
+  uint32_t total = 0;
+  const int from = c->mesh_cur, to = c->mesh_cur ^ 1;
+  if (nb) {
+    const size_t nvb = (size_t)512 << (3 * sh);
+    const uint32_t tiles_per_block = 1u << (3 * sh);
+    if (nr * (size_t)tiles_per_block >= (1ull << 31) || nr * nvb * 5 >= (1ull << 36)) {
+      c->err = "ks_mesh_update: too many blocks for one call";
+      return KS_ERR_INVALID_ARG;
+    }
+    int rc;
+    if ((rc = mesh_scratch(c, 0, std::max<size_t>(nr, 1) * 12)) || (rc = mesh_scratch(c, 1, std::max<size_t>(nr, 1) * nvb)) ||
+        (rc = mesh_scratch(c, 2, std::max<size_t>(nr, 1) * nvb * 4)) || (rc = mesh_scratch(c, 3, std::max<size_t>(nr, 1) * 4)) ||
+        (rc = mesh_scratch(c, 4, std::max<size_t>(nr, 1) * 4)) || (rc = mesh_scratch(c, 5, nb * 8)) || (rc = mesh_scratch(c, 6, (nb + 1) * 4)) ||
+        (rc = mesh_scratch(c, 7, nb * 4)) || (rc = mesh_scratch(c, 8, nb * 12)) || (rc = mesh_scratch(c, 9, 8)))
+      return rc;
+    MeshWork W{};
+    W.rblocks = (const int32_t*)c->d_mesh_buf[0];
+    W.cube_cnt = c->d_mesh_buf[1];
+    W.cube_off = (uint32_t*)c->d_mesh_buf[2];
+    W.block_tri = (uint32_t*)c->d_mesh_buf[3];
+    W.rb_first = (uint32_t*)c->d_mesh_buf[4];
+    W.degenerate = (unsigned long long*)c->d_mesh_buf[9];
+    W.voxel_size = c->cfg.voxel_size;
+    W.min_weight = m->min_weight;
+    W.vps_shift = sh;
+    uint32_t* d_dir_out = (uint32_t*)c->d_mesh_buf[6];
+    HIPCHK(c, hipMemsetAsync(W.degenerate, 0, 8, st));
+    HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[5], dir_in.data(), nb * 8, hipMemcpyHostToDevice, st));
+    if (nr) {
+      HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[0], c->mesh_changed.data(), nr * 12, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemsetAsync(W.cube_cnt, 0, nr * nvb, st));
+      hipLaunchKernelGGL(k_mesh_tiles<false>, dim3((uint32_t)(nr * tiles_per_block)), dim3(512), 0, st, c->table, c->pool, W, MeshArena{});
+      hipLaunchKernelGGL(k_mesh_scan, dim3((uint32_t)nr), dim3(1024), 0, st, W);
+    }
+    hipLaunchKernelGGL(k_mesh_dir, dim3(1), dim3(1024), 0, st, W, (const uint2*)c->d_mesh_buf[5], (uint32_t)nb, d_dir_out, (uint32_t*)c->d_mesh_buf[7]);
+    std::vector<uint32_t> first(nb + 1);
+    HIPCHK(c, hipMemcpyAsync(first.data(), d_dir_out, (nb + 1) * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&degenerate, W.degenerate, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    total = first[nb];
+    if ((rc = mesh_arena_reserve(c, to, total))) return rc;
+    std::vector<uint32_t> moves;
+    for (size_t i = 0; i < nb; ++i) {
+      dir[i].first_vertex = first[i];
+      dir[i].n_vertices = first[i + 1] - first[i];
+      if (dir_in[2 * i] == 0xffffffffu && dir[i].n_vertices) {
+        moves.push_back(old_first[i]);
+        moves.push_back(first[i]);
+        moves.push_back(dir[i].n_vertices);
+      }
+    }
+    if (nr && total) hipLaunchKernelGGL(k_mesh_tiles<true>, dim3((uint32_t)(nr * tiles_per_block)), dim3(512), 0, st, c->table, c->pool, W, c->mesh_arena[to]);
+    if (!moves.empty()) {
+      HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[8], moves.data(), moves.size() * 4, hipMemcpyHostToDevice, st));
+      hipLaunchKernelGGL(k_mesh_copy, dim3((uint32_t)(moves.size() / 3)), dim3(256), 0, st, c->mesh_arena[from], c->mesh_arena[to], (const uint32_t*)c->d_mesh_buf[8]);
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+  } else if (nt) {
+    HIPCHK(c, hipStreamSynchronize(st));
+  }
+  c->mesh_cur = to;
+  c->mesh_dir.swap(dir);
+  c->mesh_valid = true;
+  c->mesh_min_weight = m->min_weight;
+  if (stats) {
+    stats->blocks_meshed = nr;
+    stats->blocks_total = nb;
+    stats->triangles_total = total / 3;
+    stats->degenerate_dropped = degenerate;
+    uint64_t ch = 0;
+    for (size_t i = 0; i < nb; ++i)
+      if (dir_in[2 * i] != 0xffffffffu) ch += c->mesh_dir[i].n_vertices / 3;
+    stats->triangles_changed = ch;
+  }
+  return KS_OK;
+}
+
+int ks_mesh_size(ks_ctx* c, size_t* n_blocks, size_t* n_vertices) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  size_t b = 0, v = 0;
+  for (const ks_mesh_block& d : c->mesh_dir) {
+    b += d.n_vertices != 0;
+    v += d.n_vertices;
+  }
+  if (n_blocks) *n_blocks = b;
+  if (n_vertices) *n_vertices = v;
+  return KS_OK;
+}
+
+int ks_mesh_download(ks_ctx* c, ks_mesh_block* blocks, size_t cap_blocks, float* xyz, float* normals, uint8_t* rgba, uint8_t* labels,
+                     size_t cap_vertices) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  size_t nbl = 0, nv = 0;
+  ks_mesh_size(c, &nbl, &nv);
+  if ((blocks && cap_blocks < nbl) || ((xyz || normals || rgba || labels) && cap_vertices < nv)) {
+    c->err = "ks_mesh_download: output buffer too small (call ks_mesh_size first)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (blocks) {
+    size_t o = 0;
+    for (const ks_mesh_block& d : c->mesh_dir)
+      if (d.n_vertices) blocks[o++] = d;
+  }
+  if (nv == 0) return KS_OK;
+  const MeshArena& A = c->mesh_arena[c->mesh_cur];
+  hipStream_t st = c->stream;
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, A.xyz, nv * 12, hipMemcpyDeviceToHost, st));
+  if (normals) HIPCHK(c, hipMemcpyAsync(normals, A.nrm, nv * 12, hipMemcpyDeviceToHost, st));
+  if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, A.rgba, nv * 4, hipMemcpyDeviceToHost, st));
+  if (labels) HIPCHK(c, hipMemcpyAsync(labels, A.label, nv, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return KS_OK;
+}
+
+int ks_mesh_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
+  *n = c->mesh_changed.size() / 3;
+  if (out_xyz) {
+    if (cap < *n) {
+      c->err = "ks_mesh_changed_blocks: output buffer too small";
+      return KS_ERR_INVALID_ARG;
+    }
+    std::memcpy(out_xyz, c->mesh_changed.data(), c->mesh_changed.size() * sizeof(int32_t));
+  }
   return KS_OK;
 }
 
@@ -3417,6 +3698,13 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
 // frame counters and the early-out table stay as the frames so far left them — what vxb::TsdfServer::clear() does to the
 // reference's integrator, which it does not touch.  Frames in flight are completed first (their stage B has already
 // entered its marks); without it a frame that was never applied is dropped with the map.
+static void mesh_reset(ks_ctx* c) {
+  c->mesh_valid = false;
+  c->mesh_blocks.clear();
+  c->mesh_dir.clear();
+  c->mesh_changed.clear();
+  c->mesh_tiles_seen = 0;
+}
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {
     if (int rc = quiesce(c)) return rc;
@@ -3433,6 +3721,8 @@ static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   HIPCHK(c, hipMemset(c->table.ent, 0xff, ((size_t)c->table.mask + 1) * sizeof(TileEntry)));
   HIPCHK(c, hipMemset(c->pool.updated, 0, c->cfg.max_tiles));
   HIPCHK(c, hipMemset(c->pool.dirty, 0, c->cfg.max_tiles));
+  HIPCHK(c, hipMemset(c->pool.mesh_stale(), 0, c->cfg.max_tiles));
+  mesh_reset(c);   // the mesh goes with the map
   HIPCHK(c, hipMemset(c->d_state, 0, 64 * (kSlots + 1)));
   if (!keep_integrator_state) {
     // a cleared context behaves like a fresh one: both approximate sets as their constructor leaves them

@@ -130,6 +130,7 @@ struct TileTable {
   uint32_t max_tiles;
 };
 
+constexpr size_t kFlagPlane = 1u << 23;   // tiles a pool can hold at most (grow_pool), = offset of Pool::mesh_stale() in `updated`
 struct Pool {
   // One 128-byte record per voxel (array of structures, 8 x uint4):
   //   dword 0 distance | 1 weight | 2 colour (rgba) | 3 label (255 = never updated)
@@ -139,6 +140,11 @@ struct Pool {
   uint4* vox;          // [tile][512][8]
   uint8_t* updated;    // per tile: touched since the host last fetched the updated-block list
   uint8_t* dirty;      // per tile: touched since the last multi-GPU reduce (ks_reduce)
+  // per tile: a voxel's distance, weight, colour or label written since ks_mesh_update last meshed it (set wherever the other
+  // two flags are, and by upload and merge; cleared by the mesher alone).  A second plane of the `updated` allocation, at the
+  // fixed offset kFlagPlane (the pool never holds that many tiles), so that Pool — a kernel argument of the whole hot path —
+  // keeps its size.
+  __host__ __device__ __forceinline__ uint8_t* mesh_stale() const { return updated + kFlagPlane; }
 };
 
 struct FrameParams {

@@ -152,6 +152,35 @@ int main(int argc, char** argv) {
                 integrate_ms / n_frames, n_frames, tail_frames ? tail_ms / tail_frames : 0.0, tail_frames,
                 pipeline ? "kOnDemand + pipeline_frames" : "kEveryFrame layer sync");
 
+  // KS_DEMO_MESH=<file>: the semantic mesh, made on the device without any layer sync (updateMesh), written as
+  // { u32 blocks; per block: i32 index[3], u32 n, n x Point vertices, n x Point normals, n x Color, n x u8 label }
+  if (const char* mesh_path = std::getenv("KS_DEMO_MESH")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    std::vector<kimera::HipSemanticTsdfIntegrator::MeshBlock> changed;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->updateMesh(false, &changed);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* mf = std::fopen(mesh_path, "wb");
+    if (!mf) return 9;
+    const uint32_t n_mesh_blocks = changed.size();
+    std::fwrite(&n_mesh_blocks, 4, 1, mf);
+    size_t n_vertices = 0;
+    for (const auto& mb : changed) {
+      const int32_t idx[3] = {mb.index.x(), mb.index.y(), mb.index.z()};
+      const uint32_t n = mb.vertices.size();
+      std::fwrite(idx, 4, 3, mf);
+      std::fwrite(&n, 4, 1, mf);
+      std::fwrite(mb.vertices.data(), sizeof(vxb::Point), n, mf);
+      std::fwrite(mb.normals.data(), sizeof(vxb::Point), n, mf);
+      std::fwrite(mb.colors.data(), sizeof(vxb::Color), n, mf);
+      std::fwrite(mb.labels.data(), 1, n, mf);
+      n_vertices += n;
+    }
+    std::fclose(mf);
+    std::printf("adapter_demo: updateMesh %.3f ms, %u blocks, %zu triangles\n", ms, n_mesh_blocks, n_vertices / 3);
+  }
+
   vxb::BlockIndexList blocks;
   tsdf_layer.getAllAllocatedBlocks(&blocks);
   std::sort(blocks.begin(), blocks.end(), [](const vxb::BlockIndex& a, const vxb::BlockIndex& b) {

@@ -219,6 +219,48 @@ void HipSemanticTsdfIntegrator::clearDeviceMap(bool keep_integrator_state) {
   else check(ks_clear(ctx_), "ks_clear");
 }
 
+bool HipSemanticTsdfIntegrator::updateMesh(bool only_mesh_updated_blocks, std::vector<MeshBlock>* changed) {
+  CHECK_NOTNULL(changed);
+  changed->clear();
+  ks_mesh_config mc;
+  ks_mesh_default_config(&mc);
+  mc.only_stale = only_mesh_updated_blocks ? 1 : 0;
+  check(ks_mesh_update(ctx_, &mc, &last_mesh_stats_), "ks_mesh_update");
+  size_t n_changed = 0, n_blocks = 0, n_vertices = 0;
+  check(ks_mesh_changed_blocks(ctx_, nullptr, 0, &n_changed), "ks_mesh_changed_blocks");
+  if (n_changed == 0) return false;
+  std::vector<int32_t> idx(3 * n_changed);
+  check(ks_mesh_changed_blocks(ctx_, idx.data(), n_changed, &n_changed), "ks_mesh_changed_blocks");
+  check(ks_mesh_size(ctx_, &n_blocks, &n_vertices), "ks_mesh_size");
+  static_assert(sizeof(vxb::Point) == 12 && sizeof(vxb::Color) == 4, "mesh element layout");
+  std::vector<ks_mesh_block> dir(n_blocks);
+  std::vector<vxb::Point> xyz(n_vertices), nrm(n_vertices);
+  std::vector<vxb::Color> rgba(n_vertices);
+  std::vector<uint8_t> labels(n_vertices);
+  check(ks_mesh_download(ctx_, dir.data(), n_blocks, reinterpret_cast<float*>(xyz.data()), reinterpret_cast<float*>(nrm.data()),
+                         reinterpret_cast<uint8_t*>(rgba.data()), labels.data(), n_vertices),
+        "ks_mesh_download");
+  // both lists ascend by (x, y, z); a changed block without an entry in the directory has no triangles any more
+  changed->resize(n_changed);
+  size_t d = 0;
+  auto less = [](const int32_t* a, const int32_t* b) {
+    return a[0] != b[0] ? a[0] < b[0] : (a[1] != b[1] ? a[1] < b[1] : a[2] < b[2]);
+  };
+  for (size_t i = 0; i < n_changed; ++i) {
+    MeshBlock& mb = (*changed)[i];
+    const int32_t* b = &idx[3 * i];
+    mb.index = vxb::BlockIndex(b[0], b[1], b[2]);
+    while (d < n_blocks && less(dir[d].block, b)) ++d;
+    if (d == n_blocks || less(b, dir[d].block)) continue;
+    const size_t a = dir[d].first_vertex, n = dir[d].n_vertices;
+    mb.vertices.assign(xyz.begin() + a, xyz.begin() + a + n);
+    mb.normals.assign(nrm.begin() + a, nrm.begin() + a + n);
+    mb.colors.assign(rgba.begin() + a, rgba.begin() + a + n);
+    mb.labels.assign(labels.begin() + a, labels.begin() + a + n);
+  }
+  return true;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

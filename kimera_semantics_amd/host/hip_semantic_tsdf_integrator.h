@@ -94,6 +94,22 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// (ks_clear_voxels) — vxb::TsdfServer::clear() removes the TSDF blocks and leaves the integrator and the semantic layer
   /// alone: integration/server.patch syncs, lets the base class clear, empties the GPU map this way and uploads what survived.
   void clearDeviceMap(bool keep_integrator_state = false);
+
+  /// One block of the semantic mesh: the fields of vxb::Mesh (three vertices per triangle, no indices) plus the arg-max
+  /// label of the voxel that contains each vertex, in types this adapter already uses.
+  struct MeshBlock {
+    vxb::BlockIndex index;
+    std::vector<vxb::Point> vertices, normals;
+    std::vector<vxb::Color> colors;
+    std::vector<uint8_t> labels;
+  };
+  /// Refreshes the mesh ON THE DEVICE (ks_mesh_update: marching cubes over the resident tiles) and hands back the blocks
+  /// whose mesh it replaced — blocks that are empty now included, so a caller can clear them.  Needs NO syncLayers(): the
+  /// voxels stay in HBM, only triangles travel.  only_mesh_updated_blocks = false meshes everything.  Returns true when
+  /// `changed` is not empty.  What vxb::MeshIntegrator::generateMesh + the layer sync before it do in the reference's
+  /// server ("Mesh without a layer sync").
+  bool updateMesh(bool only_mesh_updated_blocks, std::vector<MeshBlock>* changed);
+  const ks_mesh_stats& lastMeshStats() const { return last_mesh_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -105,6 +121,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   Method method_;
   DeviceOptions options_;
   ks_frame_stats last_stats_{};
+  ks_mesh_stats last_mesh_stats_{};
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand
   struct Staging {

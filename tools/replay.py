@@ -2,9 +2,10 @@
 """Offline replay through the MI355X integrator — the role of the reference's kimera_semantics_rosbag executable
 (kimera_semantics_ros/src/kimera_semantics_rosbag.cpp:83-141) for the path this repository accelerates: read a ROS1
 bag (or generate the synthetic stand-in), compose T_G_C = T_G_B * T_B_C per depth image, integrate depth + labels on
-the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  Meshing / ESDF / map saving stay on the host side
-of the drop-in boundary (out of scope).
-  python tools/replay.py --synthetic 50 [--method merged]
+the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  The semantic mesh — what the reference's executable
+generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every; ESDF and
+map saving stay on the host side of the drop-in boundary (out of scope).
+  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -34,6 +35,8 @@ def main():
     ap.add_argument("--label-csv", help="the reference's label CSV (name,red,green,blue,alpha,id); default: the synthetic palette")
     ap.add_argument("--voxel-size", type=float, default=0.05)
     ap.add_argument("--pipeline-frames", type=int, default=4)
+    ap.add_argument("--mesh", metavar="OUT.ply", help="extract the semantic mesh at the end of the replay and write it (binary PLY with a label property)")
+    ap.add_argument("--mesh-every", type=int, default=0, metavar="N", help="refresh the mesh on the device (only_stale) every N frames")
     a = ap.parse_args()
     if a.bag:
         seq = FS.read_rosbag(a.bag, a.depth_topic, a.semantic_topic, a.camera_info_topic, a.sensor_frame, a.base_link_frame, a.world_frame)
@@ -57,9 +60,17 @@ def main():
     integ.set_color_to_label(lut[:21], np.arange(21, dtype=np.uint8))
     upd = 0
 
+    refresh_s, refreshes, n_seen = 0.0, [], 0
+
     def acc(fr, T, st):
-        nonlocal upd
+        nonlocal upd, refresh_s, n_seen
         upd += st.n_voxel_updates
+        n_seen += 1
+        if a.mesh_every and n_seen % a.mesh_every == 0:
+            t1 = time.perf_counter()
+            m = integ.mesh(only_stale=True)        # (completes the frames in flight, like every query)
+            refresh_s += time.perf_counter() - t1
+            refreshes.append((m.stats["blocks_meshed"], m.stats["blocks_total"], m.n_triangles))
     t0 = time.perf_counter()
     out = FS.replay(seq, integ, use_label_img=not a.bag, on_frame=acc)
     upd += integ.flush().n_voxel_updates
@@ -68,6 +79,18 @@ def main():
     print(f"{out['integrated']} frames integrated ({out['skipped_no_tf']} skipped: no tf) in {dt:.3f} s: "
           f"{out['integrated'] / dt:.1f} frames/s incl. H2D of the images, {upd / dt / 1e6:.1f} M voxel updates/s, "
           f"{len(integ.block_indices())} blocks")
+    if refreshes:
+        print(f"{len(refreshes)} mesh refreshes (only_stale, incl. the download) in {refresh_s * 1e3:.1f} ms of the above: "
+              f"{refresh_s / len(refreshes) * 1e3:.2f} ms each; last: {refreshes[-1][0]} of {refreshes[-1][1]} blocks re-meshed, "
+              f"{refreshes[-1][2]} triangles")
+    if a.mesh:
+        from kimera_semantics_amd.mesh import write_ply
+        t1 = time.perf_counter()
+        m = integ.mesh(only_stale=bool(refreshes))
+        t_mesh = time.perf_counter() - t1
+        write_ply(a.mesh, m)
+        print(f"mesh: {m.n_triangles} triangles in {len(m.blocks)} blocks, labels {sorted(set(m.labels.tolist()))}, "
+              f"{t_mesh * 1e3:.2f} ms (extraction + download) -> {a.mesh}")
 
 
 if __name__ == "__main__":
