@@ -403,6 +403,12 @@ int ks_update_stats(ks_ctx* ctx, uint64_t out[4]);
 /* How the context pipelines: out[0] = frames of lag in effect (0: one frame at a time — what ks_create made of
  * ks_config.pipeline_frames), out[1] = frame slots, out[2] = frames per stage-B batch, out[3] = march streams. */
 int ks_pipeline_shape(ks_ctx* ctx, int32_t out[4]);
+/* Diagnostics (host arithmetic, no device involved): the launch shape of the early-out's ordered phases for a context whose
+ * frame slots hold cap_points points, integration_order_mode and early_out_phase_growth (16..4096) as in ks_config.  Per phase
+ * j < max_phases: out[3 j] and out[3 j + 1] = its generations [g0, g1), out[3 j + 2] = wavefronts launched per frame = the most
+ * (chain, sub-run) work items any frame of at most cap_points points can have in that phase (0: no such frame reaches the
+ * phase; it is not launched).  Returns the number of phases (>= 0; out may be NULL with max_phases = 0) or KS_ERR_INVALID_ARG. */
+int ks_seed_launch_shape(int32_t integration_order_mode, int32_t early_out_phase_growth, uint64_t cap_points, uint32_t* out, int32_t max_phases);
 
 #ifdef __cplusplus
 }

@@ -120,6 +120,7 @@ struct FrameSlot {
   uint32_t* d_lp = nullptr;         // exclusive prefix of d_cnt inside blocks of kScanBlock
   unsigned long long* d_bt = nullptr;  // block totals of that scan
   uint8_t* d_live = nullptr;        // fast: position holds a ray that survived start-voxel dedup
+  uint32_t *d_seed_gen = nullptr, *d_seed_items = nullptr, *d_seed_n = nullptr;   // early-out: the seed's work list (k_seed_list -> k_test)
   bool wide = false;                // stage B uses a whole wavefront per ray (long rays)
   FrameParams* d_F = nullptr;       // the frame's parameters in device memory (stage B reads them from there)
   uint64_t *d_gkeys = nullptr, *d_rkeys = nullptr;  // anti-grazing: this frame's sorted end-voxel keys / key per bundle
@@ -215,6 +216,11 @@ struct ks_ctx {
   Counters* d_retry_counters = nullptr;  // scratch of the pair-buffer overflow retry
   std::atomic<size_t> pairs_hint{0};     // largest pair count of a frame so far (written by the thread that runs the tails, read by the caller's)
   bool uses_early_out = false;           // fast integrator whose consecutive-collision limit can fire
+  // the seed's launch shape for cap_points (seed_launch_shape; ensure_points): per phase its generations, its part of the
+  // slots' item lists and the wavefronts launched per frame — on the host for stage B's grids, on the device for k_seed_list
+  std::vector<SeedPhase> seed_phases;
+  SeedPhase* d_seed_phases = nullptr;
+  size_t seed_cap_items = 0;             // KS_DEBUG=1 KS_SEED_CAP_ITEMS=<n>: no phase's launch covers more items (tests: the overflow guard)
   // Pipelined contexts enqueue the tail of frame i-lag on a helper thread while the calling thread enqueues
   // stages A and B of frame i (the host, not the GPU, bounds small frames: ~25 launches of ~8 us each per
   // frame).  The call still returns only after both are done, so what a call delivers does not change.
@@ -536,6 +542,41 @@ std::vector<uint32_t> phase_bounds(uint32_t n_gen, int growth) {
   }
   return b;
 }
+// (chain, sub-run) pairs that EXIST in phase [g0, g1) of a frame of n points — those with at least one integration position
+// below n; the ones that hold a live ray (the items of k_seed_list) are among them
+inline uint64_t seed_items_of(int order_mode, size_t n, uint32_t g0, uint32_t g1) {
+  if (n == 0) return 0;
+  const uint64_t chains = order_chains(order_mode, n), full = n / chains, part = n % chains;   // `part` chains reach one generation further
+  auto subs = [&](uint64_t gens) -> uint64_t {
+    const uint64_t hi = std::min<uint64_t>(g1, gens);
+    return hi > g0 ? (hi - g0 + kSubRun - 1) / kSubRun : 0;
+  };
+  return (chains - part) * subs(full) + part * subs(full + 1);
+}
+// The seed's launch shape for a slot of `cap` points: the phases of the capacity's generation count, and per phase the most
+// items ANY frame of at most cap points can have in it (item_cap = wavefronts launched per frame; 0 = no frame reaches the
+// phase, nothing is launched).  The chain count and the generation count never peak together — in the default order a
+// frame of n points has n / 1024 chains and fewer than 1024 + 1024 / (n / 1024) + 1 generations — so this is far below their
+// product.  For a given chain count the items grow with n: the maximum is taken over the largest frame of every chain count.
+std::vector<SeedPhase> seed_launch_shape(int order_mode, int growth, size_t cap) {
+  const uint32_t n_gen = order_generations_cap(order_mode, cap);
+  const std::vector<uint32_t> B = phase_bounds(n_gen, growth);
+  std::vector<SeedPhase> out;
+  uint64_t off = 0;
+  for (size_t j = 0; j < B.size(); ++j) {
+    const uint32_t g0 = B[j], g1 = (j + 1 < B.size()) ? B[j + 1] : n_gen;
+    uint64_t m = 0;
+    if (order_mode == KS_ORDER_MIXED) {
+      m = seed_items_of(order_mode, std::min<size_t>(cap, kOrderStep - 1), g0, g1);   // fewer than 1024 points: one generation of them
+      for (size_t q = 1; q <= cap / kOrderStep; ++q) m = std::max(m, seed_items_of(order_mode, std::min<size_t>(cap, q * kOrderStep + kOrderStep - 1), g0, g1));
+    } else {
+      m = seed_items_of(order_mode, cap, g0, g1);   // 1024 chains whatever n
+    }
+    out.push_back(SeedPhase{g0, g1, (uint32_t)off, (uint32_t)m});
+    off += m;
+  }
+  return out;
+}
 
 // longest possible ray of a frame of this context, in voxels
 size_t steps_max_of(const ks_config& cfg, float voxel_size_inv) {
@@ -554,7 +595,33 @@ int ensure_points(ks_ctx* c, size_t n) {
   if ((rc = dev_alloc(c, &c->d_labels, cap))) return rc;
   ++c->buffers_epoch;
   const size_t scan_cap = (c->cfg.method == KS_METHOD_MERGED ? 2 : 1) * cap;
+  size_t seed_items = 0;
+  if (c->uses_early_out) {
+    // the seed's launch shape and work-list sizes follow the capacity (the captured stage-B graphs are keyed by it)
+    c->seed_phases = seed_launch_shape(c->cfg.integration_order_mode, c->cfg.early_out_phase_growth, cap);
+    uint32_t off = 0;
+    for (SeedPhase& P : c->seed_phases) {
+      // (the fields of an item word, ks_k_march.h: nowhere near with the 2^22 points the early-out's marks allow)
+      if ((P.g1 - P.g0 + kSubRun - 1) / kSubRun > (1u << kSeedSubBits) || order_chains_cap(c->cfg.integration_order_mode, cap) > (1u << kSeedChainBits)) {
+        c->err = "point cloud too large for the early-out's work list";
+        return KS_ERR_INVALID_ARG;
+      }
+      if (c->seed_cap_items) P.item_cap = (uint32_t)std::min<size_t>(P.item_cap, c->seed_cap_items);
+      P.item_off = off;
+      off += P.item_cap;
+    }
+    seed_items = off;
+    if ((rc = dev_alloc(c, &c->d_seed_phases, c->seed_phases.size()))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->d_seed_phases, c->seed_phases.data(), c->seed_phases.size() * sizeof(SeedPhase), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
   for (int i = 0; i < (c->cfg.pipeline_frames ? c->n_slots : 1); ++i) {
+    if (c->uses_early_out) {
+      // (one generation of slack: a frame's last generation may be partial)
+      if ((rc = dev_alloc(c, &c->slot[i].d_seed_gen, cap + order_chains_cap(c->cfg.integration_order_mode, cap)))) return rc;
+      if ((rc = dev_alloc(c, &c->slot[i].d_seed_items, seed_items))) return rc;
+      if ((rc = dev_alloc(c, &c->slot[i].d_seed_n, c->seed_phases.size()))) return rc;
+    }
     if ((rc = dev_alloc(c, &c->slot[i].d_rays, cap))) return rc;
     if ((rc = dev_alloc(c, &c->slot[i].d_ray_list, cap))) return rc;
     if ((rc = dev_alloc(c, &c->slot[i].d_cnt, scan_cap))) return rc;
@@ -733,7 +800,6 @@ void resolve_prof(ks_ctx* c, int set) {
 SlotView slot_view(const FrameSlot& S, Counters* counters = nullptr) {
   SlotView v{};
   v.F = S.d_F;
-  v.live = S.d_live;
   v.rays = S.d_rays;
   v.cnt = S.d_cnt;
   v.lp = S.d_lp;
@@ -744,6 +810,9 @@ SlotView slot_view(const FrameSlot& S, Counters* counters = nullptr) {
   v.C = counters ? counters : S.d_counters;
   v.host_snap = (uint32_t*)S.h_snap;
   v.eo_stats = S.d_eo_ctl ? &S.d_eo_ctl->n_x : nullptr;
+  v.seed_gen = S.d_seed_gen;
+  v.seed_items = S.d_seed_items;
+  v.seed_n = S.d_seed_n;
   return v;
 }
 
@@ -777,21 +846,18 @@ void enqueue_stage_b(ks_ctx* c, const BatchView& V, uint32_t nb, bool wide, hipS
   const size_t n = c->cap_points;  // NOT the frame's point count: see launch_emit
   if (c->uses_early_out && part != 2) {
     // ordered-phase early-out: per phase, k_test decides how far the phase's rays get against the set as it
-    // stood when the phase began and enters their marks (ks_k_march.h)
-    const uint32_t n_gen = order_generations_cap(cfg.integration_order_mode, n);
-    const uint32_t chains_cap = order_chains_cap(cfg.integration_order_mode, n);
-    const std::vector<uint32_t> B = phase_bounds(n_gen, cfg.early_out_phase_growth);
-    for (size_t j = 0; j < B.size(); ++j) {
-      const uint32_t g0 = B[j], g1 = (j + 1 < B.size()) ? B[j + 1] : n_gen;  // k_test ends the frame's last phase at ITS n
-      const uint32_t n_sub = (g1 - g0 + kSubRun - 1) / kSubRun;  // wavefronts per chain (worst case: every ray live)
+    // stood when the phase began and enters their marks (ks_k_march.h).  One wavefront per item of the phase's work list
+    // (built by stage A: k_seed_list, frame_front); the launch covers what a frame of the slot's capacity can have (seed_launch_shape),
+    // a phase no such frame reaches is not launched, and k_test ends the frame's last phase at ITS n.
+    for (size_t j = 0; j < c->seed_phases.size(); ++j) {
+      const SeedPhase& P = c->seed_phases[j];
+      if (P.item_cap == 0) continue;
       const uint32_t steps_cap = (uint32_t)((steps_max + 3) & ~(size_t)3);
       const size_t lds_wave = (size_t)test_lds_words64(steps_cap) * sizeof(unsigned long long);
       const uint32_t wpb = lds_wave * 4 <= 60 * 1024 ? 4u : lds_wave * 2 <= 60 * 1024 ? 2u : 1u;  // wavefronts per block
-      // (a frame with fewer chains than the capacity allows finds its (chain, sub-run) pairs among the first wavefronts; the rest
-      // see no live ray and end)
-      const dim3 grid((chains_cap * n_sub + wpb - 1) / wpb, nb), block(64 * wpb);
-      if (c->test_overlap) hipLaunchKernelGGL(k_test<true>, grid, block, lds_wave * wpb, sm, V, g0, g1, steps_cap);
-      else hipLaunchKernelGGL(k_test<false>, grid, block, lds_wave * wpb, sm, V, g0, g1, steps_cap);
+      const dim3 grid((P.item_cap + wpb - 1) / wpb, nb), block(64 * wpb);
+      if (c->test_overlap) hipLaunchKernelGGL(k_test<true>, grid, block, lds_wave * wpb, sm, V, P.g0, P.g1, (uint32_t)j, P.item_off, P.item_cap, steps_cap);
+      else hipLaunchKernelGGL(k_test<false>, grid, block, lds_wave * wpb, sm, V, P.g0, P.g1, (uint32_t)j, P.item_off, P.item_cap, steps_cap);
     }
   }
   if (part == 1) return;
@@ -1314,6 +1380,16 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     stage_mark(c, S.prof_set, 2);
     hipLaunchKernelGGL(k_dedup, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set, S.d_ray_list,
                        S.d_rays, S.d_cnt, S.d_live, S.d_counters);
+    if (c->uses_early_out && n > 0) {
+      // live[] is final: the work list of the seed's phases (k_test), here and not at the head of stage B's chain of
+      // dependent launches.  Only the phases this frame reaches.
+      const uint32_t n_gen = (uint32_t)((n + F.chains - 1) / F.chains);
+      uint32_t n_ph = 0;
+      while (n_ph < c->seed_phases.size() && c->seed_phases[n_ph].g0 < n_gen) ++n_ph;
+      HIPCHK(c, hipMemsetAsync(S.d_seed_n, 0, c->seed_phases.size() * sizeof(uint32_t), st));
+      hipLaunchKernelGGL(k_seed_list, dim3((F.chains + 63u) / 64u, n_ph), dim3(64 * kSeedSegs), 0, st, F, (const SeedPhase*)c->d_seed_phases,
+                         (const uint8_t*)S.d_live, S.d_seed_gen, S.d_seed_items, S.d_seed_n, S.d_counters);
+    }
     hipLaunchKernelGGL(k_dedup_commit, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set,
                        S.d_counters);
   } else {
@@ -2401,6 +2477,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   // (tests: start small, so that the overflow -> host-driven loop -> grow path is exercised)
   if (const char* e = dbg_env("KS_EXACT_CAP_MARKS")) eo_marks0 = std::max<size_t>(64, (size_t)atoll(e)), eo_marks_first = 0;
   if (const char* e = dbg_env("KS_EXACT_CAP_X")) eo_x0 = std::max<size_t>(8, (size_t)atoll(e));
+  // (tests: a seed launch that covers fewer items than a frame has — the frame must end in the error path, not lose rays)
+  if (const char* e = dbg_env("KS_SEED_CAP_ITEMS")) c->seed_cap_items = std::max<size_t>(1, (size_t)atoll(e));
   if (eo_marks_first > eo_marks0) c->eo_want_marks.store(eo_marks_first, std::memory_order_relaxed);
   if (ensure_points(c, cfg->max_points) != KS_OK || ensure_exact_slots(c, eo_marks0, eo_x0) != KS_OK) {
     g_create_error = c->err;
@@ -2444,7 +2522,7 @@ void ks_destroy(ks_ctx* c) {
       if (p) (void)hipFree(p);
   for (auto& S : c->slot) {
     for (void* p : {(void*)S.d_rays, (void*)S.d_deltas, (void*)S.d_ray_list, (void*)S.d_pairs, (void*)S.d_cnt, (void*)S.d_lp,
-                    (void*)S.d_bt, (void*)S.d_live, (void*)S.d_F, (void*)S.d_gkeys, (void*)S.d_rkeys,
+                    (void*)S.d_bt, (void*)S.d_live, (void*)S.d_seed_gen, (void*)S.d_seed_items, (void*)S.d_seed_n, (void*)S.d_F, (void*)S.d_gkeys, (void*)S.d_rkeys,
                     (void*)S.d_eo_keys[0], (void*)S.d_eo_keys[1], (void*)S.d_eo_vals[0], (void*)S.d_eo_vals[1], (void*)S.d_eo_tab, (void*)S.d_eo_xnode,
                     (void*)S.d_eo_cnt_b, (void*)S.d_eo_ux, (void*)S.d_eo_dirty, (void*)S.d_eo_list[0], (void*)S.d_eo_list[1], (void*)S.d_eo_chg,
                     (void*)S.d_eo_consulted, (void*)S.d_eo_lp, (void*)S.d_eo_bt, (void*)S.d_eo_ctl, (void*)S.d_eo_sort_ws, (void*)S.d_eo_hitb, (void*)S.d_eo_bits_a, (void*)S.d_eo_bits_b, (void*)S.d_eo_btp, (void*)S.d_eo_hseq, (void*)S.d_eo_where, (void*)S.d_eo_rinfo, (void*)S.d_eo_ckpt})
@@ -2452,6 +2530,7 @@ void ks_destroy(ks_ctx* c) {
     if (S.eo_committed) (void)hipEventDestroy(S.eo_committed);
   }
   if (c->d_eo_committed) (void)hipFree(c->d_eo_committed);
+  if (c->d_seed_phases) (void)hipFree(c->d_seed_phases);
   if (c->h_eo_state) (void)hipHostFree(c->h_eo_state);
   ksrs::release(c->sort_ws);
   ksrs::release(c->sort_ws_tail);
@@ -3828,6 +3907,19 @@ int ks_pipeline_shape(ks_ctx* c, int32_t out[4]) {
   out[2] = c->batch;
   out[3] = c->n_march;
   return KS_OK;
+}
+
+int ks_seed_launch_shape(int32_t order_mode, int32_t phase_growth, uint64_t cap_points, uint32_t* out, int32_t max_phases) {
+  if (order_mode < KS_ORDER_MIXED || order_mode > KS_ORDER_MIXED_1024_GROUPS || phase_growth < 16 || phase_growth > 4096 || cap_points == 0 ||
+      cap_points > kObsMaxPoints || (max_phases > 0 && !out))
+    return KS_ERR_INVALID_ARG;
+  const std::vector<SeedPhase> ph = seed_launch_shape(order_mode, phase_growth, std::max<size_t>((size_t)cap_points, 1024));   // (ensure_points: a slot holds 1024 points at least)
+  for (size_t j = 0; j < ph.size() && (int64_t)j < (int64_t)max_phases; ++j) {
+    out[3 * j] = ph[j].g0;
+    out[3 * j + 1] = ph[j].g1;
+    out[3 * j + 2] = ph[j].item_cap;
+  }
+  return (int)ph.size();
 }
 
 int ks_profile_enable(ks_ctx* c, int level) {

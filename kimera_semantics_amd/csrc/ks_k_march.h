@@ -178,7 +178,6 @@ __device__ __forceinline__ Dda dda_bcast(const Dda& d, int src) {
 constexpr int kBatchMax = 8;
 struct SlotView {
   const FrameParams* F;          // the frame's parameters in device memory
-  const uint8_t* live;           // fast: position holds a ray that survived the start-voxel dedup
   const RayDesc* rays;
   uint32_t* cnt;                 // updates per integration position (| kCntBroke)
   uint32_t* lp;                  // block-local exclusive prefix of cnt
@@ -189,6 +188,10 @@ struct SlotView {
   Counters* C;
   uint32_t* host_snap;           // pinned snapshot (k_publish)
   const uint32_t* eo_stats;      // exact early-out, event-driven: {X marks + 1, failure bits, rounds} of the frame (else nullptr)
+  // the seed's work list (k_seed_list -> k_test; contexts with the early-out only)
+  const uint32_t* seed_gen;      // per (phase, chain): the generations of its live rays, ascending
+  const uint32_t* seed_items;    // per phase: the (chain, sub-run) items that hold a live ray
+  const uint32_t* seed_n;        // per phase: how many
 };
 struct BatchView {
   SlotView s[kBatchMax];
@@ -204,9 +207,13 @@ constexpr uint32_t kCntBroke = 1u << 31;  // cnt[] flag: the ray stopped on a vo
 // FrameParams::chains: N / 1024 in the upstream form, 1024 in the other one); one launch per phase of generations
 // [g0, g1).  Inside a phase a chain's LIVE rays (those that survived the start-voxel dedup: nearly all of the
 // first generations, one in five to one in twenty of the late ones) are cut, in generation order, into SUB-RUNS
-// of 16; ONE WAVEFRONT owns a (chain, sub-run) and resolves its rays in generation order.  The launch covers the worst
-// case (every ray live: one wavefront per 16 generations); a wavefront finds its rays by ranking the chain's live
-// flags of the phase (64 generations per ballot) and ends at once if the chain has fewer than 16 * sub + 1 of them.
+// of 16; ONE WAVEFRONT owns a (chain, sub-run) and resolves its rays in generation order.  Which sub-runs hold a live
+// ray, and the generations of their rays, is a function of live[] alone: k_seed_list (below) lists them once per frame,
+// on stage A's stream right after the dedup.  Wavefront w of a phase's launch takes item w of the phase's list — its
+// chain, its sub-run, how many rays — and reads the <= 16 generations with one coalesced load; wavefronts beyond the
+// frame's item count leave after reading the count.  The launch covers the most items ANY frame that fits the slot's
+// capacity can have in that phase (host: seed_launch_shape), not the product of the largest chain count and the
+// largest generation count, which no frame reaches together.
 // A ray tests its voxels against (a) the
 // marks previous rays of its sub-run made (8 KiB of LDS, newest (generation, step) wins a slot) and
 // (b) the shared set as it stood when the phase began (read-only during the launch).
@@ -298,12 +305,87 @@ __device__ __forceinline__ bool priv_lookup(const unsigned long long* priv, uint
 // LDS per wavefront: private set | keys of the first 16 voxels of 16 rays | keys of one long ray | per-ray words
 __host__ __device__ inline uint32_t test_lds_words64(uint32_t steps_cap) { return kPrivSlots + 256u + steps_cap + 16u + (3u * kES + 1u) / 2u; }
 
+// ------------------------------------------------------------------------------------------
+// k_seed_list — the work list of k_test, built once per frame from live[] (final after k_dedup).
+//   gens[]   the positions of phase [g0, g1) are the block [g0 * chains, g1 * chains) of the integration order; inside
+//            that block chain c owns the (g1 - g0) entries from c * (g1 - g0) on and keeps there the generations of its
+//            live rays, ascending — the 16 of a sub-run are contiguous.  (g1 is cut at the frame's generation count; its
+//            last generation may be partial, so the array has one generation of slack beyond the capacity.)
+//   items[]  per phase, from SeedPhase::item_off on: one word per (chain, sub-run) that holds a live ray —
+//            [15:0] chain | [26:16] sub-run | [31:27] rays - 1 — in no particular order (a phase's wavefronts are
+//            independent: every test sees the shared set as it stood when the phase began, marks enter by atomicMax)
+//   n_items[] per phase: how many (zeroed before the launch).  More than SeedPhase::item_cap — the launch of the phase
+//            covers no more — raises the frame's error word: the frame is not applied, no ray is dropped silently.
+// A workgroup = 64 chains (a lane per chain: the flags of one generation are consecutive bytes) x 4 segments of the
+// phase's generations; blockIdx.y = phase.  Two passes over the flags (count, then place: the second hits the cache).
+// ------------------------------------------------------------------------------------------
+struct SeedPhase {
+  uint32_t g0, g1;        // generations [g0, g1) of the slot's capacity (a frame ends its last phase at ITS generation count)
+  uint32_t item_off;      // the phase's part of items[]
+  uint32_t item_cap;      // most items a frame that fits the capacity can have in this phase = wavefronts launched per frame
+};
+constexpr uint32_t kSeedChainBits = 16, kSeedSubBits = 11;   // (checked against the capacity by the host: ensure_points)
+constexpr uint32_t kSeedSegs = 4;
+__global__ void __launch_bounds__(64 * kSeedSegs) k_seed_list(FrameParams F, const SeedPhase* __restrict__ phases,
+                                                              const uint8_t* __restrict__ live, uint32_t* __restrict__ gens,
+                                                              uint32_t* __restrict__ items, uint32_t* __restrict__ n_items, Counters* C) {
+  __shared__ uint32_t s_cnt[kSeedSegs][64];
+  const SeedPhase P = phases[blockIdx.y];
+  const uint32_t n = F.n, n_chains = F.chains;
+  const uint32_t n_gen = (n + n_chains - 1u) / n_chains;
+  const uint32_t g0 = P.g0, g1 = P.g1 < n_gen ? P.g1 : n_gen;
+  if (g0 >= g1 || blockIdx.x * 64u >= n_chains) return;  // (the whole workgroup)
+  const uint32_t lane = lane_id(), seg = threadIdx.x >> 6, chain = blockIdx.x * 64u + lane;
+  const uint32_t len = g1 - g0, seg_len = (len + kSeedSegs - 1u) / kSeedSegs;
+  const uint32_t a = g0 + seg * seg_len < g1 ? g0 + seg * seg_len : g1, b = a + seg_len < g1 ? a + seg_len : g1;
+  auto flag = [&](uint32_t g) -> bool {
+    const uint32_t p = g * n_chains + chain;   // (< n + chains: 32 bits hold it, ks_create bounds n)
+    const bool in = chain < n_chains && p < n;
+    return live[in ? p : 0u] != 0 && in;       // (an unconditional load from a clamped address: the loads of a pass are in flight together)
+  };
+  uint32_t mine = 0;
+#pragma unroll 8
+  for (uint32_t g = a; g < b; ++g) mine += flag(g) ? 1u : 0u;
+  s_cnt[seg][lane] = mine;
+  __syncthreads();
+  uint32_t rank = 0, total = 0;
+  for (uint32_t s = 0; s < kSeedSegs; ++s) {
+    const uint32_t v = s_cnt[s][lane];
+    rank += s < seg ? v : 0u;
+    total += v;
+  }
+  uint32_t* __restrict__ mine_out = gens + (size_t)g0 * n_chains + (size_t)chain * len;   // (written only where a flag is set: chain < n_chains)
+#pragma unroll 8
+  for (uint32_t g = a; g < b; ++g)
+    if (flag(g)) mine_out[rank++] = g;
+  if (seg != 0) return;
+  // the chain's sub-runs that hold a ray: one atomic per wavefront for their places in the phase's list
+  const uint32_t n_it = (total + kSubRun - 1u) / kSubRun;
+  uint32_t x = n_it;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint32_t y = __shfl_up(x, o);
+    if (lane >= (uint32_t)o) x += y;
+  }
+  const uint32_t wave_total = __shfl(x, 63);
+  uint32_t base = 0;
+  if (lane == 0 && wave_total) base = atomicAdd(&n_items[blockIdx.y], wave_total);
+  base = __shfl(base, 0) + x - n_it;
+  for (uint32_t s = 0; s < n_it; ++s) {
+    const uint32_t left = total - s * kSubRun;
+    if (base + s < P.item_cap) items[P.item_off + base + s] = chain | (s << kSeedChainBits) | (((left < kSubRun ? left : kSubRun) - 1u) << (kSeedChainBits + kSeedSubBits));
+    else atomicOr(&C->err, kErrIndex);
+  }
+}
+// (pointers that SAY global memory, like the shared set's: the list's addresses come out of the kernel-argument struct by a dynamic index)
+typedef __attribute__((address_space(1))) const uint32_t seed_global_u32;
+
 template <bool OVERLAP>
-__global__ void __launch_bounds__(kTestThreads) k_test(BatchView V, uint32_t g0, uint32_t g1, uint32_t steps_cap) {
+__global__ void __launch_bounds__(kTestThreads) k_test(BatchView V, uint32_t g0, uint32_t g1, uint32_t phase, uint32_t item_off, uint32_t item_cap,
+                                                       uint32_t steps_cap) {
   // stage B kernels read the frame's parameters from device memory: the launch sequence of a frame slot is
   // then identical from frame to frame and is replayed as a captured graph
   const SlotView& sv = V.s[blockIdx.y];
-  const uint8_t* __restrict__ live = sv.live;
   const RayDesc* __restrict__ rays = sv.rays;
   uint32_t* __restrict__ cnt = sv.cnt;
   const Counters* C = sv.C;
@@ -340,44 +422,22 @@ __global__ void __launch_bounds__(kTestThreads) k_test(BatchView V, uint32_t g0,
   unsigned long long* lkeys = keys + 256;              // [steps_cap]          the long ray's voxels from step 16 on
   uint32_t* rinfo = (uint32_t*)(lkeys + steps_cap);    // [16] steps of the ray | [16] shared-set hit mask
   float* escr = (float*)(rinfo + 32);                  // [3 * kES] scratch of the parallel caster
-  // (looked at below: this load and the live flags are in flight together; an atomic load stays where it is written)
+  // (looked at below: this load, the item count and the item are in flight together; an atomic load stays where it is written)
   const uint32_t frame_err = __hip_atomic_load(&C->err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   const uint32_t w = blockIdx.x * (blockDim.x >> 6) + wave;
-  const uint32_t chain = w % n_chains, sub = w / n_chains;
+  // ---- which rays: item w of the phase's work list (k_seed_list); my_gen = generation of the ray lane l < 16 owns (~0u: none) ----
+  uint32_t n_items = ((seed_global_u32*)sv.seed_n)[phase];
+  const uint32_t item = ((seed_global_u32*)sv.seed_items)[item_off + (w < item_cap ? w : item_cap - 1u)];   // (unconditional, clamped: not behind the count)
+  if (n_items > item_cap) n_items = item_cap;   // (more than the launch covers: the builder has raised the frame's error word)
+  if (w >= n_items) return;
+  const uint32_t chain = item & ((1u << kSeedChainBits) - 1u), sub = (item >> kSeedChainBits) & ((1u << kSeedSubBits) - 1u);
+  const uint32_t n_mine = (item >> (kSeedChainBits + kSeedSubBits)) + 1u;
   {  // the launch covers the slot's capacity: the frame's last generation ends the last phase
     const uint32_t n_gen = (F.n + n_chains - 1u) / n_chains;
     if (g1 > n_gen) g1 = n_gen;
   }
-  // ---- which rays: my_gen = generation of the ray lane l < 16 owns (~0u: none) ----
   uint32_t my_gen = ~0u;
-  {
-    // rank of every live ray of the chain within the phase; ranks [16 sub, 16 sub + 16) are this wavefront's.  Four
-    // ballots' worth of flags are in flight at a time (a late phase of a 640x480 frame is 128 generations long).
-    const uint32_t r_lo = sub * kSubRun;
-    uint32_t seen = 0;
-    for (uint32_t gb = g0; gb < g1 && seen < r_lo + kSubRun; gb += 256u) {
-      uint8_t fl[4];
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        // (unconditional loads from a clamped address: a load under a branch would be waited for before the next is issued)
-        const uint32_t g = gb + 64u * (uint32_t)q + lane;
-        const bool in = g < g1 && (uint64_t)g * n_chains + chain < F.n;
-        fl[q] = live[in ? (uint64_t)g * n_chains + chain : (uint64_t)0];
-        if (!in) fl[q] = 0;
-      }
-#pragma unroll
-      for (int q = 0; q < 4; ++q) {
-        const unsigned long long m = __ballot(fl[q] != 0);
-        const uint32_t rank = seen + (uint32_t)__popcll(m & ((1ull << lane) - 1ull));
-        if (fl[q] != 0 && rank >= r_lo && rank < r_lo + kSubRun) rinfo[rank - r_lo] = gb + 64u * (uint32_t)q + lane;
-        seen += (uint32_t)__popcll(m);
-      }
-    }
-    if (seen <= r_lo) return;  // the chain has no 16 * sub + 1 live rays in this phase
-    KS_WAVE_LDS_ORDER();
-    if (lane < kSubRun && lane < seen - r_lo) my_gen = rinfo[lane];
-    KS_WAVE_LDS_ORDER();       // (rinfo is reused below)
-  }
+  if (lane < n_mine) my_gen = ((seed_global_u32*)sv.seed_gen)[g0 * n_chains + chain * (g1 - g0) + sub * kSubRun + lane];
   if (__ballot(my_gen != ~0u) == 0ull || (frame_err & (kErrLabel | kErrIndex))) return;
   const int lim = F.max_collisions;
 #ifdef KS_STATS
