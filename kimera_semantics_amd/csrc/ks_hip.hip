@@ -53,6 +53,7 @@
 
 #include "../../include/ks_hip.h"
 #include "ks_device_math.h"
+#include "ks_owned.h"
 #include "ks_radix_sort.h"
 
 using namespace ksd;
@@ -112,55 +113,62 @@ struct HostSnap {
 };
 struct FrameSlot {
   int index = 0;
-  RayDesc* d_rays = nullptr;
-  float* d_deltas = nullptr;        // merged: label histograms of mixed bundles
-  uint64_t* d_pairs = nullptr;      // (voxel, ray) pairs in integration order, written by k_emit
-  size_t cap_pairs_in = 0;
-  uint32_t* d_cnt = nullptr;        // updates per integration position (merged: 2 n entries)
-  uint32_t* d_lp = nullptr;         // exclusive prefix of d_cnt inside blocks of kScanBlock
-  unsigned long long* d_bt = nullptr;  // block totals of that scan
-  uint8_t* d_live = nullptr;        // fast: position holds a ray that survived start-voxel dedup
-  uint32_t *d_seed_gen = nullptr, *d_seed_items = nullptr, *d_seed_n = nullptr;   // early-out: the seed's work list (k_seed_list -> k_test)
+  DevBuf<RayDesc> d_rays;
+  DevBuf<float> d_deltas;           // merged: label histograms of mixed bundles
+  DevBuf<uint64_t> d_pairs;         // (voxel, ray) pairs in integration order, written by k_emit
+  DevBuf<uint32_t> d_cnt;           // updates per integration position (merged: 2 n entries)
+  DevBuf<uint32_t> d_lp;            // exclusive prefix of d_cnt inside blocks of kScanBlock
+  DevBuf<unsigned long long> d_bt;  // block totals of that scan
+  DevBuf<uint8_t> d_live;           // fast: position holds a ray that survived start-voxel dedup
+  DevBuf<uint32_t> d_seed_gen, d_seed_items, d_seed_n;   // early-out: the seed's work list (k_seed_list -> k_test)
   bool wide = false;                // stage B uses a whole wavefront per ray (long rays)
-  FrameParams* d_F = nullptr;       // the frame's parameters in device memory (stage B reads them from there)
-  uint64_t *d_gkeys = nullptr, *d_rkeys = nullptr;  // anti-grazing: this frame's sorted end-voxel keys / key per bundle
+  DevBuf<FrameParams> d_F;          // the frame's parameters in device memory (stage B reads them from there)
+  DevBuf<uint64_t> d_gkeys, d_rkeys;  // anti-grazing: this frame's sorted end-voxel keys / key per bundle
   // stage B of the batch that STARTS on this slot as captured graphs, valid for a (point count, buffers, batch size) key.
   // Exact early-out, event-driven fix point (ks_k_exact.h): THREE graphs (seed + marks + bulk rounds | finisher + commit |
   // scan + emission) with the wait for the previous frame's commit between the first two; otherwise g1 alone.
   // Two sets: [0] full batches, [1] partial ones (a flush ends a batch early: a stream that is flushed every K frames, K no
   // multiple of the batch, would otherwise re-capture on every change of the size).
-  struct GraphSet {
+  struct GraphSet {   // owns its graphs
     hipGraphExec_t g1 = nullptr, g2 = nullptr, g3 = nullptr;
     uint64_t key = 0;
+    GraphSet() = default;
+    GraphSet(const GraphSet&) = delete;
+    GraphSet& operator=(const GraphSet&) = delete;
+    ~GraphSet() { reset(); }
+    void reset() {
+      for (hipGraphExec_t* g : {&g1, &g2, &g3}) {
+        if (*g) (void)hipGraphExecDestroy(*g);
+        *g = nullptr;
+      }
+      key = 0;
+    }
   } b_graphs[2];
   // exact early-out, event-driven fix point (ks_k_exact.h): the slot's marks, per-slot table, X marks, lists
-  uint64_t* d_eo_keys[2] = {nullptr, nullptr};
-  uint32_t* d_eo_vals[2] = {nullptr, nullptr};
-  size_t eo_cap_marks = 0;
-  uint4* d_eo_tab = nullptr;
-  unsigned long long* d_eo_xnode = nullptr;
-  size_t eo_cap_x = 0;
-  uint32_t *d_eo_cnt_b = nullptr, *d_eo_ux = nullptr, *d_eo_dirty = nullptr, *d_eo_list[2] = {nullptr, nullptr}, *d_eo_chg = nullptr,
-           *d_eo_consulted = nullptr, *d_eo_lp = nullptr;
-  unsigned long long* d_eo_bt = nullptr;
-  EoCtl* d_eo_ctl = nullptr;
-  uint32_t* d_eo_sort_ws = nullptr;
-  size_t eo_sort_words = 0;
-  uint32_t *d_eo_hseq = nullptr, *d_eo_where = nullptr;   // per seed mark in emission order: voxel hash | index in M
-  uint4 *d_eo_rinfo = nullptr, *d_eo_ckpt = nullptr;      // per position: {u0, um, length, checkpoint step} | caster state there
-  uint8_t* d_eo_hitb = nullptr;            // first iteration: per mark in emission order, the visit is a hit
-  unsigned long long *d_eo_bits_a = nullptr, *d_eo_bits_b = nullptr;   // per mark of M: it counts under the current / next lengths
-  unsigned long long* d_eo_btp = nullptr;  // ... exclusive prefix of the scan's block totals
-  hipEvent_t eo_committed = nullptr;  // the frame's marks have entered the shared table
-  Counters* d_counters = nullptr;   // inside ks_ctx::d_state
-  uint32_t* d_ray_list = nullptr;   // rays to march (written by stage A, read by B)
-  HostSnap* h_snap = nullptr;       // pinned + device-visible: written by k_publish at the end of B
-  hipEvent_t a_done = nullptr;      // stage A complete
-  hipEvent_t ready = nullptr;       // snapshot has landed
-  hipEvent_t tail_done = nullptr;   // the tail has consumed this slot's buffers
-  hipEvent_t fork = nullptr, join = nullptr;  // tail: pairs sorted and long runs listed | long runs applied
-  hipEvent_t join_x = nullptr;                // the runs of more than kXLongRun updates applied (stream_xlong)
-  hipEvent_t found = nullptr;                 // the long runs listed on the long-run stream (k_find_long beside k_apply_runs)
+  DevBuf<uint64_t> d_eo_keys[2];
+  DevBuf<uint32_t> d_eo_vals[2];
+  size_t eo_cap_marks = 0;          // of the marks' group: keys, values, sort workspace, hit bytes, hseq, where, the two bitmaps
+  DevBuf<uint4> d_eo_tab;
+  DevBuf<unsigned long long> d_eo_xnode;   // [2 x X marks]
+  DevBuf<uint32_t> d_eo_cnt_b, d_eo_ux, d_eo_dirty, d_eo_list[2], d_eo_chg, d_eo_consulted, d_eo_lp;
+  DevBuf<unsigned long long> d_eo_bt;
+  DevBuf<EoCtl> d_eo_ctl;
+  DevBuf<uint32_t> d_eo_sort_ws;
+  DevBuf<uint32_t> d_eo_hseq, d_eo_where;   // per seed mark in emission order: voxel hash | index in M
+  DevBuf<uint4> d_eo_rinfo, d_eo_ckpt;      // per position: {u0, um, length, checkpoint step} | caster state there
+  DevBuf<uint8_t> d_eo_hitb;                // first iteration: per mark in emission order, the visit is a hit
+  DevBuf<unsigned long long> d_eo_bits_a, d_eo_bits_b;   // per mark of M: it counts under the current / next lengths
+  DevBuf<unsigned long long> d_eo_btp;      // ... exclusive prefix of the scan's block totals
+  Event eo_committed;               // the frame's marks have entered the shared table
+  Counters* d_counters = nullptr;   // a VIEW: inside ks_ctx::d_state
+  DevBuf<uint32_t> d_ray_list;      // rays to march (written by stage A, read by B)
+  PinnedBuf<HostSnap> h_snap;       // pinned + device-visible: written by k_publish at the end of B
+  Event a_done;                     // stage A complete
+  Event ready;                      // snapshot has landed
+  Event tail_done;                  // the tail has consumed this slot's buffers
+  Event fork, join;                 // tail: pairs sorted and long runs listed | long runs applied
+  Event join_x;                     // the runs of more than kXLongRun updates applied (stream_xlong)
+  Event found;                      // the long runs listed on the long-run stream (k_find_long beside k_apply_runs)
   bool tail_recorded = false;
   bool join_recorded = false;
   bool b_launched = false;    // stage B of the frame has been enqueued (with its batch)
@@ -179,13 +187,17 @@ struct FrameSlot {
 constexpr int kProfSets = 32;   // 2 x the largest lag (kMaxLag = 16): a set is reused 32 frames later, long after its frame's tail
 constexpr int kStageEvents = KS_STAGE_COUNT + 3;  // 0..3 stage A | 4,5 march begin/end | 6 tail begin, 7..10
 struct ProfSet {
-  hipEvent_t ev[kStageEvents]{};
-  hipEvent_t k0 = nullptr, k1 = nullptr;  // begin/end of the k_apply dispatch itself
+  Event ev[kStageEvents];
+  Event k0, k1;  // begin/end of the k_apply dispatch itself
   bool used = false, complete = false, stages = false, apply = false, applied = false;
   uint64_t n_pairs = 0, n_points = 0;
 };
 
+// MEMBER ORDER IS TEARDOWN ORDER, reversed: the stream owners come first, so `delete c` frees every buffer, pinned block,
+// event and graph before it destroys the streams whose work referred to them (ks_destroy has synchronised them all).
 struct ks_ctx {
+  Stream streams[kMarchStreams + 4];   // every stream of the context, in creation order; the named handles below are views
+  int n_streams = 0;
   ks_config cfg{};
   std::string err;
   hipStream_t stream = nullptr;        // stage A (and everything else)
@@ -205,21 +217,25 @@ struct ks_ctx {
   float voxel_size_inv = 0.f, log_match = 0.f, log_non_match = 0.f;
   int vps_shift = 1;  // log2(vps / 8)
 
-  TileTable table{};
-  Pool pool{};
-  uint64_t* d_start_set = nullptr;
-  uint64_t* d_observed_[kObsTables] = {};
+  TileTable table{};                   // views of table_ent, table_slot_keys and (n_tiles) d_state
+  Pool pool{};                         // views of pool_vox, pool_updated, pool_dirty
+  DevBuf<TileEntry> table_ent;
+  DevBuf<uint64_t> table_slot_keys;
+  DevBuf<uint4> pool_vox;
+  DevBuf<uint8_t> pool_updated, pool_dirty;
+  DevBuf<uint64_t> d_start_set;
+  DevBuf<uint64_t> d_observed_[kObsTables];
   int n_obs = 1;
   uint64_t start_offset = 0, observed_offset = 0;
   int64_t reset_counter = 0;
   uint32_t obs_tag = 0, obs_tag_lo = 1;  // frame tag of the observed set's entries (ks_k_march.h)
-  Counters* d_retry_counters = nullptr;  // scratch of the pair-buffer overflow retry
+  DevBuf<Counters> d_retry_counters;     // scratch of the pair-buffer overflow retry
   std::atomic<size_t> pairs_hint{0};     // largest pair count of a frame so far (written by the thread that runs the tails, read by the caller's)
   bool uses_early_out = false;           // fast integrator whose consecutive-collision limit can fire
   // the seed's launch shape for cap_points (seed_launch_shape; ensure_points): per phase its generations, its part of the
   // slots' item lists and the wavefronts launched per frame — on the host for stage B's grids, on the device for k_seed_list
   std::vector<SeedPhase> seed_phases;
-  SeedPhase* d_seed_phases = nullptr;
+  DevBuf<SeedPhase> d_seed_phases;
   size_t seed_cap_items = 0;             // KS_DEBUG=1 KS_SEED_CAP_ITEMS=<n>: no phase's launch covers more items (tests: the overflow guard)
   // Pipelined contexts enqueue the tail of frame i-lag on a helper thread while the calling thread enqueues
   // stages A and B of frame i (the host, not the GPU, bounds small frames: ~25 launches of ~8 us each per
@@ -236,52 +252,52 @@ struct ks_ctx {
   bool use_graphs = true;                // stage B replayed as a hipGraph (a capture failure: plain launches)
   bool test_overlap = true;              // k_test casts a long ray's next 64 voxels while the shared-set entries of the current 64 are in flight (KS_TEST_OVERLAP=0: one after the other, as measured until round 3)
   std::atomic<uint64_t> buffers_epoch{1};  // bumped whenever a buffer a captured graph points at is re-allocated
-  uint8_t* d_color_lut = nullptr;   // 16 MiB rgb -> label
-  uint32_t* d_label_lut = nullptr;  // 256 label -> rgba
+  DevBuf<uint8_t> d_color_lut;      // 16 MiB rgb -> label
+  DevBuf<uint32_t> d_label_lut;     // 256 label -> rgba
   uint32_t tiles_initialised = 0;
 
   // per-frame buffers
   size_t cap_points = 0;
-  float* d_xyz = nullptr;
-  uint8_t* d_rgba = nullptr;
-  uint8_t* d_labels = nullptr;
-  uint32_t* d_hash = nullptr;
-  uint32_t *d_skeys32 = nullptr, *d_skeys32b = nullptr;
-  float4* d_gpw = nullptr;
-  uint64_t* d_ray_keys = nullptr;
-  uint2* d_glc = nullptr;
+  DevBuf<float> d_xyz;
+  DevBuf<uint8_t> d_rgba;
+  DevBuf<uint8_t> d_labels;
+  DevBuf<uint32_t> d_hash;
+  DevBuf<uint32_t> d_skeys32, d_skeys32b;
+  DevBuf<float4> d_gpw;
+  DevBuf<uint64_t> d_ray_keys;
+  DevBuf<uint2> d_glc;
   // stage T's shared buffers exist twice (frame parity): the long runs of frame f may still be applied from
   // set f & 1 while frame f+1 sorts its pairs and lists its long runs into the other set (deferred join)
-  unsigned long long* d_long_list_[2] = {nullptr, nullptr};
-  uint32_t* d_blong = nullptr;
+  DevBuf<unsigned long long> d_long_list_[2];
+  DevBuf<uint32_t> d_blong;
   // merged, reference bundle order: the epochs of the rehash recurrence are launched for this many bundles (the counts of the
   // frames before, with a margin; ~0: as many as the frame has points) — k_bo_rest completes a frame that has more
   std::atomic<uint32_t> bo_hint{~0u};
   bool bo_hint_fixed = false;
-  uint64_t* d_key_overflow = nullptr;   // merged, compact grouping keys: the table of the end voxels outside the key window (k_points_merged)
+  DevBuf<uint64_t> d_key_overflow;      // merged, compact grouping keys: the table of the end voxels outside the key window (k_points_merged)
   uint32_t key_overflow_mask = 0;
   uint32_t key_bits = 0;                // bits per axis of the key window; 0: the 64-bit keys are sorted (FrameParams::key_bits)
-  uint64_t *d_pkeys = nullptr, *d_pkeys2 = nullptr;
-  uint32_t *d_pvals = nullptr, *d_pvals2 = nullptr;
-  uint32_t* d_order = nullptr;
-  uint32_t* d_inv_order = nullptr;
-  uint32_t *d_okeys = nullptr, *d_okeys2 = nullptr, *d_ovals = nullptr;
+  DevBuf<uint64_t> d_pkeys, d_pkeys2;
+  DevBuf<uint32_t> d_pvals, d_pvals2;
+  DevBuf<uint32_t> d_order;
+  DevBuf<uint32_t> d_inv_order;
+  DevBuf<uint32_t> d_okeys, d_okeys2, d_ovals;
   size_t cap_pairs = 0;
-  uint64_t* d_pairs2_[2] = {nullptr, nullptr};
-  hipEvent_t pending_join = nullptr;     // recorded on stream_long; the next k_apply / k_apply_long wait for it
+  DevBuf<uint64_t> d_pairs2_[2];
+  hipEvent_t pending_join = nullptr;     // (a view: some slot's join) recorded on stream_long; the next k_apply / k_apply_long wait for it
   ksrs::Workspace sort_ws, sort_ws_tail;
   // fast, early-out in the reference's serial order (ks_k_exact.h): marks (two sets for the sort), slot ranges,
   // the reference's table content, the scan of the visited lengths, the iteration's counters
   bool exact_early_out = false;
-  uint64_t* d_eo_keys[2] = {nullptr, nullptr};
-  uint32_t* d_eo_vals[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> d_eo_keys[2];
+  DevBuf<uint32_t> d_eo_vals[2];
   size_t cap_marks = 0;
-  uint2* d_eo_range = nullptr;
-  uint64_t* d_eo_plain = nullptr;
-  uint32_t* d_eo_lp = nullptr;
-  unsigned long long* d_eo_bt = nullptr;
-  EoState* d_eo_state = nullptr;
-  EoState* h_eo_state = nullptr;         // pinned
+  DevBuf<uint2> d_eo_range;
+  DevBuf<uint64_t> d_eo_plain;
+  DevBuf<uint32_t> d_eo_lp;
+  DevBuf<unsigned long long> d_eo_bt;
+  DevBuf<EoState> d_eo_state;
+  PinnedBuf<EoState> h_eo_state;
   uint64_t eo_iterations = 0, eo_frames = 0;  // statistics (ks_exact_early_out_stats)
   // ... event-driven (the default; KS_EXACT_HOST_LOOP=1: every frame through the host-driven loop above)
   bool eo_device = false;
@@ -290,9 +306,9 @@ struct ks_ctx {
                                          // at the count once per such chunk (launch_batch) and enqueues more while rays still change
   int eo_sweep_chunks = 16;              // ... at most this many chunks, then the host-driven loop takes the frame
   std::atomic<int> eo_want_bulk{0};      // ... as a frame whose finisher was handed too long a list asks for (applied by the caller's thread between frames)
-  uint32_t* d_eo_committed = nullptr;    // frames [0, *d_eo_committed) of the exact path have entered d_eo_plain
+  DevBuf<uint32_t> d_eo_committed;       // frames [0, *d_eo_committed) of the exact path have entered d_eo_plain
   uint32_t eo_frame_no = 0;              // frames launched through the exact path
-  hipEvent_t eo_last_commit = nullptr;   // commit event of the previous frame (nullptr: nothing to wait for)
+  hipEvent_t eo_last_commit = nullptr;   // (a view: some slot's eo_committed) commit event of the previous frame (nullptr: nothing to wait for)
   std::atomic<size_t> eo_want_marks{0}, eo_want_x{0};   // capacities a failed frame asked for (grown by the caller's thread between frames)
   size_t eo_cap_marks = 0, eo_cap_x = 0; // per-slot capacities in use
   std::atomic<uint64_t> eo_fallbacks{0}; // frames that fell back to the host-driven loop (counted by the thread that runs the tails)
@@ -301,39 +317,33 @@ struct ks_ctx {
   bool eo_device_off = false;            // ... three of them: the context stays with the host-driven loop (one frame at a time)
   // merged in the reference's bundle order (ks_k_bundle_order.h): scratch of the rank computation, one slab
   bool use_bundle_rank = false;
-  BoCtx bo{};
+  BoCtx bo{};                            // views into d_bo_slab
   BoSchedule bo_sched{};
-  uint8_t* d_bo_slab = nullptr;
+  DevBuf<uint8_t> d_bo_slab;
   int bo_epochs = 0;                     // epochs launched per frame (those a cloud of cap_points could reach)
   // ks_reduce: grow-only exchange scratch (send / receive keys and raw tile records, per-owner counts)
-  int32_t* d_rx_counts = nullptr;
-  size_t rx_world = 0;
-  uint64_t *d_tx_keys = nullptr, *d_rx_keys = nullptr;
-  uint32_t* d_tx_slots = nullptr;
-  uint8_t *d_tx_payload = nullptr, *d_rx_payload = nullptr;
+  DevBuf<int32_t> d_rx_counts;           // [(world + 3) x world]
+  DevBuf<uint64_t> d_tx_keys, d_rx_keys;
+  DevBuf<uint32_t> d_tx_slots;
+  DevBuf<uint8_t> d_tx_payload, d_rx_payload;
   size_t cap_tx = 0, cap_rx = 0;
   // scratch of the multi-GPU exchange entry points (slots / group offsets + order / distinct keys)
-  uint32_t* d_xchg_u32 = nullptr;
-  uint64_t* d_xchg_u64 = nullptr;
-  size_t cap_xchg = 0;
+  DevBuf<uint32_t> d_xchg_u32;           // [2 x d_xchg_u64.size() + 2]
+  DevBuf<uint64_t> d_xchg_u64;
   // Device words: Counters of slot k at 64 * k, the persistent tile count at 64 * kSlots.
-  uint8_t* d_state = nullptr;
+  DevBuf<uint8_t> d_state;
   FrameSlot slot[kSlots];
   int n_slots = 1;   // slots in use: 1 (unpipelined), 12 or 24 (ks_create)
   uint64_t frame_no = 0;
   ks_frame_stats owed{};  // statistics of frames completed but not yet handed to the caller (summed)
-  int32_t* d_block_idx = nullptr;
-  size_t cap_block_idx = 0;
-  uint8_t *d_tsdf_out = nullptr, *d_sem_out = nullptr;
-  uint8_t* d_vox_out = nullptr;     // staging of ks_download_updated_voxels
-  size_t cap_vox_out = 0;
-  size_t cap_out_blocks = 0;
+  DevBuf<int32_t> d_block_idx;
+  DevBuf<uint8_t> d_tsdf_out, d_sem_out;
+  DevBuf<uint8_t> d_vox_out;        // staging of ks_download_updated_voxels
+  size_t cap_out_blocks = 0;        // of the staging group: d_tsdf_out, d_sem_out, d_block_idx
 
-  uint32_t* d_depth_blocks = nullptr;
-  size_t cap_depth_blocks = 0;
-  uint8_t* d_img_depth = nullptr;
-  uint8_t* d_img_aux = nullptr;
-  size_t cap_img_depth = 0, cap_img_aux = 0;
+  DevBuf<uint32_t> d_depth_blocks;
+  DevBuf<uint8_t> d_img_depth;
+  DevBuf<uint8_t> d_img_aux;
 
   int profiling = 0;  // 0 off, 1 all stages + every k_apply, 2 every 4th k_apply only
   // the voxel update of the short runs: k_apply_runs (a lane per run, runs bucketed by length: ks_k_apply.h) from this many
@@ -343,56 +353,56 @@ struct ks_ctx {
   // runs in order on stream_xlong
   bool xl_parallel = true;
   unsigned long long xl_min_pairs = 1ull << 23;   // (below: the five launches of the path cost a 640x480 frame more than its handful of such runs through k_apply_xlong)
-  XlRun* d_xl_runs = nullptr;
-  XlHeader* d_xl_hdr = nullptr;
-  XlChunk* d_xl_chunks = nullptr;
-  uint32_t* d_xl_idx = nullptr;
+  DevBuf<XlRun> d_xl_runs;
+  DevBuf<XlHeader> d_xl_hdr;
+  DevBuf<XlChunk> d_xl_chunks;
+  DevBuf<uint32_t> d_xl_idx;
   // ks_integrate_round_exact (ks_k_shard.h).  A MARCHER context: frame_tail ends with the frame's updates as records grouped by
   // owner (sh_out[*]), nothing is applied; an OWNER context: scratch for the records of one frame of a round.
   bool shard_export = false;
   int shard_world = 1;
   uint64_t shard_frames_seen = 0;        // global frames this marcher has accounted for (its own, and empty ones for the other ranks')
-  uint64_t* d_sh_okey[2] = {nullptr, nullptr};
-  uint64_t* d_sh_gkey[2] = {nullptr, nullptr};
-  uint32_t* d_sh_seq[2] = {nullptr, nullptr};
-  float* d_sh_sdf[2] = {nullptr, nullptr};
-  float* d_sh_uw[2] = {nullptr, nullptr};
-  uint32_t* d_sh_counts = nullptr;       // [64] per owner + [64] the origin-voxel flag
+  DevBuf<uint64_t> d_sh_okey[2];
+  DevBuf<uint64_t> d_sh_gkey[2];
+  DevBuf<uint32_t> d_sh_seq[2];
+  DevBuf<float> d_sh_sdf[2];
+  DevBuf<float> d_sh_uw[2];
+  DevBuf<uint32_t> d_sh_counts;          // [64] per owner + [64] the origin-voxel flag
   size_t cap_sh = 0;
   uint32_t sh_counts[65] = {0};          // the last exported frame's
   uint64_t sh_exported = 0;              // its update count
-  uint64_t* d_sh_tk = nullptr;           // owner: tile keys / pair keys / record numbers of the segment being applied
-  uint64_t* d_sh_pairs[2] = {nullptr, nullptr};
-  uint32_t* d_sh_vals[2] = {nullptr, nullptr};
+  DevBuf<uint64_t> d_sh_tk;              // owner: tile keys / pair keys / record numbers of the segment being applied
+  DevBuf<uint64_t> d_sh_pairs[2];
+  DevBuf<uint32_t> d_sh_vals[2];
   size_t cap_sh_rx = 0;
   // ... of `merged` (ks_k_shard_merged.h).  Marcher: bundle number by position, the frame's bundle table, its mixed-label rows
-  uint32_t* d_shm_bno = nullptr;
-  float2* d_shm_btab = nullptr;
-  uint32_t* d_shm_mpos = nullptr;
-  uint32_t* d_shm_cnt = nullptr;         // [0] bundles, [1] mixed-label bundles
-  size_t cap_shm_n = 0;
-  float* d_shm_mixed = nullptr;
-  size_t cap_shm_mixed = 0;
+  DevBuf<uint32_t> d_shm_bno;
+  DevBuf<float2> d_shm_btab;
+  DevBuf<uint32_t> d_shm_mpos;
+  DevBuf<uint32_t> d_shm_cnt;            // [0] bundles, [1] mixed-label bundles
+  size_t cap_shm_n = 0;                  // of the four above
+  DevBuf<float> d_shm_mixed;             // [mixed-label bundles x kNumLabels]
   uint32_t shm_counts[2] = {0, 0};       // the last exported frame's
   // owner: the tables received from the peers (one after the other, by source rank), the staged operands, the long runs
-  float2* d_shm_rx_btab = nullptr;
-  size_t cap_shm_rx_btab = 0;
-  float* d_shm_rx_mixed = nullptr;
-  size_t cap_shm_rx_mixed = 0;
-  float4* d_shm_ops = nullptr;
-  uint32_t* d_shm_long = nullptr;        // [cap / (kLongRun + 1) + 1] heads of the long runs, then the count
-  size_t cap_shm_ops = 0;
+  DevBuf<float2> d_shm_rx_btab;
+  DevBuf<float> d_shm_rx_mixed;          // [rows x kNumLabels]
+  DevBuf<float4> d_shm_ops;
+  DevBuf<uint32_t> d_shm_long;           // [cap / (kLongRun + 1) + 1] heads of the long runs, then the count
+  size_t cap_shm_ops = 0;                // of the two above
   // the runs of 33 .. 1024 updates a lane per run, bucketed by length over the frame (k_apply_long_lanes); by parity, like the lists
   bool long_lanes = true;
   unsigned long long long_lanes_min_pairs = 1ull << 24;
-  unsigned long long* d_long_sorted_[2] = {nullptr, nullptr};
-  LongHdr* d_long_hdr_[2] = {nullptr, nullptr};
-  unsigned long long* d_xl_fb = nullptr;
+  DevBuf<unsigned long long> d_long_sorted_[2];
+  DevBuf<LongHdr> d_long_hdr_[2];
+  DevBuf<unsigned long long> d_xl_fb;
   uint32_t cap_xl_chunks = 1u << 17;   // 8 M updates in such runs per frame (more: the serial kernel takes the rest)
   // ks_mesh_update (ks_k_mesh.h).  The mesh lives in one of two arenas as per-block segments back to back; a call writes the
   // other arena (re-meshed blocks from the kernels, kept ones copied) and swaps.  The host keeps the directory and the
   // sorted block list (tiles only ever join a map, so the list is extended by the tiles that are new since the last call).
-  MeshArena mesh_arena[2] = {};
+  MeshArena mesh_arena[2] = {};            // views of the four owners below
+  DevBuf<float> mesh_xyz[2], mesh_nrm[2];
+  DevBuf<uint32_t> mesh_rgba[2];
+  DevBuf<uint8_t> mesh_label[2];
   size_t mesh_cap[2] = {0, 0};
   int mesh_cur = 0;
   bool mesh_valid = false;                 // false: the next call meshes everything, whatever only_stale says
@@ -401,8 +411,7 @@ struct ks_ctx {
   uint32_t mesh_tiles_seen = 0;            // tiles [0, seen) have entered mesh_blocks
   std::vector<ks_mesh_block> mesh_dir;     // one entry per element of mesh_blocks as of the last update (n_vertices may be 0)
   std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
-  uint8_t* d_mesh_buf[10] = {};            // grow-only scratch of the passes (mesh_scratch)
-  size_t cap_mesh_buf[10] = {};
+  DevBuf<uint8_t> d_mesh_buf[10];          // grow-only scratch of the passes (mesh_scratch)
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -417,6 +426,11 @@ struct ks_ctx {
     }                                                                                             \
   } while (0)
 
+int ks_hip_failed(ks_ctx* ctx, const char* what, hipError_t e) {
+  ctx->err = std::string(what) + ": " + hipGetErrorString(e);
+  return KS_ERR_HIP;
+}
+
 namespace {
 
 inline hipStream_t march_stream(ks_ctx* c, uint64_t frame_no) { return c->stream_march_[frame_no % (uint64_t)c->n_march]; }
@@ -424,13 +438,6 @@ inline uint64_t* observed_table(ks_ctx* c, uint64_t frame_no) { return c->d_obse
 int sync_march(ks_ctx* c) {
   for (int i = 0; i < c->n_march; ++i)
     if (c->stream_march_[i] != c->stream) HIPCHK(c, hipStreamSynchronize(c->stream_march_[i]));
-  return KS_OK;
-}
-
-template <typename T>
-int dev_alloc(ks_ctx* c, T** p, size_t n) {
-  if (*p) { (void)hipFree(*p); *p = nullptr; }
-  HIPCHK(c, hipMalloc((void**)p, std::max<size_t>(n, 1) * sizeof(T)));
   return KS_OK;
 }
 
@@ -491,9 +498,7 @@ int ensure_bundle_order(ks_ctx* c, size_t cap) {
   auto al = [](size_t words) { return (words * 4 + 255) & ~(size_t)255; };
   const size_t per_map = 11 * al(cap) + al(nbt) + al(heads);
   const size_t total = 2 * per_map + al(2) + al((sizeof(BoSchedule) + 3) / 4) + 2 * al(2 * cap) + al(nfbt) + al(cap);
-  if (c->d_bo_slab) (void)hipFree(c->d_bo_slab);
-  c->d_bo_slab = nullptr;
-  HIPCHK(c, hipMalloc((void**)&c->d_bo_slab, total));
+  if (int rc = c->d_bo_slab.alloc(c, total)) return rc;
   uint8_t* p = c->d_bo_slab;
   auto take = [&](size_t words) { uint32_t* r = (uint32_t*)p; p += al(words); return r; };
   for (int m = 0; m < 2; ++m) {
@@ -589,10 +594,11 @@ int ensure_points(ks_ctx* c, size_t n) {
   // the create-time size is exact; a cloud that outgrows it gets head-room (growing completes the frames in
   // flight and re-captures stage B)
   const size_t cap = std::max<size_t>(c->cap_points ? n + n / 8 : n, 1024);
+  c->cap_points = 0;   // (of the whole group below: a failure part-way leaves a context that allocates again, not one that trusts the old size)
   int rc;
-  if ((rc = dev_alloc(c, &c->d_xyz, cap * 3))) return rc;
-  if ((rc = dev_alloc(c, &c->d_rgba, cap * 4))) return rc;
-  if ((rc = dev_alloc(c, &c->d_labels, cap))) return rc;
+  if ((rc = c->d_xyz.alloc(c, cap * 3))) return rc;
+  if ((rc = c->d_rgba.alloc(c, cap * 4))) return rc;
+  if ((rc = c->d_labels.alloc(c, cap))) return rc;
   ++c->buffers_epoch;
   const size_t scan_cap = (c->cfg.method == KS_METHOD_MERGED ? 2 : 1) * cap;
   size_t seed_items = 0;
@@ -611,58 +617,58 @@ int ensure_points(ks_ctx* c, size_t n) {
       off += P.item_cap;
     }
     seed_items = off;
-    if ((rc = dev_alloc(c, &c->d_seed_phases, c->seed_phases.size()))) return rc;
+    if ((rc = c->d_seed_phases.alloc(c, c->seed_phases.size()))) return rc;
     HIPCHK(c, hipMemcpyAsync(c->d_seed_phases, c->seed_phases.data(), c->seed_phases.size() * sizeof(SeedPhase), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   for (int i = 0; i < (c->cfg.pipeline_frames ? c->n_slots : 1); ++i) {
     if (c->uses_early_out) {
       // (one generation of slack: a frame's last generation may be partial)
-      if ((rc = dev_alloc(c, &c->slot[i].d_seed_gen, cap + order_chains_cap(c->cfg.integration_order_mode, cap)))) return rc;
-      if ((rc = dev_alloc(c, &c->slot[i].d_seed_items, seed_items))) return rc;
-      if ((rc = dev_alloc(c, &c->slot[i].d_seed_n, c->seed_phases.size()))) return rc;
+      if ((rc = c->slot[i].d_seed_gen.alloc(c, cap + order_chains_cap(c->cfg.integration_order_mode, cap)))) return rc;
+      if ((rc = c->slot[i].d_seed_items.alloc(c, seed_items))) return rc;
+      if ((rc = c->slot[i].d_seed_n.alloc(c, c->seed_phases.size()))) return rc;
     }
-    if ((rc = dev_alloc(c, &c->slot[i].d_rays, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->slot[i].d_ray_list, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->slot[i].d_cnt, scan_cap))) return rc;
-    if ((rc = dev_alloc(c, &c->slot[i].d_lp, scan_cap))) return rc;
-    if ((rc = dev_alloc(c, &c->slot[i].d_bt, scan_cap / kScanBlock + 2))) return rc;
-    if (c->cfg.method == KS_METHOD_FAST && (rc = dev_alloc(c, &c->slot[i].d_live, cap))) return rc;
+    if ((rc = c->slot[i].d_rays.alloc(c, cap))) return rc;
+    if ((rc = c->slot[i].d_ray_list.alloc(c, cap))) return rc;
+    if ((rc = c->slot[i].d_cnt.alloc(c, scan_cap))) return rc;
+    if ((rc = c->slot[i].d_lp.alloc(c, scan_cap))) return rc;
+    if ((rc = c->slot[i].d_bt.alloc(c, scan_cap / kScanBlock + 2))) return rc;
+    if (c->cfg.method == KS_METHOD_FAST && (rc = c->slot[i].d_live.alloc(c, cap))) return rc;
     if (c->cfg.enable_anti_grazing && c->cfg.method == KS_METHOD_MERGED) {
-      if ((rc = dev_alloc(c, &c->slot[i].d_gkeys, cap))) return rc;
-      if ((rc = dev_alloc(c, &c->slot[i].d_rkeys, cap))) return rc;
+      if ((rc = c->slot[i].d_gkeys.alloc(c, cap))) return rc;
+      if ((rc = c->slot[i].d_rkeys.alloc(c, cap))) return rc;
     }
-    if (c->cfg.method == KS_METHOD_MERGED && (rc = dev_alloc(c, &c->slot[i].d_deltas, cap * kNumLabels))) return rc;
+    if (c->cfg.method == KS_METHOD_MERGED && (rc = c->slot[i].d_deltas.alloc(c, cap * kNumLabels))) return rc;
   }
-  if ((rc = dev_alloc(c, &c->d_hash, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_skeys32, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_skeys32b, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_pkeys, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_pkeys2, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_pvals, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_pvals2, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_order, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_inv_order, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_okeys, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_okeys2, cap))) return rc;
-  if ((rc = dev_alloc(c, &c->d_ovals, cap))) return rc;
+  if ((rc = c->d_hash.alloc(c, cap))) return rc;
+  if ((rc = c->d_skeys32.alloc(c, cap))) return rc;
+  if ((rc = c->d_skeys32b.alloc(c, cap))) return rc;
+  if ((rc = c->d_pkeys.alloc(c, cap))) return rc;
+  if ((rc = c->d_pkeys2.alloc(c, cap))) return rc;
+  if ((rc = c->d_pvals.alloc(c, cap))) return rc;
+  if ((rc = c->d_pvals2.alloc(c, cap))) return rc;
+  if ((rc = c->d_order.alloc(c, cap))) return rc;
+  if ((rc = c->d_inv_order.alloc(c, cap))) return rc;
+  if ((rc = c->d_okeys.alloc(c, cap))) return rc;
+  if ((rc = c->d_okeys2.alloc(c, cap))) return rc;
+  if ((rc = c->d_ovals.alloc(c, cap))) return rc;
   if (c->cfg.method == KS_METHOD_MERGED) {
-    if ((rc = dev_alloc(c, &c->d_gpw, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_glc, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_ray_keys, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_blong, cap / kLongRun + 64))) return rc;
+    if ((rc = c->d_gpw.alloc(c, cap))) return rc;
+    if ((rc = c->d_glc.alloc(c, cap))) return rc;
+    if ((rc = c->d_ray_keys.alloc(c, cap))) return rc;
+    if ((rc = c->d_blong.alloc(c, cap / kLongRun + 64))) return rc;
     if (c->key_bits) {
       size_t slots = 1024;
       while (slots < 2 * cap) slots <<= 1;
-      if ((rc = dev_alloc(c, &c->d_key_overflow, slots))) return rc;
+      if ((rc = c->d_key_overflow.alloc(c, slots))) return rc;
       HIPCHK(c, hipMemsetAsync(c->d_key_overflow, 0, slots * sizeof(uint64_t), c->stream));
       c->key_overflow_mask = (uint32_t)(slots - 1);
     }
   }
   if (c->use_bundle_rank && (rc = ensure_bundle_order(c, cap))) return rc;
   if (c->exact_early_out) {
-    if ((rc = dev_alloc(c, &c->d_eo_lp, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_eo_bt, cap / kScanBlock + 2))) return rc;
+    if ((rc = c->d_eo_lp.alloc(c, cap))) return rc;
+    if ((rc = c->d_eo_bt.alloc(c, cap / kScanBlock + 2))) return rc;
     if ((rc = ensure_exact_points(c, cap))) return rc;
   }
   c->cap_points = cap;
@@ -674,28 +680,26 @@ int ensure_points(ks_ctx* c, size_t n) {
 // grows the buffer and repeats the emission (frame_tail).  d_pairs2 / the long-run list are sized by
 // the actual count.
 int ensure_pairs_in(ks_ctx* c, FrameSlot& S, size_t bound) {
-  if (bound <= S.cap_pairs_in) return KS_OK;
-  const size_t cap = std::max<size_t>(bound, 1 << 20);
-  int rc;
-  if ((rc = dev_alloc(c, &S.d_pairs, cap))) return rc;
-  S.cap_pairs_in = cap;
+  if (bound <= S.d_pairs.size()) return KS_OK;
+  if (int rc = S.d_pairs.alloc(c, std::max<size_t>(bound, 1 << 20))) return rc;
   ++c->buffers_epoch;  // captured stage-B graphs point at the old buffer
   return KS_OK;
 }
 int ensure_pairs_out(ks_ctx* c, size_t n) {
   if (n <= c->cap_pairs) return KS_OK;
   const size_t cap = std::max<size_t>(n + n / 4, 1 << 20);
+  c->cap_pairs = 0;
   int rc;
   HIPCHK(c, hipStreamSynchronize(c->stream_long));  // long runs of the previous frame may still read them
   if (c->stream_xlong) HIPCHK(c, hipStreamSynchronize(c->stream_xlong));
   if (c->stream_tail) HIPCHK(c, hipStreamSynchronize(c->stream_tail));
   for (int b = 0; b < 2; ++b) {
-    if ((rc = dev_alloc(c, &c->d_pairs2_[b], cap))) return rc;
+    if ((rc = c->d_pairs2_[b].alloc(c, cap))) return rc;
     // heads of the long runs, then (from cap / kLongRunLanes + 64 on) the heads of the runs of more than kXLongRun updates
-    if ((rc = dev_alloc(c, &c->d_long_list_[b], cap / kLongRunLanes + 64 + cap / kXLongRun + 64))) return rc;
-    if (c->long_lanes && (rc = dev_alloc(c, &c->d_long_sorted_[b], cap / kLongRunLanes + 64))) return rc;
+    if ((rc = c->d_long_list_[b].alloc(c, cap / kLongRunLanes + 64 + cap / kXLongRun + 64))) return rc;
+    if (c->long_lanes && (rc = c->d_long_sorted_[b].alloc(c, cap / kLongRunLanes + 64))) return rc;
   }
-  if (c->d_xl_hdr && (rc = dev_alloc(c, &c->d_xl_fb, cap / kXLongRun + 64))) return rc;   // (the runs the integer-sum path leaves to k_apply_xlong)
+  if (c->d_xl_hdr && (rc = c->d_xl_fb.alloc(c, cap / kXLongRun + 64))) return rc;   // (the runs the integer-sum path leaves to k_apply_xlong)
   c->cap_pairs = cap;
   return KS_OK;
 }
@@ -806,9 +810,9 @@ SlotView slot_view(const FrameSlot& S, Counters* counters = nullptr) {
   v.bt = S.d_bt;
   v.ray_list = S.d_ray_list;
   v.pairs = S.d_pairs;
-  v.pairs_cap = (unsigned long long)S.cap_pairs_in;
+  v.pairs_cap = (unsigned long long)S.d_pairs.size();
   v.C = counters ? counters : S.d_counters;
-  v.host_snap = (uint32_t*)S.h_snap;
+  v.host_snap = (uint32_t*)S.h_snap.get();
   v.eo_stats = S.d_eo_ctl ? &S.d_eo_ctl->n_x : nullptr;
   v.seed_gen = S.d_seed_gen;
   v.seed_items = S.d_seed_items;
@@ -875,10 +879,11 @@ void enqueue_stage_b(ks_ctx* c, const BatchView& V, uint32_t nb, bool wide, hipS
 int ensure_marks(ks_ctx* c, size_t n) {
   if (n <= c->cap_marks) return KS_OK;
   const size_t cap = std::max<size_t>(n + n / 4, 1 << 20);
+  c->cap_marks = 0;
   int rc;
   for (int b = 0; b < 2; ++b) {
-    if ((rc = dev_alloc(c, &c->d_eo_keys[b], cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_eo_vals[b], cap))) return rc;
+    if ((rc = c->d_eo_keys[b].alloc(c, cap))) return rc;
+    if ((rc = c->d_eo_vals[b].alloc(c, cap))) return rc;
   }
   c->cap_marks = cap;
   return KS_OK;
@@ -959,29 +964,26 @@ int ensure_exact_slots(ks_ctx* c, size_t cap_marks, size_t cap_x) {
   for (int i = 0; i < n_slots; ++i) {
     FrameSlot& S = c->slot[i];
     if (!S.d_eo_ctl) {
-      if ((rc = dev_alloc(c, &S.d_eo_ctl, 1))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_tab, (size_t)1 << kSetBits))) return rc;
+      if ((rc = S.d_eo_ctl.alloc(c, 1))) return rc;
+      if ((rc = S.d_eo_tab.alloc(c, (size_t)1 << kSetBits))) return rc;
       HIPCHK(c, hipMemsetAsync(S.d_eo_tab, 0, sizeof(uint4) << kSetBits, c->stream));
-      HIPCHK(c, hipEventCreateWithFlags(&S.eo_committed, hipEventDisableTiming));
+      if ((rc = S.eo_committed.create(c, hipEventDisableTiming))) return rc;
     }
     if (S.eo_cap_marks < cap_marks) {
+      S.eo_cap_marks = 0;
       for (int b = 0; b < 2; ++b) {
-        if ((rc = dev_alloc(c, &S.d_eo_keys[b], cap_marks))) return rc;
-        if ((rc = dev_alloc(c, &S.d_eo_vals[b], cap_marks))) return rc;
+        if ((rc = S.d_eo_keys[b].alloc(c, cap_marks))) return rc;
+        if ((rc = S.d_eo_vals[b].alloc(c, cap_marks))) return rc;
       }
-      S.eo_sort_words = ksrs::ws_words_dev(cap_marks, 3);
-      if ((rc = dev_alloc(c, &S.d_eo_sort_ws, S.eo_sort_words))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_hitb, cap_marks))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_hseq, cap_marks))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_where, cap_marks))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_bits_a, cap_marks / 64 + 2))) return rc;
-      if ((rc = dev_alloc(c, &S.d_eo_bits_b, cap_marks / 64 + 2))) return rc;
+      if ((rc = S.d_eo_sort_ws.alloc(c, ksrs::ws_words_dev(cap_marks, 3)))) return rc;
+      if ((rc = S.d_eo_hitb.alloc(c, cap_marks))) return rc;
+      if ((rc = S.d_eo_hseq.alloc(c, cap_marks))) return rc;
+      if ((rc = S.d_eo_where.alloc(c, cap_marks))) return rc;
+      if ((rc = S.d_eo_bits_a.alloc(c, cap_marks / 64 + 2))) return rc;
+      if ((rc = S.d_eo_bits_b.alloc(c, cap_marks / 64 + 2))) return rc;
       S.eo_cap_marks = cap_marks;
     }
-    if (S.eo_cap_x < cap_x) {
-      if ((rc = dev_alloc(c, &S.d_eo_xnode, 2 * cap_x))) return rc;
-      S.eo_cap_x = cap_x;
-    }
+    if ((rc = S.d_eo_xnode.reserve(c, 2 * cap_x, 2 * cap_x))) return rc;
   }
   c->eo_cap_marks = cap_marks;
   c->eo_cap_x = cap_x;
@@ -994,12 +996,12 @@ int ensure_exact_points(ks_ctx* c, size_t cap) {   // the per-position arrays (c
   int rc;
   for (int i = 0; i < (c->cfg.pipeline_frames ? c->n_slots : 1); ++i) {
     FrameSlot& S = c->slot[i];
-    for (uint32_t** p : {&S.d_eo_cnt_b, &S.d_eo_ux, &S.d_eo_dirty, &S.d_eo_list[0], &S.d_eo_list[1], &S.d_eo_chg, &S.d_eo_consulted, &S.d_eo_lp})
-      if ((rc = dev_alloc(c, p, cap))) return rc;
-    if ((rc = dev_alloc(c, &S.d_eo_bt, cap / kScanBlock + 2))) return rc;
-    if ((rc = dev_alloc(c, &S.d_eo_btp, cap / kScanBlock + 2))) return rc;
-    if ((rc = dev_alloc(c, &S.d_eo_rinfo, cap))) return rc;
-    if ((rc = dev_alloc(c, &S.d_eo_ckpt, 3 * cap))) return rc;
+    for (DevBuf<uint32_t>* p : {&S.d_eo_cnt_b, &S.d_eo_ux, &S.d_eo_dirty, &S.d_eo_list[0], &S.d_eo_list[1], &S.d_eo_chg, &S.d_eo_consulted, &S.d_eo_lp})
+      if ((rc = p->alloc(c, cap))) return rc;
+    if ((rc = S.d_eo_bt.alloc(c, cap / kScanBlock + 2))) return rc;
+    if ((rc = S.d_eo_btp.alloc(c, cap / kScanBlock + 2))) return rc;
+    if ((rc = S.d_eo_rinfo.alloc(c, cap))) return rc;
+    if ((rc = S.d_eo_ckpt.alloc(c, 3 * cap))) return rc;
   }
   return KS_OK;
 }
@@ -1033,7 +1035,7 @@ EoView eo_view(ks_ctx* c, const FrameSlot& S) {
   E.ckpt = S.d_eo_ckpt;
   E.tab = S.d_eo_tab;
   E.xnode = S.d_eo_xnode;
-  E.cap_x = (uint32_t)S.eo_cap_x;
+  E.cap_x = (uint32_t)(S.d_eo_xnode.size() / 2);
   E.list[0] = S.d_eo_list[0];
   E.list[1] = S.d_eo_list[1];
   E.chg = S.d_eo_chg;
@@ -1082,7 +1084,7 @@ int enqueue_exact_rounds(ks_ctx* c, FrameSlot* const* slots, uint32_t nb, hipStr
     hipLaunchKernelGGL(k_eo2_full, dim3(gn, nb), dim3(256), 0, st, Bt);
     hipLaunchKernelGGL(k_eo2_scan, dim3(nb4k, nb), dim3(1024), 0, st, Bt);
     hipLaunchKernelGGL(k_eo2_emit<8>, dim3((uint32_t)((n + 31) / 32), nb), dim3(256), lds, st, Bt);
-    HIPCHK(c, ksrs::sort_dev_batch<uint64_t>(Rs, (int)nb, S0.eo_sort_words, S0.eo_cap_marks, 44, 64, st));
+    HIPCHK(c, ksrs::sort_dev_batch<uint64_t>(Rs, (int)nb, S0.d_eo_sort_ws.size(), S0.eo_cap_marks, 44, 64, st));
     hipLaunchKernelGGL(k_eo2_bits, dim3(gm, nb), dim3(256), 0, st, Bt, 0u);
     hipLaunchKernelGGL(k_eo2_where, dim3(gm, nb), dim3(256), 0, st, Bt);
     enqueue_sweeps(c, Bt, nb, c->eo_sweeps, st);
@@ -1092,7 +1094,7 @@ int enqueue_exact_rounds(ks_ctx* c, FrameSlot* const* slots, uint32_t nb, hipStr
     hipLaunchKernelGGL(k_eo2_emit<64>, dim3((uint32_t)((n + 255) / 256), nb), dim3(256), lds, st, Bt);
     // stable sort on the slot bits only: a slot's marks stay in (position, step) order; three passes: the result is in the
     // second buffer set (eo_view)
-    HIPCHK(c, ksrs::sort_dev_batch<uint64_t>(Rs, (int)nb, S0.eo_sort_words, S0.eo_cap_marks, 44, 64, st));
+    HIPCHK(c, ksrs::sort_dev_batch<uint64_t>(Rs, (int)nb, S0.d_eo_sort_ws.size(), S0.eo_cap_marks, 44, 64, st));
     // the first iteration, full and streaming: hit bits of the sorted seed marks (and the slots' ranges), stop rule per ray,
     // validity bitmaps
     hipLaunchKernelGGL(k_eo2_hits, dim3(gm, nb), dim3(256), 0, st, Bt);
@@ -1158,11 +1160,7 @@ int launch_batch(ks_ctx* c) {
     bool graphs = c->use_graphs && !S0.wide;   // (long rays: the host looks at the sweeps' progress between chunks of them)
     if (graphs && (G.key != key || !G.g1 || !G.g2 || !G.g3)) {
       std::lock_guard<std::mutex> cap(c->capture_mu);
-      for (hipGraphExec_t* g : {&G.g1, &G.g2, &G.g3}) {
-        if (*g) (void)hipGraphExecDestroy(*g);
-        *g = nullptr;
-      }
-      G.key = 0;
+      G.reset();
       int part_rc = KS_OK;
       auto capture = [&](hipGraphExec_t* out, int part) -> bool {
         hipGraph_t g = nullptr;
@@ -1186,10 +1184,7 @@ int launch_batch(ks_ctx* c) {
         G.key = key;
       } else {
         (void)hipGetLastError();
-        for (hipGraphExec_t* g : {&G.g1, &G.g2, &G.g3}) {
-          if (*g) (void)hipGraphExecDestroy(*g);
-          *g = nullptr;
-        }
+        G.reset();
         c->use_graphs = graphs = false;  // plain launches from now on
       }
     }
@@ -1235,9 +1230,7 @@ int launch_batch(ks_ctx* c) {
   } else if (c->use_graphs) {
     if (G.key != key || !G.g1) {
       std::lock_guard<std::mutex> cap(c->capture_mu);  // (rare: once per group of slots)
-      if (G.g1) (void)hipGraphExecDestroy(G.g1);
-      G.g1 = nullptr;
-      G.key = 0;
+      G.reset();
       hipGraph_t g = nullptr;
       bool ok = hipStreamBeginCapture(sm, hipStreamCaptureModeRelaxed) == hipSuccess;
       if (ok) {
@@ -1364,7 +1357,7 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
   if (F.sorted_order) {
     hipLaunchKernelGGL(k_sqnorm, dim3(nb), dim3(256), 0, st, (uint32_t)n, d_xyz, c->d_okeys, c->d_ovals);
     uint32_t *ok = nullptr, *ov = nullptr;
-    if ((rc = sort_pairs(c, c->d_okeys, c->d_okeys2, c->d_ovals, c->d_order, n, 32, &ok, &ov))) return rc;
+    if ((rc = sort_pairs(c, c->d_okeys.get(), c->d_okeys2.get(), c->d_ovals.get(), c->d_order.get(), n, 32, &ok, &ov))) return rc;
     order_ptr = ov;  // position -> index
     hipLaunchKernelGGL(k_invert, dim3(nb), dim3(256), 0, st, (uint32_t)n, order_ptr, c->d_inv_order);
     F.order = order_ptr;
@@ -1376,7 +1369,7 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     stage_mark(c, S.prof_set, 1);
     // stable sort by slot only: position order inside a slot is preserved
     uint32_t *sk = nullptr, *sv = nullptr;
-    if ((rc = sort_pairs(c, c->d_skeys32, c->d_skeys32b, c->d_pvals, c->d_pvals2, n, kSetBits + 1, &sk, &sv))) return rc;
+    if ((rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, kSetBits + 1, &sk, &sv))) return rc;
     stage_mark(c, S.prof_set, 2);
     hipLaunchKernelGGL(k_dedup, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set, S.d_ray_list,
                        S.d_rays, S.d_cnt, S.d_live, S.d_counters);
@@ -1413,10 +1406,10 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     if (c->key_bits) {
       // four passes over 32-bit grouping keys instead of eight over the 64-bit end-voxel keys; k_gather_sorted writes the
       // sorted 64-bit keys for everything downstream
-      if ((rc = sort_pairs(c, c->d_skeys32, c->d_skeys32b, c->d_pvals, c->d_pvals2, n, 32, &sk32, &sv))) return rc;
+      if ((rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 32, &sk32, &sv))) return rc;
       sk = c->d_pkeys;
     } else {
-      if ((rc = sort_pairs(c, c->d_pkeys, c->d_pkeys2, c->d_pvals, c->d_pvals2, n, 64, &sk, &sv))) return rc;
+      if ((rc = sort_pairs(c, c->d_pkeys.get(), c->d_pkeys2.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 64, &sk, &sv))) return rc;
     }
     stage_mark(c, S.prof_set, 2);
     hipLaunchKernelGGL(k_gather_sorted, dim3(nb), dim3(256), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
@@ -1482,24 +1475,26 @@ int shard_export_frame(ks_ctx* c, FrameSlot& S, unsigned long long n_pairs, hipS
   int rc;
   if (n_pairs > c->cap_sh) {
     const size_t cap = std::max<size_t>(n_pairs + n_pairs / 4, 1 << 20);
+    c->cap_sh = 0;
     for (int b = 0; b < 2; ++b) {
-      if ((rc = dev_alloc(c, &c->d_sh_okey[b], cap))) return rc;
-      if ((rc = dev_alloc(c, &c->d_sh_gkey[b], cap))) return rc;
-      if ((rc = dev_alloc(c, &c->d_sh_seq[b], cap))) return rc;
-      if ((rc = dev_alloc(c, &c->d_sh_sdf[b], cap))) return rc;
-      if ((rc = dev_alloc(c, &c->d_sh_uw[b], cap))) return rc;
+      if ((rc = c->d_sh_okey[b].alloc(c, cap))) return rc;
+      if ((rc = c->d_sh_gkey[b].alloc(c, cap))) return rc;
+      if ((rc = c->d_sh_seq[b].alloc(c, cap))) return rc;
+      if ((rc = c->d_sh_sdf[b].alloc(c, cap))) return rc;
+      if ((rc = c->d_sh_uw[b].alloc(c, cap))) return rc;
     }
     c->cap_sh = cap;
   }
-  if (!c->d_sh_counts && (rc = dev_alloc(c, &c->d_sh_counts, 128))) return rc;
+  if (!c->d_sh_counts && (rc = c->d_sh_counts.alloc(c, 128))) return rc;
   const bool merged = c->cfg.method == KS_METHOD_MERGED;
   c->shm_counts[0] = c->shm_counts[1] = 0;
   if (merged && (S.n > c->cap_shm_n || !c->d_shm_cnt)) {
     const size_t cap = std::max<size_t>(S.n, 1 << 16);
-    if ((rc = dev_alloc(c, &c->d_shm_bno, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_shm_btab, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_shm_mpos, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_shm_cnt, 2))) return rc;
+    c->cap_shm_n = 0;
+    if ((rc = c->d_shm_bno.alloc(c, cap))) return rc;
+    if ((rc = c->d_shm_btab.alloc(c, cap))) return rc;
+    if ((rc = c->d_shm_mpos.alloc(c, cap))) return rc;
+    if ((rc = c->d_shm_cnt.alloc(c, 2))) return rc;
     c->cap_shm_n = cap;
   }
   HIPCHK(c, hipMemsetAsync(c->d_sh_counts, 0, 128 * sizeof(uint32_t), st));
@@ -1534,11 +1529,7 @@ int shard_export_frame(ks_ctx* c, FrameSlot& S, unsigned long long n_pairs, hipS
   HIPCHK(c, hipStreamSynchronize(st));
   if (merged && c->shm_counts[1]) {
     const size_t nm = c->shm_counts[1];
-    if (nm > c->cap_shm_mixed) {
-      const size_t cap = std::max<size_t>(nm + nm / 2, 1024);
-      if ((rc = dev_alloc(c, &c->d_shm_mixed, cap * kNumLabels))) return rc;
-      c->cap_shm_mixed = cap;
-    }
+    if ((rc = c->d_shm_mixed.reserve(c, nm * kNumLabels, std::max<size_t>(nm + nm / 2, 1024) * kNumLabels))) return rc;
     hipLaunchKernelGGL(k_shard_mixed_rows, dim3((uint32_t)((nm * kNumLabels + 255) / 256)), dim3(256), 0, st, (uint32_t)nm,
                        (const uint32_t*)c->d_shm_mpos, (const float*)S.d_deltas, c->d_shm_mixed);
     HIPCHK(c, hipStreamSynchronize(st));
@@ -1713,7 +1704,7 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     const int par = (int)(S.frame_no & 1u);
     uint64_t* const d_pairs2 = c->d_pairs2_[par];
     unsigned long long* const d_long_list = c->d_long_list_[par];
-    if ((rc = sort_keys(c, S.d_pairs, d_pairs2, n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
+    if ((rc = sort_keys(c, S.d_pairs.get(), d_pairs2, n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
     stage_mark(c, set, 8);
     const uint32_t ab = (uint32_t)((n_pairs + 255) / 256);
     // k_apply_runs: 256 threads (tiles of 1024 pairs), not 512 (tiles of 2048).  Measured at 1280x720 / 2 cm beside the long-run
@@ -1758,15 +1749,15 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
 #define KS_LAUNCH_APPLY_M(MODE, MERGED)                                                                              \
   if (by_runs && time_apply)                                                                                         \
     hipExtLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, c->pset[set].k0,           \
-                          c->pset[set].k1, 0, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut, \
-                          kLongRun);                                                                                  \
+                          c->pset[set].k1, 0, F, n_pairs, sp, S.d_rays.get(), S.d_deltas.get(), c->table, c->pool,     \
+                          c->d_label_lut.get(), kLongRun);                                                             \
   else if (by_runs)                                                                                                  \
     hipLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, F, n_pairs, sp, S.d_rays,     \
                        S.d_deltas, c->table, c->pool, c->d_label_lut, kLongRun);                                      \
   else if (time_apply)                                                                                               \
     hipExtLaunchKernelGGL((k_apply<MODE, MERGED>), dim3(ab), dim3(256), 0, st, c->pset[set].k0, c->pset[set].k1, 0,   \
-                          F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut, d_long_list,       \
-                          S.d_counters);                                                                              \
+                          F, n_pairs, sp, S.d_rays.get(), S.d_deltas.get(), c->table, c->pool, c->d_label_lut.get(),  \
+                          d_long_list, S.d_counters);                                                                 \
   else                                                                                                               \
     hipLaunchKernelGGL((k_apply<MODE, MERGED>), dim3(ab), dim3(256), 0, st, F, n_pairs, sp, S.d_rays, S.d_deltas,     \
                        c->table, c->pool, c->d_label_lut, d_long_list, S.d_counters)
@@ -1875,13 +1866,11 @@ int flush_pending(ks_ctx* c) {
 }
 
 int ensure_exchange(ks_ctx* c, size_t n) {
-  if (n <= c->cap_xchg) return KS_OK;
+  if (n <= c->d_xchg_u64.size()) return KS_OK;
   const size_t cap = std::max<size_t>(n + n / 2, 1024);
-  int rc;
-  if ((rc = dev_alloc(c, &c->d_xchg_u32, 2 * cap + 2))) return rc;
-  if ((rc = dev_alloc(c, &c->d_xchg_u64, cap))) return rc;
-  c->cap_xchg = cap;
-  return KS_OK;
+  c->d_xchg_u64.release();   // (its size stands for both)
+  if (int rc = c->d_xchg_u32.alloc(c, 2 * cap + 2)) return rc;
+  return c->d_xchg_u64.alloc(c, cap);
 }
 
 // complete every outstanding frame and drain both streams
@@ -1939,56 +1928,41 @@ int grow_pool(ks_ctx* c) {
   const size_t new_max = std::min<size_t>(old_max * 2, (1u << 23) - 1);
   if (new_max <= old_max) return KS_OK;
   const uint32_t nt = c->tiles_initialised;
-  uint4* vox = nullptr;
-  uint8_t *upd = nullptr, *dirty = nullptr;
-  uint64_t* skeys = nullptr;
-  TileEntry* ent = nullptr;
+  DevBuf<uint4> vox;
+  DevBuf<uint8_t> upd, dirty;
+  DevBuf<uint64_t> skeys;
+  DevBuf<TileEntry> ent;
   uint32_t cap = 1024;
   while (cap < 2u * new_max) cap <<= 1;
-  if (hipMalloc((void**)&vox, new_max * kTileVoxels * 8 * sizeof(uint4)) != hipSuccess) {
+  if (vox.try_alloc(new_max * kTileVoxels * 8) != hipSuccess) {
     (void)hipGetLastError();
     return KS_OK;  // no memory for a bigger pool: carry on with the current one (exhaustion is reported when it happens)
   }
-  // (a failure part-way leaves the old pool in place and frees what was allocated for the new one)
-  auto fill = [&]() -> hipError_t {
-    hipError_t e;
-    if ((e = hipMalloc((void**)&upd, kFlagPlane + new_max)) != hipSuccess) return e;   // two planes: updated | mesh_stale
-    if ((e = hipMalloc((void**)&dirty, new_max)) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&skeys, new_max * sizeof(uint64_t))) != hipSuccess) return e;
-    if ((e = hipMalloc((void**)&ent, (size_t)cap * sizeof(TileEntry))) != hipSuccess) return e;
-    if ((e = hipMemset(upd, 0, new_max)) != hipSuccess) return e;
-    if ((e = hipMemset(dirty, 0, new_max)) != hipSuccess) return e;
-    if ((e = hipMemset(upd + kFlagPlane, 0, new_max)) != hipSuccess) return e;
-    if ((e = hipMemset(ent, 0xff, (size_t)cap * sizeof(TileEntry))) != hipSuccess) return e;
-    if (nt) {
-      if ((e = hipMemcpy(vox, c->pool.vox, (size_t)nt * kTileVoxels * 8 * sizeof(uint4), hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-      if ((e = hipMemcpy(upd, c->pool.updated, nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-      if ((e = hipMemcpy(dirty, c->pool.dirty, nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-      if ((e = hipMemcpy(upd + kFlagPlane, c->pool.mesh_stale(), nt, hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-      if ((e = hipMemcpy(skeys, c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToDevice)) != hipSuccess) return e;
-    }
-    return hipSuccess;
-  };
-  if (const hipError_t e = fill(); e != hipSuccess) {
-    for (void* q : {(void*)vox, (void*)upd, (void*)dirty, (void*)skeys, (void*)ent})
-      if (q) (void)hipFree(q);
-    c->err = std::string("grow_pool: ") + hipGetErrorString(e);
-    return KS_ERR_HIP;
+  // (a failure part-way leaves the old pool in place; the locals free what was allocated for the new one)
+  if ((rc = upd.alloc(c, kFlagPlane + new_max))) return rc;   // two planes: updated | mesh_stale
+  if ((rc = dirty.alloc(c, new_max))) return rc;
+  if ((rc = skeys.alloc(c, new_max))) return rc;
+  if ((rc = ent.alloc(c, cap))) return rc;
+  HIPCHK(c, hipMemset(upd, 0, new_max));
+  HIPCHK(c, hipMemset(dirty, 0, new_max));
+  HIPCHK(c, hipMemset(upd + kFlagPlane, 0, new_max));
+  HIPCHK(c, hipMemset(ent, 0xff, (size_t)cap * sizeof(TileEntry)));
+  if (nt) {
+    HIPCHK(c, hipMemcpy(vox, c->pool.vox, (size_t)nt * kTileVoxels * 8 * sizeof(uint4), hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(upd, c->pool.updated, nt, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(dirty, c->pool.dirty, nt, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(upd + kFlagPlane, c->pool.mesh_stale(), nt, hipMemcpyDeviceToDevice));
+    HIPCHK(c, hipMemcpy(skeys, c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToDevice));
   }
-  (void)hipFree(c->pool.vox);
-  (void)hipFree(c->pool.updated);
-  (void)hipFree(c->pool.dirty);
-  (void)hipFree(c->table.slot_keys);
-  (void)hipFree(c->table.ent);
-  c->pool.vox = vox;
-  c->pool.updated = upd;
-  c->pool.dirty = dirty;
-  c->table.slot_keys = skeys;
-  c->table.ent = ent;
+  c->pool.vox = c->pool_vox = std::move(vox);
+  c->pool.updated = c->pool_updated = std::move(upd);
+  c->pool.dirty = c->pool_dirty = std::move(dirty);
+  c->table.slot_keys = c->table_slot_keys = std::move(skeys);
+  c->table.ent = c->table_ent = std::move(ent);
   c->table.mask = cap - 1;
   c->table.max_tiles = (uint32_t)new_max;
   c->cfg.max_tiles = (uint32_t)new_max;
-  if (nt) hipLaunchKernelGGL(k_rehash_tiles, dim3((nt + 255) / 256), dim3(256), 0, c->stream, c->table, (const uint64_t*)skeys, nt);
+  if (nt) hipLaunchKernelGGL(k_rehash_tiles, dim3((nt + 255) / 256), dim3(256), 0, c->stream, c->table, (const uint64_t*)c->table.slot_keys, nt);
   HIPCHK(c, hipStreamSynchronize(c->stream));
   ++c->buffers_epoch;  // captured graphs hold the old table / pool
   return KS_OK;
@@ -2332,8 +2306,25 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
       return KS_ERR_HIP;                                                   \
     }                                                                      \
   } while (0)
+  // ... for a call that returns a KS_* code with its text in c->err (an owner's alloc / create)
+#define CRKS(expr)                \
+  do {                            \
+    if ((expr) != KS_OK) {        \
+      g_create_error = c->err;    \
+      ks_destroy(c);              \
+      return KS_ERR_HIP;          \
+    }                             \
+  } while (0)
+  // the next stream of the context (creation order matters: below)
+  auto new_stream = [c](hipStream_t* out) {
+    Stream& s = c->streams[c->n_streams];
+    if (int rc = s.create(c, hipStreamNonBlocking)) return rc;
+    ++c->n_streams;
+    *out = s;
+    return (int)KS_OK;
+  };
   CRCHK(hipSetDevice(cfg->device_id));
-  CRCHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
+  CRKS(new_stream(&c->stream));
   // Frames in flight share nothing in stage B when a frame's early-out marks can never be seen by the next frame
   // (every frame bumps the set offset).  Then either (pipeline_frames < 8) every frame's stage B is its own launch
   // sequence and up to four of them run side by side on four streams, or (pipeline_frames = 8) stage B of four
@@ -2364,9 +2355,9 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
       c->n_march = 1;
       c->stream_march_[0] = c->stream;
     } else {
-      for (int i = 0; i < c->n_march; ++i) CRCHK(hipStreamCreateWithFlags(&c->stream_march_[i], hipStreamNonBlocking));
+      for (int i = 0; i < c->n_march; ++i) CRKS(new_stream(&c->stream_march_[i]));
     }
-    CRCHK(hipStreamCreateWithFlags(&c->stream_tail, hipStreamNonBlocking));
+    CRKS(new_stream(&c->stream_tail));
   } else {
     c->stream_march_[0] = c->stream_tail = c->stream;
   }
@@ -2375,92 +2366,92 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     // share a hardware queue run one after the other: the heavy chains (stage B, stage T) must not share one.  With
     // the default of four hardware queues — one of which other streams of the process use — stage A and the long
     // runs (the two lightest: ~90 + ~65 us per 640x480 frame) are the pair that shares.
-    CRCHK(hipStreamCreateWithFlags(&c->stream_long, hipStreamNonBlocking));
+    CRKS(new_stream(&c->stream_long));
     // the runs of more than kXLongRun updates (the voxels next to the sensor) on a stream of their own, four waves per run
     // (k_apply_xlong).  Same arithmetic, same order: the map does not change.  KS_XLONG=0 (diagnostics): one list, k_apply_long.
     if (const char* ar = dbg_env("KS_APPLY_RUNS")) c->apply_runs_min_pairs = atoi(ar) ? 0ull : ~0ull;   // tests / A-B: always / never
     const char* xp = dbg_env("KS_XLONG");
     c->xlong = xp ? atoi(xp) != 0 : true;
-    if (c->xlong) CRCHK(hipStreamCreateWithFlags(&c->stream_xlong, hipStreamNonBlocking));
+    if (c->xlong) CRKS(new_stream(&c->stream_xlong));
     if (const char* ll = dbg_env("KS_LONG_LANES")) {   // A/B: 0 = k_apply_long (two wavefronts per run) for all of them, 2 = lanes for frames of any size (tests)
       c->long_lanes = atoi(ll) != 0;
       if (atoi(ll) == 2) c->long_lanes_min_pairs = 0ull;
     }
     if (c->long_lanes)
-      for (int b = 0; b < 2; ++b) CRCHK(hipMalloc((void**)&c->d_long_hdr_[b], sizeof(LongHdr)));
+      for (int b = 0; b < 2; ++b) CRKS(c->d_long_hdr_[b].alloc(c, 1));
     if (const char* xl = dbg_env("KS_XL_PARALLEL")) {   // A/B: 0 = every such run through k_apply_xlong, 2 = the integer-sum path for frames of any size (tests)
       c->xl_parallel = atoi(xl) != 0;
       if (atoi(xl) == 2) c->xl_min_pairs = 0ull;
     }   // A/B: 0 = every such run through k_apply_xlong
     if (c->stream_xlong && c->xl_parallel) {
-      CRCHK(hipMalloc((void**)&c->d_xl_runs, kXlMaxRuns * sizeof(XlRun)));
-      CRCHK(hipMalloc((void**)&c->d_xl_idx, kXlMaxRuns * sizeof(uint32_t)));
-      CRCHK(hipMalloc((void**)&c->d_xl_hdr, sizeof(XlHeader)));
+      CRKS(c->d_xl_runs.alloc(c, kXlMaxRuns));
+      CRKS(c->d_xl_idx.alloc(c, kXlMaxRuns));
+      CRKS(c->d_xl_hdr.alloc(c, 1));
       CRCHK(hipMemset(c->d_xl_hdr, 0, sizeof(XlHeader)));
-      CRCHK(hipMalloc((void**)&c->d_xl_chunks, (size_t)c->cap_xl_chunks * sizeof(XlChunk)));
+      CRKS(c->d_xl_chunks.alloc(c, c->cap_xl_chunks));
     }
   }
   for (auto& P : c->pset) {
-    for (auto& e : P.ev) CRCHK(hipEventCreate(&e));
-    CRCHK(hipEventCreate(&P.k0));
-    CRCHK(hipEventCreate(&P.k1));
+    for (auto& e : P.ev) CRKS(e.create(c, 0));   // (timing events)
+    CRKS(P.k0.create(c, 0));
+    CRKS(P.k1.create(c, 0));
   }
   uint32_t cap = 1024;
   while (cap < 2u * cfg->max_tiles) cap <<= 1;
   c->table.mask = cap - 1;
   c->table.max_tiles = cfg->max_tiles;
   const size_t mt = cfg->max_tiles;
-  CRCHK(hipMalloc((void**)&c->table.ent, cap * sizeof(TileEntry)));
-  CRCHK(hipMalloc((void**)&c->table.slot_keys, mt * sizeof(uint64_t)));
+  CRKS(c->table_ent.alloc(c, cap));
+  CRKS(c->table_slot_keys.alloc(c, mt));
+  c->table.ent = c->table_ent;
+  c->table.slot_keys = c->table_slot_keys;
   CRCHK(hipMemset(c->table.ent, 0xff, cap * sizeof(TileEntry)));  // key = empty, val = kSlotPending
-  CRCHK(hipMalloc((void**)&c->pool.vox, mt * kTileVoxels * 8 * sizeof(uint4)));
-  CRCHK(hipMalloc((void**)&c->pool.updated, kFlagPlane + mt));   // two planes: updated | mesh_stale (ks_types.h: Pool)
+  CRKS(c->pool_vox.alloc(c, mt * kTileVoxels * 8));
+  CRKS(c->pool_updated.alloc(c, kFlagPlane + mt));   // two planes: updated | mesh_stale (ks_types.h: Pool)
+  CRKS(c->pool_dirty.alloc(c, mt));
+  c->pool.vox = c->pool_vox;
+  c->pool.updated = c->pool_updated;
+  c->pool.dirty = c->pool_dirty;
   CRCHK(hipMemset(c->pool.updated, 0, mt));
-  CRCHK(hipMalloc((void**)&c->pool.dirty, mt));
   CRCHK(hipMemset(c->pool.dirty, 0, mt));
   CRCHK(hipMemset(c->pool.mesh_stale(), 0, mt));
-  CRCHK(hipMalloc((void**)&c->d_start_set, sizeof(uint64_t) << kSetBits));
+  CRKS(c->d_start_set.alloc(c, (size_t)1 << kSetBits));
   c->n_obs = (uses_early_out && frames_independent) ? std::min(kObsTables, std::max(c->n_march, c->batch * c->n_march)) : 1;
   for (int t = 0; t < c->n_obs; ++t) {
-    CRCHK(hipMalloc((void**)&c->d_observed_[t], 2 * (sizeof(uint64_t) << kSetBits)));   // {newest, older} per slot
+    CRKS(c->d_observed_[t].alloc(c, (size_t)2 << kSetBits));   // {newest, older} per slot
     CRCHK(hipMemset(c->d_observed_[t], 0, 2 * (sizeof(uint64_t) << kSetBits)));
     CRCHK(hipMemcpy(c->d_observed_[t], &kObsPoison, 8, hipMemcpyHostToDevice));
   }
   CRCHK(hipMemset(c->d_start_set, 0, sizeof(uint64_t) << kSetBits));
   const uint64_t poison = ~0ull;  // ApproxHashSet ctor: slot[offset_=0] = SIZE_MAX
   CRCHK(hipMemcpy(c->d_start_set, &poison, 8, hipMemcpyHostToDevice));
-  CRCHK(hipMalloc((void**)&c->d_retry_counters, sizeof(Counters)));
+  CRKS(c->d_retry_counters.alloc(c, 1));
   if (c->exact_early_out) {
-    CRCHK(hipMalloc((void**)&c->d_eo_committed, 64));
+    CRKS(c->d_eo_committed.alloc(c, 16));
     CRCHK(hipMemset(c->d_eo_committed, 0, 64));
-    CRCHK(hipMalloc((void**)&c->d_eo_range, sizeof(uint2) << kSetBits));
-    CRCHK(hipMalloc((void**)&c->d_eo_plain, sizeof(uint64_t) << kSetBits));
+    CRKS(c->d_eo_range.alloc(c, (size_t)1 << kSetBits));
+    CRKS(c->d_eo_plain.alloc(c, (size_t)1 << kSetBits));
     CRCHK(hipMemset(c->d_eo_plain, 0, sizeof(uint64_t) << kSetBits));
     CRCHK(hipMemcpy(c->d_eo_plain, &poison, 8, hipMemcpyHostToDevice));  // ApproxHashSet ctor: slot[0] = SIZE_MAX
-    CRCHK(hipMalloc((void**)&c->d_eo_state, sizeof(EoState)));
-    CRCHK(hipHostMalloc((void**)&c->h_eo_state, sizeof(EoState)));
+    CRKS(c->d_eo_state.alloc(c, 1));
+    CRKS(c->h_eo_state.alloc(c, 1));
   }
-  CRCHK(hipMalloc((void**)&c->d_label_lut, 256 * sizeof(uint32_t)));
+  CRKS(c->d_label_lut.alloc(c, 256));
   CRCHK(hipMemcpy(c->d_label_lut, cfg->label_rgba, 1024, hipMemcpyHostToDevice));
   static_assert(sizeof(Counters) == 32, "snapshot layout");
-  CRCHK(hipMalloc((void**)&c->d_state, 64 * (kSlots + 1)));
+  CRKS(c->d_state.alloc(c, 64 * (kSlots + 1)));
   CRCHK(hipMemset(c->d_state, 0, 64 * (kSlots + 1)));
   c->table.n_tiles = (uint32_t*)(c->d_state + 64 * kSlots);
   for (int i = 0; i < kSlots; ++i) {
     FrameSlot& S = c->slot[i];
     S.index = i;
     S.d_counters = (Counters*)(c->d_state + 64 * i);
-    CRCHK(hipHostMalloc((void**)&S.h_snap, sizeof(HostSnap)));
-    CRCHK(hipMalloc((void**)&S.d_F, sizeof(FrameParams)));
+    CRKS(S.h_snap.alloc(c, 1));
+    CRKS(S.d_F.alloc(c, 1));
     std::memset(S.h_snap, 0, sizeof(HostSnap));
-    CRCHK(hipEventCreateWithFlags(&S.a_done, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.ready, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.tail_done, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.fork, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.join, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.join_x, hipEventDisableTiming));
-    CRCHK(hipEventCreateWithFlags(&S.found, hipEventDisableTiming));
+    for (Event* e : {&S.a_done, &S.ready, &S.tail_done, &S.fork, &S.join, &S.join_x, &S.found}) CRKS(e->create(c, hipEventDisableTiming));
   }
+#undef CRKS
 #undef CRCHK
   // pair buffers start at 4 updates per point of the largest cloud (a frame that needs more grows its buffer and
   // repeats the emission once)
@@ -2501,64 +2492,7 @@ void ks_destroy(ks_ctx* c) {
     c->tail_cv.notify_all();
     c->tail_thread.join();
   }
-  if (c->stream_tail && c->stream_tail != c->stream) (void)hipStreamSynchronize(c->stream_tail);
-  for (auto sm : c->stream_march_)
-    if (sm && sm != c->stream) (void)hipStreamSynchronize(sm);
-  if (c->stream_long) (void)hipStreamSynchronize(c->stream_long);
-  if (c->stream) (void)hipStreamSynchronize(c->stream);
-  void* ptrs[] = {c->table.ent, c->table.slot_keys, c->pool.vox, c->pool.updated, c->pool.dirty, c->d_start_set, c->d_observed_[0], c->d_observed_[1], c->d_observed_[2], c->d_observed_[3], c->d_observed_[4], c->d_observed_[5], c->d_observed_[6], c->d_observed_[7], c->d_observed_[8], c->d_observed_[9], c->d_observed_[10], c->d_observed_[11], c->d_observed_[12], c->d_observed_[13], c->d_observed_[14], c->d_observed_[15], c->d_color_lut,
-                  c->d_label_lut, c->d_xyz, c->d_rgba, c->d_labels, c->d_hash, c->d_skeys32, c->d_skeys32b, c->d_gpw, c->d_glc, c->d_ray_keys, c->d_long_list_[0], c->d_long_list_[1], c->d_blong, c->d_key_overflow, c->d_pkeys,
-                  c->d_pkeys2, c->d_pvals, c->d_pvals2, c->d_order, c->d_inv_order, c->d_okeys, c->d_okeys2, c->d_ovals,
-                  c->d_pairs2_[0], c->d_pairs2_[1], c->d_state, c->d_xchg_u32, c->d_xchg_u64, c->d_retry_counters,
-                  c->d_block_idx, c->d_tsdf_out, c->d_sem_out, c->d_vox_out, c->d_depth_blocks, c->d_img_depth, c->d_img_aux, c->d_bo_slab,
-                  c->d_eo_keys[0], c->d_eo_keys[1], c->d_eo_vals[0], c->d_eo_vals[1], c->d_eo_range, c->d_eo_plain, c->d_eo_lp, c->d_eo_bt,
-                  c->d_eo_state, c->d_xl_runs, c->d_xl_hdr, c->d_xl_chunks, c->d_xl_idx, c->d_xl_fb, c->d_long_sorted_[0], c->d_long_sorted_[1], c->d_long_hdr_[0], c->d_long_hdr_[1], c->d_sh_okey[0], c->d_sh_okey[1], c->d_sh_gkey[0], c->d_sh_gkey[1], c->d_sh_seq[0], c->d_sh_seq[1], c->d_sh_sdf[0], c->d_sh_sdf[1], c->d_sh_uw[0], c->d_sh_uw[1], c->d_sh_counts, c->d_sh_tk, c->d_sh_pairs[0], c->d_sh_pairs[1], c->d_sh_vals[0], c->d_sh_vals[1], c->d_shm_bno, c->d_shm_btab, c->d_shm_mpos, c->d_shm_cnt, c->d_shm_mixed, c->d_shm_rx_btab, c->d_shm_rx_mixed, c->d_shm_ops, c->d_shm_long, c->d_rx_counts, c->d_tx_keys, c->d_rx_keys, c->d_tx_slots, c->d_tx_payload, c->d_rx_payload};
-  for (void* p : ptrs)
-    if (p) (void)hipFree(p);
-  for (void* p : c->d_mesh_buf)
-    if (p) (void)hipFree(p);
-  for (auto& A : c->mesh_arena)
-    for (void* p : {(void*)A.xyz, (void*)A.nrm, (void*)A.rgba, (void*)A.label})
-      if (p) (void)hipFree(p);
-  for (auto& S : c->slot) {
-    for (void* p : {(void*)S.d_rays, (void*)S.d_deltas, (void*)S.d_ray_list, (void*)S.d_pairs, (void*)S.d_cnt, (void*)S.d_lp,
-                    (void*)S.d_bt, (void*)S.d_live, (void*)S.d_seed_gen, (void*)S.d_seed_items, (void*)S.d_seed_n, (void*)S.d_F, (void*)S.d_gkeys, (void*)S.d_rkeys,
-                    (void*)S.d_eo_keys[0], (void*)S.d_eo_keys[1], (void*)S.d_eo_vals[0], (void*)S.d_eo_vals[1], (void*)S.d_eo_tab, (void*)S.d_eo_xnode,
-                    (void*)S.d_eo_cnt_b, (void*)S.d_eo_ux, (void*)S.d_eo_dirty, (void*)S.d_eo_list[0], (void*)S.d_eo_list[1], (void*)S.d_eo_chg,
-                    (void*)S.d_eo_consulted, (void*)S.d_eo_lp, (void*)S.d_eo_bt, (void*)S.d_eo_ctl, (void*)S.d_eo_sort_ws, (void*)S.d_eo_hitb, (void*)S.d_eo_bits_a, (void*)S.d_eo_bits_b, (void*)S.d_eo_btp, (void*)S.d_eo_hseq, (void*)S.d_eo_where, (void*)S.d_eo_rinfo, (void*)S.d_eo_ckpt})
-      if (p) (void)hipFree(p);
-    if (S.eo_committed) (void)hipEventDestroy(S.eo_committed);
-  }
-  if (c->d_eo_committed) (void)hipFree(c->d_eo_committed);
-  if (c->d_seed_phases) (void)hipFree(c->d_seed_phases);
-  if (c->h_eo_state) (void)hipHostFree(c->h_eo_state);
-  ksrs::release(c->sort_ws);
-  ksrs::release(c->sort_ws_tail);
-  for (auto& S : c->slot) {
-    for (auto& G : S.b_graphs)
-      for (hipGraphExec_t g : {G.g1, G.g2, G.g3})
-        if (g) (void)hipGraphExecDestroy(g);
-    if (S.h_snap) (void)hipHostFree(S.h_snap);
-    if (S.ready) (void)hipEventDestroy(S.ready);
-    if (S.tail_done) (void)hipEventDestroy(S.tail_done);
-    if (S.fork) (void)hipEventDestroy(S.fork);
-    if (S.join) (void)hipEventDestroy(S.join);
-    if (S.join_x) (void)hipEventDestroy(S.join_x);
-    if (S.found) (void)hipEventDestroy(S.found);
-    if (S.a_done) (void)hipEventDestroy(S.a_done);
-  }
-  for (auto& P : c->pset) {
-    for (auto& e : P.ev)
-      if (e) (void)hipEventDestroy(e);
-    if (P.k0) (void)hipEventDestroy(P.k0);
-    if (P.k1) (void)hipEventDestroy(P.k1);
-  }
-  if (c->stream_tail && c->stream_tail != c->stream) (void)hipStreamDestroy(c->stream_tail);
-  for (auto sm : c->stream_march_)
-    if (sm && sm != c->stream) (void)hipStreamDestroy(sm);
-  if (c->stream_long) (void)hipStreamDestroy(c->stream_long);
-  if (c->stream_xlong) (void)hipStreamDestroy(c->stream_xlong);
-  if (c->stream) (void)hipStreamDestroy(c->stream);
+  for (int i = 0; i < c->n_streams; ++i) (void)hipStreamSynchronize(c->streams[i]);   // every stream, before what its work refers to goes
   delete c;
 }
 
@@ -2576,7 +2510,7 @@ int ks_set_color_to_label(ks_ctx* c, const uint8_t* rgba_keys, const uint8_t* la
     lut[rgb] = labels[i];
   }
   if (int rc = quiesce(c)) return rc;  // frames in flight still read the old table
-  if (!c->d_color_lut) HIPCHK(c, hipMalloc((void**)&c->d_color_lut, 1u << 24));
+  if (int rc = c->d_color_lut.reserve(c, 1u << 24, 1u << 24)) return rc;
   HIPCHK(c, hipMemcpy(c->d_color_lut, lut.data(), 1u << 24, hipMemcpyHostToDevice));
   return KS_OK;
 }
@@ -2617,10 +2551,7 @@ static int integrate_depth_impl(ks_ctx* c, const float T[7], DepthParams D, int 
   if (n_px > c->cap_points && (rc = quiesce(c))) return rc;  // growing frees buffers a pending tail still needs
   if ((rc = ensure_points(c, n_px))) return rc;
   const uint32_t nb = (uint32_t)((n_px + 1023) / 1024);
-  if (nb + 1 > c->cap_depth_blocks) {
-    if ((rc = dev_alloc(c, &c->d_depth_blocks, (size_t)nb + 1))) return rc;
-    c->cap_depth_blocks = nb + 1;
-  }
+  if ((rc = c->d_depth_blocks.reserve(c, (size_t)nb + 1, (size_t)nb + 1))) return rc;
   hipStream_t st = c->stream;
   hipLaunchKernelGGL(k_depth_count, dim3(nb), dim3(1024), 0, st, D, (uint32_t)n_px, c->d_depth_blocks);
   hipLaunchKernelGGL(k_depth_scan, dim3(1), dim3(1024), 0, st, c->d_depth_blocks, nb);
@@ -2647,16 +2578,8 @@ int ks_integrate_depth(ks_ctx* c, const float T[7], const void* depth, int depth
   if (!c || !T || !depth || !K || width <= 0 || height <= 0 || (depth_fmt != 0 && depth_fmt != 1)) return KS_ERR_INVALID_ARG;
   const size_t n_px = (size_t)width * height;
   const size_t dbytes = n_px * (depth_fmt == 0 ? 4 : 2);
-  if (dbytes > c->cap_img_depth) {
-    int rc = dev_alloc(c, &c->d_img_depth, dbytes);
-    if (rc) return rc;
-    c->cap_img_depth = dbytes;
-  }
-  if (n_px * 4 > c->cap_img_aux) {
-    int rc = dev_alloc(c, &c->d_img_aux, n_px * 4);
-    if (rc) return rc;
-    c->cap_img_aux = n_px * 4;
-  }
+  if (int rc = c->d_img_depth.reserve(c, dbytes, dbytes)) return rc;
+  if (int rc = c->d_img_aux.reserve(c, n_px * 4, n_px * 4)) return rc;
   HIPCHK(c, hipMemcpyAsync(c->d_img_depth, depth, dbytes, hipMemcpyHostToDevice, c->stream));
   DepthParams D{};
   D.depth = c->d_img_depth;
@@ -2747,10 +2670,11 @@ int ks_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, void* tsdf_out, 
   const size_t chunk = std::max<size_t>(1, (size_t(256) << 20) / (nv * 92));
   if (c->cap_out_blocks < std::min(chunk, n)) {
     const size_t cb = std::min(chunk, std::max<size_t>(n, 16));
+    c->cap_out_blocks = 0;
     int rc;
-    if ((rc = dev_alloc(c, &c->d_tsdf_out, cb * nv * 12))) return rc;
-    if ((rc = dev_alloc(c, &c->d_sem_out, cb * nv * 92))) return rc;
-    if ((rc = dev_alloc(c, &c->d_block_idx, cb * 3))) return rc;
+    if ((rc = c->d_tsdf_out.alloc(c, cb * nv * 12))) return rc;
+    if ((rc = c->d_sem_out.alloc(c, cb * nv * 92))) return rc;
+    if ((rc = c->d_block_idx.alloc(c, cb * 3))) return rc;
     c->cap_out_blocks = cb;
   }
   for (size_t off = 0; off < n; off += c->cap_out_blocks) {
@@ -2788,19 +2712,19 @@ int ks_upload_blocks(ks_ctx* c, const int32_t* idx, size_t n, const void* tsdf_i
       for (int y = 0; y < tpb; ++y)
         for (int x = 0; x < tpb; ++x) keys.push_back(pack_tile(bx * tpb + x, by * tpb + y, bz * tpb + z));
   }
-  uint64_t* d_keys = nullptr;
-  HIPCHK(c, hipMalloc((void**)&d_keys, keys.size() * sizeof(uint64_t)));
+  DevBuf<uint64_t> d_keys;
+  int rc;
+  if ((rc = d_keys.alloc(c, keys.size()))) return rc;
   HIPCHK(c, hipMemcpyAsync(d_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
-  int rc = insert_tiles(c, d_keys, keys.size());
-  (void)hipFree(d_keys);
-  if (rc) return rc;
+  if ((rc = insert_tiles(c, d_keys, keys.size()))) return rc;   // (synchronises the stream: d_keys may go)
   // staging buffers shared with ks_download_blocks
   const size_t chunk = std::max<size_t>(1, (size_t(256) << 20) / (nv * 92));
   if (c->cap_out_blocks < std::min(chunk, n)) {
     const size_t cb = std::min(chunk, std::max<size_t>(n, 16));
-    if ((rc = dev_alloc(c, &c->d_tsdf_out, cb * nv * 12))) return rc;
-    if ((rc = dev_alloc(c, &c->d_sem_out, cb * nv * 92))) return rc;
-    if ((rc = dev_alloc(c, &c->d_block_idx, cb * 3))) return rc;
+    c->cap_out_blocks = 0;
+    if ((rc = c->d_tsdf_out.alloc(c, cb * nv * 12))) return rc;
+    if ((rc = c->d_sem_out.alloc(c, cb * nv * 92))) return rc;
+    if ((rc = c->d_block_idx.alloc(c, cb * 3))) return rc;
     c->cap_out_blocks = cb;
   }
   for (size_t off = 0; off < n; off += c->cap_out_blocks) {
@@ -2821,21 +2745,18 @@ int ks_upload_blocks(ks_ctx* c, const int32_t* idx, size_t n, const void* tsdf_i
 
 // ---- semantic mesh (ks_k_mesh.h) -------------------------------------------------------------------------
 static int mesh_scratch(ks_ctx* c, int i, size_t bytes) {
-  if (bytes <= c->cap_mesh_buf[i]) return KS_OK;
-  const size_t cap = std::max<size_t>(bytes + bytes / 2, 256);
-  if (int rc = dev_alloc(c, &c->d_mesh_buf[i], cap)) return rc;
-  c->cap_mesh_buf[i] = cap;
-  return KS_OK;
+  return c->d_mesh_buf[i].reserve(c, bytes, std::max<size_t>(bytes + bytes / 2, 256));
 }
 static int mesh_arena_reserve(ks_ctx* c, int a, size_t n_vertices) {
   if (n_vertices <= c->mesh_cap[a]) return KS_OK;
   const size_t cap = std::max<size_t>(n_vertices + n_vertices / 2, 4096);
-  MeshArena& A = c->mesh_arena[a];
+  c->mesh_cap[a] = 0;
   int rc;
-  if ((rc = dev_alloc(c, &A.xyz, 3 * cap))) return rc;
-  if ((rc = dev_alloc(c, &A.nrm, 3 * cap))) return rc;
-  if ((rc = dev_alloc(c, &A.rgba, cap))) return rc;
-  if ((rc = dev_alloc(c, &A.label, cap))) return rc;
+  if ((rc = c->mesh_xyz[a].alloc(c, 3 * cap))) return rc;
+  if ((rc = c->mesh_nrm[a].alloc(c, 3 * cap))) return rc;
+  if ((rc = c->mesh_rgba[a].alloc(c, cap))) return rc;
+  if ((rc = c->mesh_label[a].alloc(c, cap))) return rc;
+  c->mesh_arena[a] = MeshArena{c->mesh_xyz[a], c->mesh_nrm[a], c->mesh_rgba[a], c->mesh_label[a]};
   c->mesh_cap[a] = cap;
   return KS_OK;
 }
@@ -2964,16 +2885,16 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
         (rc = mesh_scratch(c, 7, nb * 4)) || (rc = mesh_scratch(c, 8, nb * 12)) || (rc = mesh_scratch(c, 9, 8)))
       return rc;
     MeshWork W{};
-    W.rblocks = (const int32_t*)c->d_mesh_buf[0];
+    W.rblocks = (const int32_t*)c->d_mesh_buf[0].get();
     W.cube_cnt = c->d_mesh_buf[1];
-    W.cube_off = (uint32_t*)c->d_mesh_buf[2];
-    W.block_tri = (uint32_t*)c->d_mesh_buf[3];
-    W.rb_first = (uint32_t*)c->d_mesh_buf[4];
-    W.degenerate = (unsigned long long*)c->d_mesh_buf[9];
+    W.cube_off = (uint32_t*)c->d_mesh_buf[2].get();
+    W.block_tri = (uint32_t*)c->d_mesh_buf[3].get();
+    W.rb_first = (uint32_t*)c->d_mesh_buf[4].get();
+    W.degenerate = (unsigned long long*)c->d_mesh_buf[9].get();
     W.voxel_size = c->cfg.voxel_size;
     W.min_weight = m->min_weight;
     W.vps_shift = sh;
-    uint32_t* d_dir_out = (uint32_t*)c->d_mesh_buf[6];
+    uint32_t* d_dir_out = (uint32_t*)c->d_mesh_buf[6].get();
     HIPCHK(c, hipMemsetAsync(W.degenerate, 0, 8, st));
     HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[5], dir_in.data(), nb * 8, hipMemcpyHostToDevice, st));
     if (nr) {
@@ -2982,7 +2903,7 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
       hipLaunchKernelGGL(k_mesh_tiles<false>, dim3((uint32_t)(nr * tiles_per_block)), dim3(512), 0, st, c->table, c->pool, W, MeshArena{});
       hipLaunchKernelGGL(k_mesh_scan, dim3((uint32_t)nr), dim3(1024), 0, st, W);
     }
-    hipLaunchKernelGGL(k_mesh_dir, dim3(1), dim3(1024), 0, st, W, (const uint2*)c->d_mesh_buf[5], (uint32_t)nb, d_dir_out, (uint32_t*)c->d_mesh_buf[7]);
+    hipLaunchKernelGGL(k_mesh_dir, dim3(1), dim3(1024), 0, st, W, (const uint2*)c->d_mesh_buf[5].get(), (uint32_t)nb, d_dir_out, (uint32_t*)c->d_mesh_buf[7].get());
     std::vector<uint32_t> first(nb + 1);
     HIPCHK(c, hipMemcpyAsync(first.data(), d_dir_out, (nb + 1) * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipMemcpyAsync(&degenerate, W.degenerate, 8, hipMemcpyDeviceToHost, st));
@@ -3002,7 +2923,7 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
     if (nr && total) hipLaunchKernelGGL(k_mesh_tiles<true>, dim3((uint32_t)(nr * tiles_per_block)), dim3(512), 0, st, c->table, c->pool, W, c->mesh_arena[to]);
     if (!moves.empty()) {
       HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[8], moves.data(), moves.size() * 4, hipMemcpyHostToDevice, st));
-      hipLaunchKernelGGL(k_mesh_copy, dim3((uint32_t)(moves.size() / 3)), dim3(256), 0, st, c->mesh_arena[from], c->mesh_arena[to], (const uint32_t*)c->d_mesh_buf[8]);
+      hipLaunchKernelGGL(k_mesh_copy, dim3((uint32_t)(moves.size() / 3)), dim3(256), 0, st, c->mesh_arena[from], c->mesh_arena[to], (const uint32_t*)c->d_mesh_buf[8].get());
     }
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
@@ -3128,12 +3049,9 @@ static int updated_voxels_impl(ks_ctx* c, void* out, size_t cap, size_t* n, bool
   const size_t bytes = (size_t)h_cnt[1] * kVoxRecBytes;
   const size_t run_bytes = (size_t)n_list * sizeof(ks_voxel_run);
   const size_t need = (rec_direct ? 0 : bytes + bytes / 4) + (run_direct ? 0 : 2 * run_bytes) + 64;
-  if ((!rec_direct || (runs && !run_direct)) && need > c->cap_vox_out) {
-    if ((rc = dev_alloc(c, &c->d_vox_out, need))) return rc;
-    c->cap_vox_out = need;
-  }
+  if ((!rec_direct || (runs && !run_direct)) && (rc = c->d_vox_out.reserve(c, need, need))) return rc;
   uint8_t* d_rec = rec_direct ? rec_direct : c->d_vox_out;
-  uint32_t* d_runs = run_direct ? run_direct : (uint32_t*)(c->d_vox_out + (rec_direct ? 0 : ((bytes + 15) & ~(size_t)15)));
+  uint32_t* d_runs = run_direct ? run_direct : (uint32_t*)(c->d_vox_out.get() + (rec_direct ? 0 : ((bytes + 15) & ~(size_t)15)));
   HIPCHK(c, hipMemsetAsync(d_cnt + 1, 0, sizeof(uint32_t), st));
   hipLaunchKernelGGL(k_export_dirty, dim3(n_list), dim3(512), 0, st, c->table, c->pool, (const uint32_t*)d_list,
                      (const uint32_t*)c->d_label_lut, c->vps_shift, 0, d_cnt, d_rec, runs ? d_runs : (uint32_t*)nullptr);
@@ -3167,40 +3085,33 @@ int ks_debug_radix_sort(ks_ctx* c, void* keys, uint32_t* vals, size_t n, int key
   if (!c || (n && !keys) || (key_bits != 32 && key_bits != 64)) return KS_ERR_INVALID_ARG;
   if (n == 0) return KS_OK;
   const size_t kb = key_bits / 8;
-  void *ka = nullptr, *kbuf = nullptr;
-  uint32_t *va = nullptr, *vb = nullptr;
-  HIPCHK(c, hipMalloc(&ka, n * kb));
-  HIPCHK(c, hipMalloc(&kbuf, n * kb));
+  DevBuf<uint8_t> ka, kbuf;
+  DevBuf<uint32_t> va, vb;
+  int rc;
+  if ((rc = ka.alloc(c, n * kb)) || (rc = kbuf.alloc(c, n * kb))) return rc;
   HIPCHK(c, hipMemcpy(ka, keys, n * kb, hipMemcpyHostToDevice));
   if (vals) {
-    HIPCHK(c, hipMalloc((void**)&va, n * 4));
-    HIPCHK(c, hipMalloc((void**)&vb, n * 4));
+    if ((rc = va.alloc(c, n)) || (rc = vb.alloc(c, n))) return rc;
     HIPCHK(c, hipMemcpy(va, vals, n * 4, hipMemcpyHostToDevice));
   }
   void* kres = nullptr;
   uint32_t* vres = nullptr;
-  int rc = KS_OK;
   if (key_bits == 32) {
     uint32_t* r = nullptr;
-    rc = vals ? sort_pairs(c, (uint32_t*)ka, (uint32_t*)kbuf, va, vb, n, end_bit, &r, &vres)
-              : sort_keys(c, (uint32_t*)ka, (uint32_t*)kbuf, n, end_bit, &r);
+    rc = vals ? sort_pairs(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres)
+              : sort_keys(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), n, end_bit, &r);
     kres = r;
   } else {
     uint64_t* r = nullptr;
-    rc = vals ? sort_pairs(c, (uint64_t*)ka, (uint64_t*)kbuf, va, vb, n, end_bit, &r, &vres)
-              : sort_keys(c, (uint64_t*)ka, (uint64_t*)kbuf, n, end_bit, &r);
+    rc = vals ? sort_pairs(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres)
+              : sort_keys(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), n, end_bit, &r);
     kres = r;
   }
-  if (rc == KS_OK) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipMemcpy(keys, kres, n * kb, hipMemcpyDeviceToHost));
-    if (vals) HIPCHK(c, hipMemcpy(vals, vres, n * 4, hipMemcpyDeviceToHost));
-  }
-  (void)hipFree(ka);
-  (void)hipFree(kbuf);
-  if (va) (void)hipFree(va);
-  if (vb) (void)hipFree(vb);
-  return rc;
+  if (rc) return rc;
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, hipMemcpy(keys, kres, n * kb, hipMemcpyDeviceToHost));
+  if (vals) HIPCHK(c, hipMemcpy(vals, vres, n * 4, hipMemcpyDeviceToHost));
+  return KS_OK;
 }
 
 int ks_get_tile_keys(ks_ctx* c, uint64_t* out, size_t cap, size_t* n) {
@@ -3343,21 +3254,21 @@ int ks_tile_owner(uint64_t tile_key, int world) { return world > 0 ? (int)(split
 // grow-only scratch of ks_reduce (no allocation in the steady state)
 static int ensure_reduce_scratch(ks_ctx* c, size_t n_send, size_t n_recv, int world) {
   int rc;
-  if ((size_t)world > c->rx_world) {
-    if ((rc = dev_alloc(c, &c->d_rx_counts, (size_t)(world + 3) * world))) return rc;  // [world] own | [world x world] all | [world] offsets | [world] cursors
-    c->rx_world = (size_t)world;
-  }
+  // [world] own | [world x world] all | [world] offsets | [world] cursors
+  if ((rc = c->d_rx_counts.reserve(c, (size_t)(world + 3) * world, (size_t)(world + 3) * world))) return rc;
   if (n_send > c->cap_tx) {
     const size_t cap = std::max<size_t>(n_send + n_send / 2, 64);
-    if ((rc = dev_alloc(c, &c->d_tx_keys, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_tx_slots, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_tx_payload, cap * (size_t)KS_TILE_BYTES))) return rc;
+    c->cap_tx = 0;
+    if ((rc = c->d_tx_keys.alloc(c, cap))) return rc;
+    if ((rc = c->d_tx_slots.alloc(c, cap))) return rc;
+    if ((rc = c->d_tx_payload.alloc(c, cap * (size_t)KS_TILE_BYTES))) return rc;
     c->cap_tx = cap;
   }
   if (n_recv > c->cap_rx) {
     const size_t cap = std::max<size_t>(n_recv + n_recv / 2, 64);
-    if ((rc = dev_alloc(c, &c->d_rx_keys, cap))) return rc;
-    if ((rc = dev_alloc(c, &c->d_rx_payload, cap * (size_t)KS_TILE_BYTES))) return rc;
+    c->cap_rx = 0;
+    if ((rc = c->d_rx_keys.alloc(c, cap))) return rc;
+    if ((rc = c->d_rx_payload.alloc(c, cap * (size_t)KS_TILE_BYTES))) return rc;
     c->cap_rx = cap;
   }
   return KS_OK;
@@ -3418,7 +3329,7 @@ int ks_reduce(ks_ctx* c, void* rccl_comm, int rank, int world, ks_reduce_stats* 
     hipLaunchKernelGGL(k_dirty_by_owner, dim3(nb), dim3(256), 0, st, c->pool, (const uint64_t*)c->table.slot_keys, nt, (uint32_t)rank,
                        (uint32_t)world, 1, d_own, (const uint32_t*)d_offs, d_cursor, c->d_tx_slots, c->d_tx_keys);
     hipLaunchKernelGGL(k_export_tiles, dim3((uint32_t)n_send), dim3(512), 0, st, c->pool, (const uint32_t*)c->d_tx_slots,
-                       (uint4*)c->d_tx_payload);
+                       (uint4*)c->d_tx_payload.get());
     HIPCHK(c, hipStreamSynchronize(st));  // (offs32 is a stack-side buffer)
   }
   // 3) keys and raw tile records: one grouped exchange — on a fully connected xGMI node a rank talks to all its
@@ -3471,17 +3382,19 @@ static int shard_apply_segment(ks_ctx* o, const uint64_t* d_gkey, const uint32_t
   int rc;
   if (n > o->cap_sh_rx) {
     const size_t cap = std::max<size_t>(n + n / 4, 1 << 18);
-    if ((rc = dev_alloc(o, &o->d_sh_tk, cap))) return rc;
+    o->cap_sh_rx = 0;
+    if ((rc = o->d_sh_tk.alloc(o, cap))) return rc;
     for (int b = 0; b < 2; ++b) {
-      if ((rc = dev_alloc(o, &o->d_sh_pairs[b], cap))) return rc;
-      if ((rc = dev_alloc(o, &o->d_sh_vals[b], cap))) return rc;
+      if ((rc = o->d_sh_pairs[b].alloc(o, cap))) return rc;
+      if ((rc = o->d_sh_vals[b].alloc(o, cap))) return rc;
     }
     o->cap_sh_rx = cap;
   }
   if (mt && n > o->cap_shm_ops) {
     const size_t cap = std::max<size_t>(n + n / 4, 1 << 18);
-    if ((rc = dev_alloc(o, &o->d_shm_ops, cap))) return rc;
-    if ((rc = dev_alloc(o, &o->d_shm_long, cap / (kLongRun + 1) + 2))) return rc;   // a long run has more than kLongRun updates
+    o->cap_shm_ops = 0;
+    if ((rc = o->d_shm_ops.alloc(o, cap))) return rc;
+    if ((rc = o->d_shm_long.alloc(o, cap / (kLongRun + 1) + 2))) return rc;   // a long run has more than kLongRun updates
     o->cap_shm_ops = cap;
   }
   hipStream_t st = o->stream;
@@ -3694,22 +3607,15 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
     // 2) receive buffers on the owner context (its own d_sh_*[0]: an owner context never exports)
     if (n_recv > o->cap_sh) {
       const size_t cap = std::max<size_t>(n_recv + n_recv / 4, 1 << 18);
-      if ((rc = dev_alloc(o, &o->d_sh_gkey[0], cap))) return rc;
-      if ((rc = dev_alloc(o, &o->d_sh_seq[0], cap))) return rc;
-      if ((rc = dev_alloc(o, &o->d_sh_sdf[0], cap))) return rc;
-      if ((rc = dev_alloc(o, &o->d_sh_uw[0], cap))) return rc;
+      o->cap_sh = 0;
+      if ((rc = o->d_sh_gkey[0].alloc(o, cap))) return rc;
+      if ((rc = o->d_sh_seq[0].alloc(o, cap))) return rc;
+      if ((rc = o->d_sh_sdf[0].alloc(o, cap))) return rc;
+      if ((rc = o->d_sh_uw[0].alloc(o, cap))) return rc;
       o->cap_sh = cap;
     }
-    if (rb_off[world] > o->cap_shm_rx_btab) {
-      const size_t cap = std::max<size_t>(rb_off[world] + rb_off[world] / 4, 1 << 14);
-      if ((rc = dev_alloc(o, &o->d_shm_rx_btab, cap))) return rc;
-      o->cap_shm_rx_btab = cap;
-    }
-    if (rm_off[world] > o->cap_shm_rx_mixed) {
-      const size_t cap = std::max<size_t>(rm_off[world] + rm_off[world] / 4, 1 << 10);
-      if ((rc = dev_alloc(o, &o->d_shm_rx_mixed, cap * kNumLabels))) return rc;
-      o->cap_shm_rx_mixed = cap;
-    }
+    if ((rc = o->d_shm_rx_btab.reserve(o, rb_off[world], std::max<size_t>(rb_off[world] + rb_off[world] / 4, 1 << 14)))) return rc;
+    if ((rc = o->d_shm_rx_mixed.reserve(o, rm_off[world] * kNumLabels, std::max<size_t>(rm_off[world] + rm_off[world] / 4, 1 << 10) * kNumLabels))) return rc;
     // 3) one grouped exchange: every rank talks to all its peers at once (xGMI is point to point)
     uint64_t bytes = 0;
     NCCLCHK(o, g_rccl.group_start());

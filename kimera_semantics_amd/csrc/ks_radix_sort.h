@@ -17,6 +17,8 @@
 #include <algorithm>
 #include <stdlib.h>
 
+#include "ks_owned.h"
+
 namespace ksrs {
 
 constexpr int kMaxPasses = 8;
@@ -319,7 +321,7 @@ __global__ void __launch_bounds__(THREADS) k_rs_pass_b(DevBatch<K> B, uint32_t c
 // Two halves used alternately: while a sort runs in one half its histogram kernel clears what the
 // previous sort left in the other, so a sort never needs a memset of its own.
 struct Workspace {
-  uint32_t* d_ws = nullptr;  // per half: [kMaxPasses][kMaxBins] histograms | kMaxPasses tickets | status[passes][tiles][bins]
+  DevBuf<uint32_t> d_ws;     // per half: [kMaxPasses][kMaxBins] histograms | kMaxPasses tickets | status[passes][tiles][bins]
   size_t words = 0;          // capacity of ONE half (multiple of 4)
   int cur = 0;               // half used by the last sort
   size_t dirty[2] = {0, 0};  // words that sort left non-zero in each half
@@ -328,11 +330,9 @@ constexpr size_t kHeadWords = (size_t)kMaxPasses * kMaxBins + kMaxPasses;
 
 inline hipError_t ensure(Workspace& w, size_t words, hipStream_t stream) {
   if (words <= w.words) return hipSuccess;
-  if (w.d_ws) (void)hipFree(w.d_ws);  // waits for the device
-  w.d_ws = nullptr;
   w.words = 0;
   const size_t cap = ((words + words / 4) + 3) & ~(size_t)3;
-  hipError_t e = hipMalloc((void**)&w.d_ws, 2 * cap * sizeof(uint32_t));
+  hipError_t e = w.d_ws.try_alloc(2 * cap);   // (frees the old block first: waits for the device)
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(w.d_ws, 0, 2 * cap * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -340,11 +340,6 @@ inline hipError_t ensure(Workspace& w, size_t words, hipStream_t stream) {
   w.cur = 0;
   w.dirty[0] = w.dirty[1] = 0;
   return hipSuccess;
-}
-
-inline void release(Workspace& w) {
-  if (w.d_ws) (void)hipFree(w.d_ws);
-  w = Workspace{};
 }
 
 template <typename K, bool HAS_VALUES, int THREADS, int ITEMS, int RB, bool REORDER = false>

@@ -502,8 +502,23 @@ inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "h
 inline hipError_t hipGetLastError() { return hipSuccess; }
 inline hipError_t hipGetDeviceCount(int* n) { *n = 1; return hipSuccess; }
 inline hipError_t hipSetDevice(int) { return hipSuccess; }
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new ihipStream_t; return hipSuccess; }
-inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; return hipSuccess; }
+// The ledger (tools/emu/README.md): what the library holds of the runtime right now — live hipMalloc + hipHostMalloc blocks and
+// their bytes, live events, live streams, and the allocations made so far.  emu_lds.cpp exports it (ks_emu_ledger) together with
+// the failure injection (ks_emu_fail_alloc: the k-th allocation from now on returns hipErrorOutOfMemory).  Freeing a block the
+// ledger does not hold — a double free, a pointer that was never allocated — ends the process with a message.
+#include <mutex>
+#include <unordered_map>
+namespace emu {
+struct Ledger {
+  std::mutex mu;
+  std::unordered_map<void*, size_t> live;
+  long long bytes = 0, allocations = 0, fail_in = -1;
+  std::atomic<long long> events{0}, streams{0};
+};
+inline Ledger g_ledger;
+}  // namespace emu
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new ihipStream_t; ++emu::g_ledger.streams; return hipSuccess; }
+inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; --emu::g_ledger.streams; return hipSuccess; }
 inline hipError_t hipStreamSynchronize(hipStream_t s) { emu::touch(s); return hipSuccess; }
 inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { emu::touch(e); emu::touch(s); return hipSuccess; }
 inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }
@@ -512,18 +527,40 @@ inline hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, void*, void*,
 inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
 inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
-inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new ihipEvent_t; return hipSuccess; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new ihipEvent_t; return hipSuccess; }
-inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new ihipEvent_t; ++emu::g_ledger.events; return hipSuccess; }
+inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
+inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; --emu::g_ledger.events; return hipSuccess; }
 inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { emu::touch(s); emu::touch(e); return hipSuccess; }
 inline hipError_t hipEventSynchronize(hipEvent_t e) { emu::touch(e); return hipSuccess; }
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 // (exactly `bytes`, 256-byte aligned like the device allocator: a sanitizer build sees every overrun)
-inline void* emu_alloc(size_t bytes) { void* p = nullptr; return posix_memalign(&p, 256, bytes ? bytes : 1) == 0 ? p : nullptr; }
+inline void* emu_alloc(size_t bytes) {
+  emu::Ledger& L = emu::g_ledger;
+  std::lock_guard<std::mutex> lk(L.mu);
+  ++L.allocations;
+  if (L.fail_in >= 0 && L.fail_in-- == 0) return nullptr;   // the injected failure (disarms itself: fail_in is -1 now)
+  void* p = nullptr;
+  if (posix_memalign(&p, 256, bytes ? bytes : 1) != 0) return nullptr;
+  L.live[p] = bytes;
+  L.bytes += (long long)bytes;
+  return p;
+}
+inline void emu_free(void* p) {
+  if (!p) return;
+  emu::Ledger& L = emu::g_ledger;
+  {
+    std::lock_guard<std::mutex> lk(L.mu);
+    auto it = L.live.find(p);
+    if (it == L.live.end()) emu::fail("hipFree / hipHostFree of a block that is not live (double free?)", 0);
+    L.bytes -= (long long)it->second;
+    L.live.erase(it);
+  }
+  free(p);
+}
 template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { *p = (T*)emu_alloc(bytes); return *p ? hipSuccess : hipErrorOutOfMemory; }
 template <typename T> inline hipError_t hipHostMalloc(T** p, size_t bytes, unsigned = 0) { *p = (T*)emu_alloc(bytes); return *p ? hipSuccess : hipErrorOutOfMemory; }
-inline hipError_t hipFree(void* p) { free(p); return hipSuccess; }
-inline hipError_t hipHostFree(void* p) { free(p); return hipSuccess; }
+inline hipError_t hipFree(void* p) { emu_free(p); return hipSuccess; }
+inline hipError_t hipHostFree(void* p) { emu_free(p); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { emu::touch((ihipStream_t*)nullptr); memmove(d, s, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st = nullptr) { emu::touch(st); memmove(d, s, n); emu::touch(st); return hipSuccess; }
 inline hipError_t hipMemset(void* d, int v, size_t n) { emu::touch((ihipStream_t*)nullptr); memset(d, v, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
