@@ -403,6 +403,17 @@ int ks_update_stats(ks_ctx* ctx, uint64_t out[4]);
 /* How the context pipelines: out[0] = frames of lag in effect (0: one frame at a time — what ks_create made of
  * ks_config.pipeline_frames), out[1] = frame slots, out[2] = frames per stage-B batch, out[3] = march streams. */
 int ks_pipeline_shape(ks_ctx* ctx, int32_t out[4]);
+/* Which chain of a frame runs on which stream.  The runtime spreads a process's streams over its hardware queues
+ * and runs kernels of streams that share a queue one after the other, so ks_create fits the context's streams into the queues
+ * the process has: out[0] = that budget (GPU_MAX_HW_QUEUES as the library found it — it only reads it —, 4 when unset or no
+ * number, 1..32), out[1] = distinct streams the context created, out[2] = march streams (= ks_pipeline_shape's), out[3] = the
+ * long-run update (k_apply_long): 1 a stream of its own beside k_apply, 0 on the stage-T stream behind it, out[4] = the same for
+ * the runs of more than 1024 updates (k_apply_xlong; -1: no such kernel, KS_XLONG=0), out[5] = stage B has streams of its own
+ * (0: it follows stage A on stage A's), out[6] = stage T has a stream of its own (0: unpipelined, stage A's), out[7] = streams
+ * the context holds (= out[1]).  Stage A, stage B and stage T never give up a stream; the two side chains do, xlong first, while
+ * the context would otherwise need more streams than the budget — below a budget of 8: from there on every context has the
+ * layout it always had.  The map is the same for every plan. */
+int ks_stream_plan(ks_ctx* ctx, int32_t out[8]);
 /* Diagnostics (host arithmetic, no device involved): the launch shape of the early-out's ordered phases for a context whose
  * frame slots hold cap_points points, integration_order_mode and early_out_phase_growth (16..4096) as in ks_config.  Per phase
  * j < max_phases: out[3 j] and out[3 j + 1] = its generations [g0, g1), out[3 j + 2] = wavefronts launched per frame = the most

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "ks_integrate_points", "ks_integrate_points_device", "ks_integrate_depth", "ks_integrate_depth_device", "ks_num_blocks", "ks_get_block_indices",
     "ks_get_updated_block_indices", "ks_count_updated_voxels", "ks_download_updated_voxels", "ks_download_blocks", "ks_upload_blocks", "ks_host_alloc", "ks_host_free", "ks_get_tile_keys", "ks_export_tiles_device", "ks_merge_tiles_device", "ks_clear", "ks_clear_voxels", "ks_reset_tiles", "ks_tile_owner", "ks_reduce",
     "ks_debug_radix_sort", "ks_synchronize", "ks_flush", "ks_stream",
-    "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
+    "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
 ]
 
@@ -160,6 +160,7 @@ def lib():
         L.ks_early_out_iterations.argtypes = [vp, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.ks_early_out_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ks_pipeline_shape.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.ks_stream_plan.argtypes = [vp, C.POINTER(C.c_int32)]
         L.ks_seed_launch_shape.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint32), C.c_int32]
         L.ks_update_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ks_integrate_round_exact.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(KsRoundStats)]
@@ -453,6 +454,15 @@ class HipIntegrator:
         out = (C.c_int32 * 4)()
         self._chk(lib().ks_pipeline_shape(self._h, out))
         return dict(lag=int(out[0]), slots=int(out[1]), batch=int(out[2]), march_streams=int(out[3]))
+
+    def stream_plan(self):
+        """dict(budget, streams, march_streams, long, xlong, march, tail): which chain runs on which stream (ks_stream_plan).
+        long / xlong: "own" (a stream beside k_apply), "tail" (on the stage-T stream, behind it) or, xlong only, "none"."""
+        out = (C.c_int32 * 8)()
+        self._chk(lib().ks_stream_plan(self._h, out))
+        side = {1: "own", 0: "tail", -1: "none"}
+        return dict(budget=int(out[0]), streams=int(out[1]), march_streams=int(out[2]), long=side[int(out[3])], xlong=side[int(out[4])],
+                    march="own" if out[5] else "A", tail="own" if out[6] else "A", streams_held=int(out[7]))
 
     def early_out_iterations(self):
         """(frames, fix-point iterations) of a KS_EARLY_OUT_EXACT context."""

@@ -94,7 +94,8 @@ const char* dbg_env(const char* name) {
 //   A  points -> sort -> dedup / bundles                  (stream)
 //   B  early-out phases, scan, emission, snapshot          (one of the march streams: frame % n_march)
 //   T  init tiles -> sort pairs -> find_long -> apply       (stream_tail; k_apply_long beside it on stream_long, k_apply_xlong
-//      on stream_xlong), enqueued by a helper thread 1..8 calls later
+//      on stream_xlong — or both behind it on stream_tail where the process has fewer hardware queues than the context
+//      has chains: stream_plan), enqueued by a helper thread 1..8 calls later
 // so that A, B and T of neighbouring frames execute concurrently: B is a chain of small dependent launches
 // (replayed as a graph captured once per slot), the sorts are bound by dependent-launch latency, the voxel
 // update by memory latency, and neither A nor B touches voxel data.  The host's one wait per frame (for the
@@ -193,6 +194,75 @@ struct ProfSet {
   uint64_t n_pairs = 0, n_points = 0;
 };
 
+// ---- the stream plan: which chain of a frame runs on which stream -------------------------------------------------------
+// The runtime spreads a process's streams over its hardware queues (GPU_MAX_HW_QUEUES of them: four unless the host says
+// otherwise), and kernels of streams that share a queue run one after the other.  A context that asks for more streams than
+// there are queues leaves it to the runtime which two of its chains serialise — a stage-B chain of 2 ms with the 9 us of the
+// runs of more than kXLongRun updates, say, whose fork and join then wait in line behind it.  So the two light
+// side chains of stage T give up their streams first: they run ON the tail stream, in order behind k_apply (the same
+// hipStream_t: an alias, a view like every named handle of ks_ctx), until the context fits the budget or nothing light is left.
+// Stage A, the march streams and stage T never fold.
+struct StreamPlanIn {
+  bool uses_early_out = false;       // `fast` whose consecutive-collision limit can fire: stage B is a chain of its own
+  bool exact_early_out = false;      // ... in the reference's serial order (the default mode)
+  bool frames_independent = true;    // a frame's early-out marks are never seen by the next frame
+  int pipeline_frames = 0;           // as in effect (ks_create may have reduced ks_config's)
+  int batch = 1;                     // frames per stage-B launch sequence
+  bool xlong = true;                 // the runs of more than kXLongRun updates have a kernel of their own (KS_XLONG)
+  int budget = 4;                    // hardware queues of the process
+};
+struct StreamPlan {
+  int budget = 4;
+  int n_march = 1;
+  bool march_own = false;            // stage B on streams of its own (else: stage A's)
+  bool tail_own = false;             // stage T on a stream of its own (else: stage A's)
+  bool long_own = true;              // k_apply_long beside k_apply (else: on the tail stream, behind it)
+  bool xlong_own = true;             // k_apply_xlong beside both (else: on the tail stream); false without xlong
+  int distinct = 1;                  // streams the context creates
+};
+inline StreamPlan stream_plan(const StreamPlanIn& in) {
+  StreamPlan p;
+  p.budget = in.budget;
+  if (in.pipeline_frames) {
+    // (shared early-out table: stage B of consecutive frames stays in order on one stream)
+    p.n_march = (!in.frames_independent || in.batch > 1) ? 1 : std::min(kMarchStreams, std::max(4, in.pipeline_frames));
+    // (exact early-out: a frame's stage B is a chain of ~75 small launches, ~1.5 ms long, and the hardware runs two or three
+    // such chains side by side at best — measured: 8 streams lose to 4.  With pipeline_frames = 8 the chain is shared by
+    // the four frames of a batch, and two batches alternate over two streams.)
+    if (in.exact_early_out && p.n_march > 4) p.n_march = 4;
+    if (in.exact_early_out && in.batch > 1) p.n_march = 2;
+    // without an early-out stage B is short (scan + emission): it follows stage A on the same stream
+    if (!in.uses_early_out) p.n_march = 1;
+    p.march_own = in.uses_early_out;
+    p.tail_own = true;
+  }
+  p.long_own = true;
+  p.xlong_own = in.xlong;
+  auto count = [&p] { return 1 + (p.march_own ? p.n_march : 0) + (p.tail_own ? 1 : 0) + (p.long_own ? 1 : 0) + (p.xlong_own ? 1 : 0); };
+  // (from eight queues on — what INTEGRATION.md 4.2 recommends and every layout was measured under — nothing folds)
+  if (p.budget < 8 && count() > p.budget) p.xlong_own = false;
+  if (p.budget < 8 && count() > p.budget) p.long_own = false;
+  p.distinct = count();
+  return p;
+}
+// Hardware queues of this process: what the runtime will read from GPU_MAX_HW_QUEUES (only read here, never set: the library
+// changes nothing in its host's environment), four — the runtime's default — when it is unset or no number.
+// KS_DEBUG=1 KS_HW_QUEUES=<n> (tests / A-B) overrides the budget of the plan; the runtime's queues stay what they are.
+inline int hw_queue_budget() {
+  auto number = [](const char* s, int* out) {
+    if (!s) return false;
+    char* end = nullptr;
+    const long v = strtol(s, &end, 10);
+    if (end == s) return false;
+    *out = (int)std::min<long>(32, std::max<long>(1, v));
+    return true;
+  };
+  int b = 4;
+  number(getenv("GPU_MAX_HW_QUEUES"), &b);
+  number(dbg_env("KS_HW_QUEUES"), &b);
+  return b;
+}
+
 // MEMBER ORDER IS TEARDOWN ORDER, reversed: the stream owners come first, so `delete c` frees every buffer, pinned block,
 // event and graph before it destroys the streams whose work referred to them (ks_destroy has synchronised them all).
 struct ks_ctx {
@@ -211,8 +281,9 @@ struct ks_ctx {
   std::vector<FrameSlot*> batch_slots;  // frames whose stage A is enqueued and whose stage B waits for the batch to fill
   hipStream_t prof_march_stream = nullptr;  // march stream of the frame being enqueued (stage events)
   hipStream_t stream_tail = nullptr;   // stage T; == stream unless pipelined
-  hipStream_t stream_long = nullptr;   // the long-run voxel update, beside k_apply (always its own stream)
-  hipStream_t stream_xlong = nullptr;  // the runs of more than kXLongRun updates, beside both (k_apply_xlong)
+  hipStream_t stream_long = nullptr;   // the long-run voxel update, beside k_apply (== stream_tail where the plan folds it)
+  hipStream_t stream_xlong = nullptr;  // the runs of more than kXLongRun updates, beside both (k_apply_xlong; == stream_tail where folded)
+  StreamPlan plan;                     // what ks_create made the streams from (ks_stream_plan)
   bool xlong = true;
   float voxel_size_inv = 0.f, log_match = 0.f, log_non_match = 0.f;
   int vps_shift = 1;  // log2(vps / 8)
@@ -1719,6 +1790,10 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     // k_apply on the tail stream, k_apply_long on its own stream (disjoint voxels)
     hipStream_t sl = c->stream_long;
     hipStream_t sx = c->stream_xlong;
+    // Where the stream plan folds a side chain, its handle IS the tail stream: its kernels follow k_apply in stream order,
+    // which is the order every fork and join below stands for, so those events are neither recorded nor waited for (and the
+    // deferred join has nothing to defer: the next frame's sort simply follows on the same stream).
+    const bool long_beside = sl != st, xlong_beside = sx && sx != st;
     unsigned long long* const d_xlong_list = sx ? d_long_list + (c->cap_pairs / kLongRunLanes + 64) : nullptr;
     const bool lanes_on = by_runs && sx && c->long_lanes && n_pairs >= c->long_lanes_min_pairs;
     // ("long" could begin at kLongRunLanes = 17 updates where the lanes kernel takes the long runs — k_find_long, k_long_measure and
@@ -1726,7 +1801,8 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     // the lanes kernel 1.47 vs 0.93 ms, the frame 6.42 vs 6.24 ms: profiles/r06_c4_merged_ab.txt.)
     // k_apply_runs decides which runs are its own by itself: the listing of the long runs (a pass over all pairs, 0.3 ms at
     // 1280x720 / 2 cm) then runs BESIDE it, on the long-run stream, instead of in front of it
-    const bool find_beside = by_runs && sx;
+    // (only where both side chains have streams of their own: on the tail stream it would run in front of k_apply_runs anyway)
+    const bool find_beside = by_runs && xlong_beside && long_beside;
     const dim3 find_grid((uint32_t)((n_pairs + 256 * kFindLongItems - 1) / (256 * kFindLongItems)));
     if (!find_beside)
       hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, st, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
@@ -1735,15 +1811,15 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     // the previous frame's long runs end before any voxel of this frame is touched
     if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
     c->pending_join = nullptr;
-    HIPCHK(c, hipEventRecord(S.fork, st));
-    HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
+    if (long_beside || xlong_beside) HIPCHK(c, hipEventRecord(S.fork, st));
+    if (long_beside) HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
     if (lanes_on) HIPCHK(c, hipMemsetAsync(c->d_long_hdr_[par], 0, sizeof(LongHdr), sl));
     if (find_beside) {
       hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
                          S.d_counters, kLongRun);
       HIPCHK(c, hipEventRecord(S.found, sl));
       HIPCHK(c, hipStreamWaitEvent(sx, S.found, 0));
-    } else if (sx) {
+    } else if (xlong_beside) {
       HIPCHK(c, hipStreamWaitEvent(sx, S.fork, 0));
     }
 #define KS_LAUNCH_APPLY_M(MODE, MERGED)                                                                              \
@@ -1813,16 +1889,18 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
     }
 #undef KS_LAUNCH_APPLY
 #undef KS_LAUNCH_APPLY_M
-    if (sx) {  // S.join stands for both lists
+    if (xlong_beside) {  // S.join stands for both lists
       HIPCHK(c, hipEventRecord(S.join_x, sx));
       HIPCHK(c, hipStreamWaitEvent(sl, S.join_x, 0));
     }
-    HIPCHK(c, hipEventRecord(S.join, sl));
-    S.join_recorded = true;
-    // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
-    // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
-    if (!(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
-    else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
+    if (long_beside) {
+      HIPCHK(c, hipEventRecord(S.join, sl));
+      S.join_recorded = true;
+      // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
+      // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
+      if (!(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
+      else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
+    }   // (else: the long runs are on the tail stream, and S.tail_done below stands for them too)
   } else {
     stage_mark(c, set, 7);
     stage_mark(c, set, 8);
@@ -2341,38 +2419,40 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   // slots: the lag plus one batch being filled, a multiple of the batch (a batch then always starts on the same slots: its
   // captured launch sequence is found again)
   c->n_slots = !c->cfg.pipeline_frames ? 1 : (c->cfg.pipeline_frames > 8 || c->batch > 4) ? kSlots : 12;
-  if (c->cfg.pipeline_frames) {
-    // (shared early-out table: stage B of consecutive frames stays in order on one stream)
-    c->n_march = (!frames_independent || c->batch > 1) ? 1 : std::min(kMarchStreams, std::max(4, c->cfg.pipeline_frames));
-    // (exact early-out: a frame's stage B is a chain of ~75 small launches, ~1.5 ms long, and the hardware runs two or three
-    // such chains side by side at best — measured: 8 streams lose to 4.  With pipeline_frames = 8 the chain is shared by
-    // the four frames of a batch, and two batches alternate over two streams.)
-    if (c->exact_early_out && c->n_march > 4) c->n_march = 4;
-    if (c->exact_early_out && c->batch > 1) c->n_march = 2;
-    // without an early-out stage B is short (scan + emission): it follows stage A on the same stream, and the three
-    // streams that remain (A+B, T, long runs) map onto hardware queues of their own
-    if (!uses_early_out) {
-      c->n_march = 1;
-      c->stream_march_[0] = c->stream;
-    } else {
-      for (int i = 0; i < c->n_march; ++i) CRKS(new_stream(&c->stream_march_[i]));
-    }
-    CRKS(new_stream(&c->stream_tail));
-  } else {
-    c->stream_march_[0] = c->stream_tail = c->stream;
-  }
   {
-    // Created LAST.  The runtime spreads streams over its hardware queues in creation order, and kernels of streams that
-    // share a hardware queue run one after the other: the heavy chains (stage B, stage T) must not share one.  With
-    // the default of four hardware queues — one of which other streams of the process use — stage A and the long
-    // runs (the two lightest: ~90 + ~65 us per 640x480 frame) are the pair that shares.
-    CRKS(new_stream(&c->stream_long));
-    // the runs of more than kXLongRun updates (the voxels next to the sensor) on a stream of their own, four waves per run
+    // the runs of more than kXLongRun updates (the voxels next to the sensor) through a kernel of their own, four waves per run
     // (k_apply_xlong).  Same arithmetic, same order: the map does not change.  KS_XLONG=0 (diagnostics): one list, k_apply_long.
-    if (const char* ar = dbg_env("KS_APPLY_RUNS")) c->apply_runs_min_pairs = atoi(ar) ? 0ull : ~0ull;   // tests / A-B: always / never
     const char* xp = dbg_env("KS_XLONG");
     c->xlong = xp ? atoi(xp) != 0 : true;
-    if (c->xlong) CRKS(new_stream(&c->stream_xlong));
+    StreamPlanIn in;
+    in.uses_early_out = uses_early_out;
+    in.exact_early_out = c->exact_early_out;
+    in.frames_independent = frames_independent;
+    in.pipeline_frames = c->cfg.pipeline_frames;
+    in.batch = c->batch;
+    in.xlong = c->xlong;
+    in.budget = hw_queue_budget();
+    c->plan = stream_plan(in);
+  }
+  {
+    // The streams of the plan.  Creation order matters: the runtime spreads streams over its hardware queues in creation order,
+    // and kernels of streams that share a hardware queue run one after the other, so the heavy chains (stage A, stage B,
+    // stage T) come first and the light side chains of stage T LAST — where the plan leaves them streams of their own.
+    // Without an early-out stage B is short (scan + emission): it follows stage A on the same stream.
+    const StreamPlan& P = c->plan;
+    c->n_march = P.n_march;
+    for (int i = 0; i < P.n_march; ++i) {
+      if (P.march_own) CRKS(new_stream(&c->stream_march_[i]));
+      else c->stream_march_[i] = c->stream;
+    }
+    if (P.tail_own) CRKS(new_stream(&c->stream_tail));
+    else c->stream_tail = c->stream;
+    // a folded chain runs on the tail stream, in order behind k_apply: the same handle, created and destroyed once
+    if (P.long_own) CRKS(new_stream(&c->stream_long));
+    else c->stream_long = c->stream_tail;
+    if (P.xlong_own) CRKS(new_stream(&c->stream_xlong));
+    else if (c->xlong) c->stream_xlong = c->stream_tail;
+    if (const char* ar = dbg_env("KS_APPLY_RUNS")) c->apply_runs_min_pairs = atoi(ar) ? 0ull : ~0ull;   // tests / A-B: always / never
     if (const char* ll = dbg_env("KS_LONG_LANES")) {   // A/B: 0 = k_apply_long (two wavefronts per run) for all of them, 2 = lanes for frames of any size (tests)
       c->long_lanes = atoi(ll) != 0;
       if (atoi(ll) == 2) c->long_lanes_min_pairs = 0ull;
@@ -3812,6 +3892,20 @@ int ks_pipeline_shape(ks_ctx* c, int32_t out[4]) {
   out[1] = c->n_slots;
   out[2] = c->batch;
   out[3] = c->n_march;
+  return KS_OK;
+}
+
+int ks_stream_plan(ks_ctx* c, int32_t out[8]) {
+  if (!c || !out) return KS_ERR_INVALID_ARG;
+  const StreamPlan& P = c->plan;
+  out[0] = P.budget;
+  out[1] = P.distinct;
+  out[2] = P.n_march;
+  out[3] = P.long_own ? 1 : 0;
+  out[4] = !c->xlong ? -1 : P.xlong_own ? 1 : 0;
+  out[5] = P.march_own ? 1 : 0;
+  out[6] = P.tail_own ? 1 : 0;
+  out[7] = c->n_streams;   // streams the context holds (= out[1])
   return KS_OK;
 }
 

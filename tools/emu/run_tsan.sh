@@ -11,7 +11,10 @@ $CXX $FLAGS -c -o /tmp/ks_tsan_lds.o "$R/tools/emu/emu_lds.cpp"
 $CXX $FLAGS -c -o /tmp/ks_tsan_main.o "$R/tools/emu/tsan_pipeline.cpp"
 $CXX -fsanitize=thread -o $OUT /tmp/ks_tsan_main.o /tmp/ks_tsan_lib.o /tmp/ks_tsan_lds.o -lpthread -ldl
 export TSAN_OPTIONS="${TSAN_OPTIONS:-halt_on_error=0 second_deadlock_stack=1 history_size=4}"
-for args in "0 4 12" "1 4 12" "0 8 14" "0 2 8" "1 8 12"; do
+# TSAN_CASES="<method> <pipeline_frames> <frames>;..." replaces the list; the stream plan follows the environment as in any
+# process (four hardware queues unless GPU_MAX_HW_QUEUES or KS_DEBUG=1 KS_HW_QUEUES say otherwise: ks_stream_plan)
+IFS=';' read -ra CASES <<< "${TSAN_CASES:-0 4 12;1 4 12;0 8 14;0 2 8;1 8 12;0 12 16}"
+for args in "${CASES[@]}"; do
   echo "== tsan_pipeline $args"
   setarch "$(uname -m)" -R $OUT $args 2>&1 | tail -${TSAN_TAIL:-40}
 done
