@@ -1190,6 +1190,112 @@ void enqueue_exact_finish(ks_ctx* c, FrameSlot& S, hipStream_t st) {
   hipLaunchKernelGGL(k_eo2_commit, dim3(1024), dim3(256), 0, st, E);
 }
 
+// What `enqueue` puts on sm (it returns KS_OK, or the error that voids the capture), captured and instantiated; nullptr where
+// the runtime refuses any of it.  Callers hold capture_mu.
+template <typename Enqueue> hipGraphExec_t capture_graph(hipStream_t sm, Enqueue enqueue) {
+  hipGraph_t g = nullptr;
+  hipGraphExec_t out = nullptr;
+  bool ok = hipStreamBeginCapture(sm, hipStreamCaptureModeRelaxed) == hipSuccess;
+  if (ok) {
+    const int rc = enqueue();
+    ok = hipStreamEndCapture(sm, &g) == hipSuccess && g != nullptr && rc == KS_OK;
+  }
+  if (ok) ok = hipGraphInstantiate(&out, g, nullptr, nullptr, 0) == hipSuccess;
+  if (g) (void)hipGraphDestroy(g);
+  return ok ? out : nullptr;
+}
+// Stage B of one batch, in the three ways it is enqueued on the batch's march stream sm (launch_batch)
+struct BatchLaunch {
+  ks_ctx* c;
+  FrameSlot* const* slots;
+  uint32_t nb;
+  FrameSlot& S0;             // the batch's first slot
+  hipStream_t sm;
+  const BatchView& V;
+  size_t steps_max;
+  uint64_t key;              // what the graphs in G have to be captured for
+  FrameSlot::GraphSet& G;
+  // long rays, plain launches: the sweeps go on until one of them changes nothing: the host reads two words per chunk of sweeps
+  // (a frame is tens of milliseconds of GPU work here, and one frame at a time: ks_create)
+  int sweeps_host_driven() const {
+    EoBatch Bt{};
+    for (uint32_t k = 0; k < nb; ++k) Bt.v[k] = eo_view(c, *slots[k]);
+    for (int chunk = 1;; ++chunk) {
+      bool going = false;
+      for (uint32_t k = 0; k < nb; ++k) {
+        uint32_t w[2] = {0u, 0u};   // {sw_prev, fail}
+        HIPCHK(c, hipMemcpyAsync(&w[0], &slots[k]->d_eo_ctl->sw_prev, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
+        HIPCHK(c, hipMemcpyAsync(&w[1], &slots[k]->d_eo_ctl->fail, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
+        HIPCHK(c, hipStreamSynchronize(sm));
+        going = going || (w[0] != 0u && w[1] == 0u);
+      }
+      if (!going || chunk >= c->eo_sweep_chunks) break;
+      enqueue_sweeps(c, Bt, nb, c->eo_sweeps, sm);
+    }
+    hipLaunchKernelGGL(k_eo2_sweep_done, dim3(nb), dim3(64), 0, sm, Bt);
+    return KS_OK;
+  }
+  // Exact early-out, event-driven (batches of one): the ordered phases give the seed; the event-driven fix point makes it the
+  // serial result, on the device: three replayed graphs, the wait for the previous frame's marks between the first two
+  int exact_device() const {
+    int rc;
+    auto seed_and_rounds = [&] {
+      enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 1);
+      return enqueue_exact_rounds(c, slots, nb, sm);
+    };
+    auto finish = [&] {
+      for (uint32_t k = 0; k < nb; ++k) enqueue_exact_finish(c, *slots[k], sm);   // (in frame order: a frame's finisher sees the marks of the one before)
+      return KS_OK;
+    };
+    auto emission = [&] { return enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 2), KS_OK; };
+    bool graphs = c->use_graphs && !S0.wide;   // (long rays: the host looks at the sweeps' progress between chunks of them)
+    if (graphs && (G.key != key || !G.g1 || !G.g2 || !G.g3)) {
+      std::lock_guard<std::mutex> cap(c->capture_mu);
+      G.reset();
+      if ((G.g1 = capture_graph(sm, seed_and_rounds)) && (G.g2 = capture_graph(sm, finish)) && (G.g3 = capture_graph(sm, emission))) {
+        G.key = key;
+      } else {
+        (void)hipGetLastError();
+        G.reset();
+        c->use_graphs = graphs = false;  // plain launches from now on
+      }
+    }
+    if (graphs) HIPCHK(c, hipGraphLaunch(G.g1, sm));
+    else if ((rc = seed_and_rounds()) || (S0.wide && (rc = sweeps_host_driven()))) return rc;
+    if (c->eo_last_commit && c->eo_last_commit != S0.eo_committed) HIPCHK(c, hipStreamWaitEvent(sm, c->eo_last_commit, 0));
+    if (graphs) HIPCHK(c, hipGraphLaunch(G.g2, sm));
+    else finish();
+    HIPCHK(c, hipEventRecord(S0.eo_committed, sm));   // (after the LAST frame's commit: the batch's frames finish in order on this stream)
+    c->eo_last_commit = S0.eo_committed;
+    if (graphs) HIPCHK(c, hipGraphLaunch(G.g3, sm));
+    else emission();
+    return KS_OK;
+  }
+  // Exact early-out, host-driven (batches of one): the ordered phases give the seed; the fix-point iteration (host waits inside) makes it serial
+  int exact_host() const {
+    enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 1);
+    if (int rc = exact_early_out(c, S0, sm)) return rc;
+    enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 2);
+    return KS_OK;
+  }
+  // Every other mode: one sequence of launches, replayed from a graph unless the context does without or the runtime has refused a capture
+  int plain_or_replayed() const {
+    if (c->use_graphs && (G.key != key || !G.g1)) {
+      std::lock_guard<std::mutex> cap(c->capture_mu);  // (rare: once per group of slots)
+      G.reset();
+      if ((G.g1 = capture_graph(sm, [&] { return enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max), KS_OK; }))) {
+        G.key = key;
+      } else {
+        (void)hipGetLastError();
+        c->use_graphs = false;  // plain launches from now on
+      }
+    }
+    if (c->use_graphs && G.g1) HIPCHK(c, hipGraphLaunch(G.g1, sm));
+    else enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max);
+    return KS_OK;
+  }
+};
+
 // Stage B of the frames whose stage A has been enqueued (consecutive frames, at most kBatchMax): ONE sequence of
 // launches for all of them, captured once per (first slot, size) and replayed.  Called by the thread that enqueues
 // stage A (graph capture and the helper thread's tail never meet on a stream).
@@ -1199,10 +1305,9 @@ int launch_batch(ks_ctx* c) {
   slots.swap(c->batch_slots);
   const uint32_t nb = (uint32_t)slots.size();
   FrameSlot& S0 = *slots[0];
-  hipStream_t st = c->stream;
   hipStream_t sm = c->batch > 1 ? c->stream_march_[(S0.frame_no / (uint64_t)c->batch) % (uint64_t)c->n_march] : march_stream(c, S0.frame_no);
   c->prof_march_stream = sm;
-  if (sm != st) HIPCHK(c, hipStreamWaitEvent(sm, slots[nb - 1]->a_done, 0));  // stage A is one in-order stream: the last frame's event covers all
+  if (sm != c->stream) HIPCHK(c, hipStreamWaitEvent(sm, slots[nb - 1]->a_done, 0));  // stage A is one in-order stream: the last frame's event covers all
   const bool stage_events = nb == 1 && S0.prof_set >= 0 && c->pset[S0.prof_set].stages;
   if (stage_events) (void)hipEventRecord(c->pset[S0.prof_set].ev[4], sm);
   // The frames' parameters go to device memory; stage B's kernels take everything else from the slots, so
@@ -1222,108 +1327,8 @@ int launch_batch(ks_ctx* c) {
   if (nb == 1) hipLaunchKernelGGL(k_set_params, dim3(1), dim3(64), 0, sm, slots[0]->F, slots[0]->d_F);
   else hipLaunchKernelGGL(k_set_params_batch, dim3(nb), dim3(64), 0, sm, PB);   // (one launch at the head of the batch's chain instead of nb)
   const uint64_t key = ((uint64_t)c->cap_points << 24) ^ (c->buffers_epoch.load() << 4) ^ (S0.wide ? 1u : 0u) ^ ((uint64_t)nb << 1);
-  FrameSlot::GraphSet& G = S0.b_graphs[nb == (uint32_t)c->batch ? 0 : 1];
-  bool replayed = false;
-  int rc;
-  if (c->exact_early_out && c->eo_device && !c->eo_device_off) {
-    // (batches of one) the ordered phases give the seed; the event-driven fix point makes it the serial result, on the
-    // device: three replayed graphs, the wait for the previous frame's marks between the first two
-    bool graphs = c->use_graphs && !S0.wide;   // (long rays: the host looks at the sweeps' progress between chunks of them)
-    if (graphs && (G.key != key || !G.g1 || !G.g2 || !G.g3)) {
-      std::lock_guard<std::mutex> cap(c->capture_mu);
-      G.reset();
-      int part_rc = KS_OK;
-      auto capture = [&](hipGraphExec_t* out, int part) -> bool {
-        hipGraph_t g = nullptr;
-        bool ok = hipStreamBeginCapture(sm, hipStreamCaptureModeRelaxed) == hipSuccess;
-        if (ok) {
-          if (part == 1) {
-            enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 1);
-            part_rc = enqueue_exact_rounds(c, slots.data(), nb, sm);
-          } else if (part == 2) {
-            for (uint32_t k = 0; k < nb; ++k) enqueue_exact_finish(c, *slots[k], sm);   // (in frame order: a frame's finisher sees the marks of the one before)
-          } else {
-            enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 2);
-          }
-          ok = hipStreamEndCapture(sm, &g) == hipSuccess && g != nullptr && part_rc == KS_OK;
-        }
-        if (ok) ok = hipGraphInstantiate(out, g, nullptr, nullptr, 0) == hipSuccess;
-        if (g) (void)hipGraphDestroy(g);
-        return ok;
-      };
-      if (capture(&G.g1, 1) && capture(&G.g2, 2) && capture(&G.g3, 3)) {
-        G.key = key;
-      } else {
-        (void)hipGetLastError();
-        G.reset();
-        c->use_graphs = graphs = false;  // plain launches from now on
-      }
-    }
-    if (graphs) HIPCHK(c, hipGraphLaunch(G.g1, sm));
-    else {
-      enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 1);
-      if ((rc = enqueue_exact_rounds(c, slots.data(), nb, sm))) return rc;
-      if (S0.wide) {
-        // the sweeps go on until one of them changes nothing: the host reads two words per chunk of sweeps (a frame is tens of
-        // milliseconds of GPU work here, and one frame at a time: ks_create)
-        EoBatch Bt{};
-        for (uint32_t k = 0; k < nb; ++k) Bt.v[k] = eo_view(c, *slots[k]);
-        for (int chunk = 1;; ++chunk) {
-          bool going = false;
-          for (uint32_t k = 0; k < nb; ++k) {
-            uint32_t w[2] = {0u, 0u};   // {sw_prev, fail}
-            HIPCHK(c, hipMemcpyAsync(&w[0], &slots[k]->d_eo_ctl->sw_prev, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
-            HIPCHK(c, hipMemcpyAsync(&w[1], &slots[k]->d_eo_ctl->fail, sizeof(uint32_t), hipMemcpyDeviceToHost, sm));
-            HIPCHK(c, hipStreamSynchronize(sm));
-            going = going || (w[0] != 0u && w[1] == 0u);
-          }
-          if (!going || chunk >= c->eo_sweep_chunks) break;
-          enqueue_sweeps(c, Bt, nb, c->eo_sweeps, sm);
-        }
-        hipLaunchKernelGGL(k_eo2_sweep_done, dim3(nb), dim3(64), 0, sm, Bt);
-      }
-    }
-    if (c->eo_last_commit && c->eo_last_commit != S0.eo_committed) HIPCHK(c, hipStreamWaitEvent(sm, c->eo_last_commit, 0));
-    if (graphs) HIPCHK(c, hipGraphLaunch(G.g2, sm));
-    else
-      for (uint32_t k = 0; k < nb; ++k) enqueue_exact_finish(c, *slots[k], sm);
-    HIPCHK(c, hipEventRecord(S0.eo_committed, sm));   // (after the LAST frame's commit: the batch's frames finish in order on this stream)
-    c->eo_last_commit = S0.eo_committed;
-    if (graphs) HIPCHK(c, hipGraphLaunch(G.g3, sm));
-    else enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 2);
-    replayed = true;
-  } else if (c->exact_early_out) {
-    // (batches of one) the ordered phases give the seed; the fix-point iteration (host waits inside) makes it the serial result
-    enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 1);
-    if ((rc = exact_early_out(c, S0, sm))) return rc;
-    enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max, 2);
-    replayed = true;
-  } else if (c->use_graphs) {
-    if (G.key != key || !G.g1) {
-      std::lock_guard<std::mutex> cap(c->capture_mu);  // (rare: once per group of slots)
-      G.reset();
-      hipGraph_t g = nullptr;
-      bool ok = hipStreamBeginCapture(sm, hipStreamCaptureModeRelaxed) == hipSuccess;
-      if (ok) {
-        enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max);
-        ok = hipStreamEndCapture(sm, &g) == hipSuccess && g != nullptr;
-      }
-      if (ok) ok = hipGraphInstantiate(&G.g1, g, nullptr, nullptr, 0) == hipSuccess;
-      if (g) (void)hipGraphDestroy(g);
-      if (ok) {
-        G.key = key;
-      } else {
-        (void)hipGetLastError();
-        G.g1 = nullptr;
-        c->use_graphs = false;  // plain launches from now on
-      }
-    }
-    if (G.g1) {
-      HIPCHK(c, hipGraphLaunch(G.g1, sm));
-      replayed = true;
-    }
-  }
-  if (!replayed) enqueue_stage_b(c, V, nb, S0.wide, sm, steps_max);
+  const BatchLaunch B{c, slots.data(), nb, S0, sm, V, steps_max, key, S0.b_graphs[nb == (uint32_t)c->batch ? 0 : 1]};
+  if (int rc = !c->exact_early_out ? B.plain_or_replayed() : c->eo_device && !c->eo_device_off ? B.exact_device() : B.exact_host()) return rc;
   for (uint32_t k = 0; k < nb; ++k) {
     HIPCHK(c, hipEventRecord(slots[k]->ready, sm));
     slots[k]->b_launched = true;
@@ -1333,11 +1338,9 @@ int launch_batch(ks_ctx* c) {
 }
 
 // ---- front half: everything up to the counter snapshot --------------------------------------
-int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, const uint8_t* d_rgba,
-                const uint8_t* d_labels, size_t n, int freespace) {
+// the frame's parameters from the context, the pose and the point count (stage A adds the order, the key window and the anti-grazing keys)
+void fill_frame_params(ks_ctx* c, FrameParams& F, const float Tq[7], size_t n, int freespace) {
   const ks_config& cfg = c->cfg;
-  int rc;
-  FrameParams& F = S.F;
   F = FrameParams{};
   F.T.w = Tq[0];
   F.T.v = {Tq[1], Tq[2], Tq[3]};
@@ -1362,13 +1365,11 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
   F.obs_tag_lo = c->obs_tag_lo;
   F.max_collisions = cfg.max_consecutive_ray_collisions;
   F.n = (uint32_t)n;
-  {
-    const uint32_t q = (uint32_t)(n / kOrderStep);
-    const bool by_1024 = c->cfg.integration_order_mode == KS_ORDER_MIXED_1024_GROUPS;
-    F.order_groups = q == 0 ? 1u : by_1024 ? kOrderStep : q;
-    F.order_per = q == 0 ? 0u : by_1024 ? q : kOrderStep;
-    F.chains = order_chains(c->cfg.integration_order_mode, n);
-  }
+  const uint32_t q = (uint32_t)(n / kOrderStep);
+  const bool by_1024 = cfg.integration_order_mode == KS_ORDER_MIXED_1024_GROUPS;
+  F.order_groups = q == 0 ? 1u : by_1024 ? kOrderStep : q;
+  F.order_per = q == 0 ? 0u : by_1024 ? q : kOrderStep;
+  F.chains = order_chains(cfg.integration_order_mode, n);
   F.carving = cfg.voxel_carving_enabled;
   F.allow_clear = cfg.allow_clear;
   F.freespace = freespace;
@@ -1377,54 +1378,151 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
   F.color_mode = cfg.color_mode;
   F.sorted_order = cfg.integration_order_mode == KS_ORDER_SORTED;
   F.n_dynamic = cfg.n_dynamic_labels;
-  {
-    const unsigned pb = bits_for(n);
-    F.point_mask = (1u << pb) - 1u;
-    F.clear_bit = (cfg.method == KS_METHOD_MERGED) ? (1u << pb) : 0u;
-    F.seq_bits = pb + (cfg.method == KS_METHOD_MERGED ? 1u : 0u);
-  }
-  F.order = nullptr;  // set below once the sorted order has been computed
+  const unsigned pb = bits_for(n);
+  F.point_mask = (1u << pb) - 1u;
+  F.clear_bit = (cfg.method == KS_METHOD_MERGED) ? (1u << pb) : 0u;
+  F.seq_bits = pb + (cfg.method == KS_METHOD_MERGED ? 1u : 0u);
   F.inv_order = F.sorted_order ? c->d_inv_order : nullptr;
   std::memcpy(F.dynamic_labels, cfg.dynamic_labels, 32);
   // the early-out can never fire if the threshold exceeds the longest possible ray
   F.early_out = c->uses_early_out;
-
-  // longest possible ray in steps: long rays get a whole wavefront per ray in stage B, short ones 16 lanes
-  const size_t steps_max = steps_max_of(cfg, c->voxel_size_inv);
-  const bool wide = steps_max > 400;
-  S.wide = wide;
-  {
-    const size_t hint = c->pairs_hint.load(std::memory_order_relaxed);
-    if ((rc = ensure_pairs_in(c, S, std::max<size_t>(hint + hint / 4, 1 << 20)))) return rc;
+}
+// the frame's profile set (its previous frame resolved first): which of its events this frame records
+void begin_prof_set(ks_ctx* c, FrameSlot& S, size_t n) {
+  const int set = (int)(c->frame_no % kProfSets);
+  resolve_prof(c, set);
+  ProfSet& P = c->pset[set];
+  P.used = true;
+  P.complete = P.applied = false;
+  P.stages = c->profiling == 1;
+  P.apply = c->profiling == 1 || (c->frame_no % 4) == 0;
+  P.n_points = n;
+  P.n_pairs = 0;
+  S.prof_set = set;
+}
+// stage A of `fast`: rays per point, the start-voxel dedup by a stable sort on the slot, the seed's work list
+int stage_a_fast(ks_ctx* c, FrameSlot& S, const float* d_xyz, const uint8_t* d_rgba, const uint8_t* d_labels, size_t n) {
+  const FrameParams& F = S.F;
+  hipStream_t st = c->stream;
+  const uint32_t nb1k = (uint32_t)((n + 1023) / 1024);
+  hipLaunchKernelGGL(k_points_fast, dim3(nb1k), dim3(1024), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
+                     S.d_rays, c->d_hash, c->d_skeys32, c->d_pvals, S.d_cnt, S.d_live, S.d_counters);
+  stage_mark(c, S.prof_set, 1);
+  // stable sort by slot only: position order inside a slot is preserved
+  uint32_t *sk = nullptr, *sv = nullptr;
+  if (int rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, kSetBits + 1, &sk, &sv)) return rc;
+  stage_mark(c, S.prof_set, 2);
+  hipLaunchKernelGGL(k_dedup, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set, S.d_ray_list, S.d_rays, S.d_cnt, S.d_live, S.d_counters);
+  if (c->uses_early_out && n > 0) {
+    // live[] is final: the work list of the seed's phases (k_test), here and not at the head of stage B's chain of
+    // dependent launches.  Only the phases this frame reaches.
+    const uint32_t n_gen = (uint32_t)((n + F.chains - 1) / F.chains);
+    uint32_t n_ph = 0;
+    while (n_ph < c->seed_phases.size() && c->seed_phases[n_ph].g0 < n_gen) ++n_ph;
+    HIPCHK(c, hipMemsetAsync(S.d_seed_n, 0, c->seed_phases.size() * sizeof(uint32_t), st));
+    hipLaunchKernelGGL(k_seed_list, dim3((F.chains + 63u) / 64u, n_ph), dim3(64 * kSeedSegs), 0, st, F, (const SeedPhase*)c->d_seed_phases,
+                       (const uint8_t*)S.d_live, S.d_seed_gen, S.d_seed_items, S.d_seed_n, S.d_counters);
   }
-
+  hipLaunchKernelGGL(k_dedup_commit, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set, S.d_counters);
+  return KS_OK;
+}
+// the bundles' ranks in the iteration order of the reference's unordered_map (ks_k_bundle_order.h):
+// insertion indices, then one walk + link launch per rehash epoch the slot capacity can reach
+void enqueue_bundle_order(ks_ctx* c, hipStream_t st, size_t n, const uint64_t* sk, const uint32_t* sv) {
+  const uint32_t capb = (uint32_t)((c->cap_points + kBoBlock - 1) / kBoBlock);
+  const size_t lds_f = (2 * c->cap_points / kBoBlock + 3) * sizeof(uint32_t), lds_e = ((size_t)capb + 2) * sizeof(uint32_t);
+  hipLaunchKernelGGL(k_bo_scan_flags, dim3((uint32_t)((2 * n + kBoBlock - 1) / kBoBlock)), dim3(kBoBlock), 0, st, (uint32_t)n, c->bo);
+  hipLaunchKernelGGL(k_bo_init, dim3((uint32_t)((n + kBoBlock - 1) / kBoBlock)), dim3(kBoBlock), lds_f, st, (uint32_t)n, sk, sv, c->bo);
+  const uint32_t nbb = (uint32_t)((n + kBoBlock - 1) / kBoBlock);  // a frame of n points has at most n bundles
+  // epochs whose bucket count fits one workgroup's LDS: one launch for all of them (both maps)
+  int e_small = 0;
+  while (e_small < c->bo_epochs && c->bo_sched.b[e_small] <= kBoSmallBuckets) ++e_small;
+  if (e_small > 0) hipLaunchKernelGGL(k_bo_small, dim3(2), dim3(kBoBlock), 0, st, c->bo, e_small);
+  // (at least the first launch pair's k_bo_link goes out: it takes over from k_bo_small)
+  const size_t nh_floor = c->bo_hint_fixed ? (e_small > 0 ? (size_t)c->bo_sched.t[e_small - 1] + 1 : 1) : 2 * (size_t)kBoSmallBuckets;
+  const size_t nh = std::min<size_t>(n, std::max<size_t>(c->bo_hint.load(std::memory_order_relaxed), nh_floor));
+  int e_last = -1;   // the epoch whose k_bo_link went out without its k_bo_walk
+  for (int e = e_small; e <= c->bo_epochs; ++e) {
+    if (e > 0 && c->bo_sched.t[e - 1] >= nh) break;  // no map of nh bundles reaches epoch e - 1
+    hipLaunchKernelGGL(k_bo_link, dim3(nbb, 2), dim3(kBoBlock), lds_e, st, c->bo, e, (e == e_small && e_small > 0) ? 1 : 0);
+    if (e < c->bo_epochs && c->bo_sched.t[e] < nh)
+      hipLaunchKernelGGL(k_bo_walk, dim3(nbb, 2), dim3(kBoBlock), 0, st, c->bo, e);
+    else
+      e_last = e;
+  }
+  // (a map with more bundles than the hint: the rest of the recurrence, one workgroup per map)
+  if (nh < n && e_last >= 0 && e_last < c->bo_epochs) hipLaunchKernelGGL(k_bo_rest, dim3(2), dim3(kBoBlock), lds_e, st, c->bo, e_last);
+}
+// stage A of `merged`: end-voxel keys per point, sorted; the points gathered in that order; bundles of points per end voxel
+int stage_a_merged(ks_ctx* c, FrameSlot& S, const float* d_xyz, const uint8_t* d_rgba, const uint8_t* d_labels, size_t n, const uint32_t* order_ptr) {
+  const ks_config& cfg = c->cfg;
+  FrameParams& F = S.F;
+  hipStream_t st = c->stream;
+  const uint32_t nb = (uint32_t)((n + 255) / 256);
+  const uint32_t nb1k = (uint32_t)((n + 1023) / 1024);
+  if (c->key_bits) {
+    // the key window of this frame: every point within max_ray of the sensor (all but far clearing points) is inside
+    const float reach = cfg.max_ray_length_m + 2.0f * cfg.voxel_size;
+    const float tq[3] = {F.T.t.x, F.T.t.y, F.T.t.z};
+    for (int a = 0; a < 3; ++a) {
+      const float lo = std::floor((tq[a] - reach) * c->voxel_size_inv) - 2.0f;
+      F.key_base[a] = (int32_t)std::min(std::max(lo, -2.0e9f), 2.0e9f);
+    }
+    F.key_bits = c->key_bits;
+  }
+  hipLaunchKernelGGL(k_points_merged, dim3(nb1k), dim3(1024), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut, c->d_pkeys, c->d_skeys32, c->d_pvals,
+                     S.d_cnt, c->use_bundle_rank ? c->bo.flag : nullptr, c->d_key_overflow, c->key_overflow_mask, S.d_counters);
+  stage_mark(c, S.prof_set, 1);
+  uint64_t* sk = nullptr;
+  uint32_t *sk32 = nullptr, *sv = nullptr;
+  if (c->key_bits) {
+    // four passes over 32-bit grouping keys instead of eight over the 64-bit end-voxel keys; k_gather_sorted writes the
+    // sorted 64-bit keys for everything downstream
+    if (int rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 32, &sk32, &sv)) return rc;
+    sk = c->d_pkeys;
+  } else {
+    if (int rc = sort_pairs(c, c->d_pkeys.get(), c->d_pkeys2.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 64, &sk, &sv)) return rc;
+  }
+  stage_mark(c, S.prof_set, 2);
+  hipLaunchKernelGGL(k_gather_sorted, dim3(nb), dim3(256), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
+                     order_ptr, (const uint64_t*)sk, (const uint32_t*)sk32, sk, sv, c->d_gpw, c->d_glc, c->use_bundle_rank ? c->bo.flag : nullptr, c->d_blong,
+                     c->d_key_overflow, S.d_counters);
+  if (c->use_bundle_rank) enqueue_bundle_order(c, st, n, sk, sv);
+  // anti-grazing: the frame keeps its own copy of the keys (the next frame's stage A reuses the sort
+  // buffers while this frame's emission — or its repetition after a pair-buffer overflow — may still run)
+  uint64_t* ray_keys = cfg.enable_anti_grazing ? S.d_rkeys : nullptr;
+  if (cfg.enable_anti_grazing) HIPCHK(c, hipMemcpyAsync(S.d_gkeys, sk, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
+  // one launch: the bundles of kLongRun points and more (one serial chain per bundle, 0.16 ms at 640x480 with a wall close
+  // to the sensor) in the first workgroups, the short bundles under them
+  const uint32_t n_long_blocks = (uint32_t)std::min<size_t>(n / kLongRun + 1, 512);
+  hipLaunchKernelGGL(k_bundles_all, dim3(n_long_blocks + (uint32_t)((n + 127) / 128)), dim3(128), 0, st, F, sk, sv, c->d_gpw, c->d_glc, c->d_blong,
+                     S.d_rays, S.d_deltas, S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters, n_long_blocks);
+  if (cfg.enable_anti_grazing) {
+    F.grazing_keys = S.d_gkeys;
+    F.ray_keys = S.d_rkeys;
+  }
+  return KS_OK;
+}
+int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, const uint8_t* d_rgba, const uint8_t* d_labels, size_t n, int freespace) {
+  int rc;
+  FrameParams& F = S.F;
+  fill_frame_params(c, F, Tq, n, freespace);
+  // longest possible ray in steps: long rays get a whole wavefront per ray in stage B, short ones 16 lanes
+  const size_t steps_max = steps_max_of(c->cfg, c->voxel_size_inv);
+  S.wide = steps_max > 400;
+  const size_t hint = c->pairs_hint.load(std::memory_order_relaxed);
+  if ((rc = ensure_pairs_in(c, S, std::max<size_t>(hint + hint / 4, 1 << 20)))) return rc;
   hipStream_t st = c->stream;
   if (S.tail_recorded && c->stream_tail != c->stream) HIPCHK(c, hipStreamWaitEvent(st, S.tail_done, 0));
   if (S.join_recorded) HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));  // (its long runs may have ended after its tail_done)
   S.n = n;
   S.prof_set = -1;
-  if (c->profiling) {
-    const int set = (int)(c->frame_no % kProfSets);
-    resolve_prof(c, set);
-    ProfSet& P = c->pset[set];
-    P.used = true;
-    P.complete = P.applied = false;
-    P.stages = c->profiling == 1;
-    P.apply = c->profiling == 1 || (c->frame_no % 4) == 0;
-    P.n_points = n;
-    P.n_pairs = 0;
-    S.prof_set = set;
-  }
-  const uint64_t this_frame = c->frame_no;
-  S.frame_no = this_frame;
-  ++c->frame_no;
+  if (c->profiling) begin_prof_set(c, S, n);
+  S.frame_no = c->frame_no++;
   // S.d_counters are zero: cleared at create time / by k_publish of the slot's previous frame
-
   const uint32_t nb = (uint32_t)((n + 255) / 256);
-  const uint32_t nb1k = (uint32_t)((n + 1023) / 1024);
   const uint32_t* order_ptr = nullptr;
   stage_mark(c, S.prof_set, 0);
-
   if (F.sorted_order) {
     hipLaunchKernelGGL(k_sqnorm, dim3(nb), dim3(256), 0, st, (uint32_t)n, d_xyz, c->d_okeys, c->d_ovals);
     uint32_t *ok = nullptr, *ov = nullptr;
@@ -1433,101 +1531,8 @@ int frame_front(ks_ctx* c, FrameSlot& S, const float Tq[7], const float* d_xyz, 
     hipLaunchKernelGGL(k_invert, dim3(nb), dim3(256), 0, st, (uint32_t)n, order_ptr, c->d_inv_order);
     F.order = order_ptr;
   }
-
-  if (cfg.method == KS_METHOD_FAST) {
-    hipLaunchKernelGGL(k_points_fast, dim3(nb1k), dim3(1024), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
-                       S.d_rays, c->d_hash, c->d_skeys32, c->d_pvals, S.d_cnt, S.d_live, S.d_counters);
-    stage_mark(c, S.prof_set, 1);
-    // stable sort by slot only: position order inside a slot is preserved
-    uint32_t *sk = nullptr, *sv = nullptr;
-    if ((rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, kSetBits + 1, &sk, &sv))) return rc;
-    stage_mark(c, S.prof_set, 2);
-    hipLaunchKernelGGL(k_dedup, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set, S.d_ray_list,
-                       S.d_rays, S.d_cnt, S.d_live, S.d_counters);
-    if (c->uses_early_out && n > 0) {
-      // live[] is final: the work list of the seed's phases (k_test), here and not at the head of stage B's chain of
-      // dependent launches.  Only the phases this frame reaches.
-      const uint32_t n_gen = (uint32_t)((n + F.chains - 1) / F.chains);
-      uint32_t n_ph = 0;
-      while (n_ph < c->seed_phases.size() && c->seed_phases[n_ph].g0 < n_gen) ++n_ph;
-      HIPCHK(c, hipMemsetAsync(S.d_seed_n, 0, c->seed_phases.size() * sizeof(uint32_t), st));
-      hipLaunchKernelGGL(k_seed_list, dim3((F.chains + 63u) / 64u, n_ph), dim3(64 * kSeedSegs), 0, st, F, (const SeedPhase*)c->d_seed_phases,
-                         (const uint8_t*)S.d_live, S.d_seed_gen, S.d_seed_items, S.d_seed_n, S.d_counters);
-    }
-    hipLaunchKernelGGL(k_dedup_commit, dim3(nb1k), dim3(1024), 0, st, F, sk, sv, c->d_hash, c->d_start_set,
-                       S.d_counters);
-  } else {
-    if (c->key_bits) {
-      // the key window of this frame: every point within max_ray of the sensor (all but far clearing points) is inside
-      const float reach = cfg.max_ray_length_m + 2.0f * cfg.voxel_size;
-      const float tq[3] = {F.T.t.x, F.T.t.y, F.T.t.z};
-      for (int a = 0; a < 3; ++a) {
-        const float lo = std::floor((tq[a] - reach) * c->voxel_size_inv) - 2.0f;
-        F.key_base[a] = (int32_t)std::min(std::max(lo, -2.0e9f), 2.0e9f);
-      }
-      F.key_bits = c->key_bits;
-    }
-    hipLaunchKernelGGL(k_points_merged, dim3(nb1k), dim3(1024), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
-                       c->d_pkeys, c->d_skeys32, c->d_pvals, S.d_cnt, c->use_bundle_rank ? c->bo.flag : nullptr, c->d_key_overflow,
-                       c->key_overflow_mask, S.d_counters);
-    stage_mark(c, S.prof_set, 1);
-    uint64_t* sk = nullptr;
-    uint32_t* sk32 = nullptr;
-    uint32_t* sv = nullptr;
-    if (c->key_bits) {
-      // four passes over 32-bit grouping keys instead of eight over the 64-bit end-voxel keys; k_gather_sorted writes the
-      // sorted 64-bit keys for everything downstream
-      if ((rc = sort_pairs(c, c->d_skeys32.get(), c->d_skeys32b.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 32, &sk32, &sv))) return rc;
-      sk = c->d_pkeys;
-    } else {
-      if ((rc = sort_pairs(c, c->d_pkeys.get(), c->d_pkeys2.get(), c->d_pvals.get(), c->d_pvals2.get(), n, 64, &sk, &sv))) return rc;
-    }
-    stage_mark(c, S.prof_set, 2);
-    hipLaunchKernelGGL(k_gather_sorted, dim3(nb), dim3(256), 0, st, F, d_xyz, d_rgba, d_labels, c->d_color_lut,
-                       order_ptr, (const uint64_t*)sk, (const uint32_t*)sk32, sk, sv, c->d_gpw, c->d_glc, c->use_bundle_rank ? c->bo.flag : nullptr, c->d_blong,
-                       c->d_key_overflow, S.d_counters);
-    if (c->use_bundle_rank) {
-      // the bundles' ranks in the iteration order of the reference's unordered_map (ks_k_bundle_order.h):
-      // insertion indices, then one walk + link launch per rehash epoch the slot capacity can reach
-      const uint32_t capb = (uint32_t)((c->cap_points + kBoBlock - 1) / kBoBlock);
-      const size_t lds_f = (2 * c->cap_points / kBoBlock + 3) * sizeof(uint32_t), lds_e = ((size_t)capb + 2) * sizeof(uint32_t);
-      hipLaunchKernelGGL(k_bo_scan_flags, dim3((uint32_t)((2 * n + kBoBlock - 1) / kBoBlock)), dim3(kBoBlock), 0, st, (uint32_t)n, c->bo);
-      hipLaunchKernelGGL(k_bo_init, dim3((uint32_t)((n + kBoBlock - 1) / kBoBlock)), dim3(kBoBlock), lds_f, st, (uint32_t)n,
-                         (const uint64_t*)sk, (const uint32_t*)sv, c->bo);
-      const uint32_t nbb = (uint32_t)((n + kBoBlock - 1) / kBoBlock);  // a frame of n points has at most n bundles
-      // epochs whose bucket count fits one workgroup's LDS: one launch for all of them (both maps)
-      int e_small = 0;
-      while (e_small < c->bo_epochs && c->bo_sched.b[e_small] <= kBoSmallBuckets) ++e_small;
-      if (e_small > 0) hipLaunchKernelGGL(k_bo_small, dim3(2), dim3(kBoBlock), 0, st, c->bo, e_small);
-      // (at least the first launch pair's k_bo_link goes out: it takes over from k_bo_small)
-      const size_t nh_floor = c->bo_hint_fixed ? (e_small > 0 ? (size_t)c->bo_sched.t[e_small - 1] + 1 : 1) : 2 * (size_t)kBoSmallBuckets;
-      const size_t nh = std::min<size_t>(n, std::max<size_t>(c->bo_hint.load(std::memory_order_relaxed), nh_floor));
-      int e_last = -1;   // the epoch whose k_bo_link went out without its k_bo_walk
-      for (int e = e_small; e <= c->bo_epochs; ++e) {
-        if (e > 0 && c->bo_sched.t[e - 1] >= nh) break;  // no map of nh bundles reaches epoch e - 1
-        hipLaunchKernelGGL(k_bo_link, dim3(nbb, 2), dim3(kBoBlock), lds_e, st, c->bo, e, (e == e_small && e_small > 0) ? 1 : 0);
-        if (e < c->bo_epochs && c->bo_sched.t[e] < nh)
-          hipLaunchKernelGGL(k_bo_walk, dim3(nbb, 2), dim3(kBoBlock), 0, st, c->bo, e);
-        else
-          e_last = e;
-      }
-      // (a map with more bundles than the hint: the rest of the recurrence, one workgroup per map)
-      if (nh < n && e_last >= 0 && e_last < c->bo_epochs) hipLaunchKernelGGL(k_bo_rest, dim3(2), dim3(kBoBlock), lds_e, st, c->bo, e_last);
-    }
-    // anti-grazing: the frame keeps its own copy of the keys (the next frame's stage A reuses the sort
-    // buffers while this frame's emission — or its repetition after a pair-buffer overflow — may still run)
-    uint64_t* ray_keys = cfg.enable_anti_grazing ? S.d_rkeys : nullptr;
-    if (cfg.enable_anti_grazing) HIPCHK(c, hipMemcpyAsync(S.d_gkeys, sk, n * sizeof(uint64_t), hipMemcpyDeviceToDevice, st));
-    // one launch: the bundles of kLongRun points and more (one serial chain per bundle, 0.16 ms at 640x480 with a wall close
-    // to the sensor) in the first workgroups, the short bundles under them
-    const uint32_t n_long_blocks = (uint32_t)std::min<size_t>(n / kLongRun + 1, 512);
-    hipLaunchKernelGGL(k_bundles_all, dim3(n_long_blocks + (uint32_t)((n + 127) / 128)), dim3(128), 0, st, F, sk, sv, c->d_gpw, c->d_glc, c->d_blong,
-                       S.d_rays, S.d_deltas, S.d_ray_list, ray_keys, S.d_cnt, c->bo, c->use_bundle_rank, S.d_counters, n_long_blocks);
-    if (cfg.enable_anti_grazing) {
-      F.grazing_keys = S.d_gkeys;
-      F.ray_keys = S.d_rkeys;
-    }
-  }
+  if ((rc = c->cfg.method == KS_METHOD_FAST ? stage_a_fast(c, S, d_xyz, d_rgba, d_labels, n) : stage_a_merged(c, S, d_xyz, d_rgba, d_labels, n, order_ptr)))
+    return rc;
   stage_mark(c, S.prof_set, 3);
   // ---- stage B (early-out phases, scan, pair emission) is enqueued per BATCH of frames: launch_batch
   if (c->stream_march_[0] != st) HIPCHK(c, hipEventRecord(S.a_done, st));
@@ -1608,22 +1613,278 @@ int shard_export_frame(ks_ctx* c, FrameSlot& S, unsigned long long n_pairs, hipS
   return KS_OK;
 }
 
+// the update's stage events of a frame that does not reach the update (an error, a marcher's export, no pairs)
+inline void skip_update_stages(ks_ctx* c, int set) {
+  for (int e = 7; e < kStageEvents - 1; ++e) stage_mark(c, set, e);
+}
+// the last event of the frame's profile set: the set is complete
+inline void finish_prof(ks_ctx* c, int set, hipStream_t st, uint64_t n_pairs) {
+  if (set < 0) return;
+  ProfSet& P = c->pset[set];
+  P.n_pairs = n_pairs;
+  (void)hipEventRecord(P.ev[kStageEvents - 1], st);
+  P.complete = true;
+}
+// the frame's statistics, owed to the caller until the next hand-over (deliver_stats)
+inline void owe_stats(ks_ctx* c, const FrameSlot& S, const Counters& cnt, unsigned long long n_pairs, uint32_t n_blocks) {
+  c->owed.n_points += S.n;
+  c->owed.n_valid_points += cnt.n_valid;
+  c->owed.n_rays_cast += cnt.n_rays;
+  c->owed.n_voxel_updates += n_pairs;
+  c->owed.n_blocks_allocated += n_blocks;
+}
+// How the early-out buffers are to grow after a fallback (hctl: the frame's control block as the device left it): requests only, nothing is launched
+void eo_grow_after_fallback(ks_ctx* c, const EoCtl& hctl) {
+  // (the largest request of the frames that failed since the buffers last grew: a later frame's smaller one must not replace it)
+  auto want_at_least = [](auto& w, auto v) {
+    auto cur = w.load(std::memory_order_relaxed);
+    while (cur < v && !w.compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
+  };
+  if (hctl.fail & kEoFailMarks) want_at_least(c->eo_want_marks, std::max<size_t>(2 * c->eo_cap_marks, (size_t)hctl.st.n_marks + (size_t)hctl.st.n_marks / 4));
+  // X marks are for the few rays the seed stopped too early; a frame that wants more of them than an eighth of its
+  // marks (2 cm voxels / 10 m rays: the approximate set is overwhelmed, the seed is wrong on most rays) is not a sparse
+  // problem, and neither is one whose lists are still long after the bulk rounds
+  const bool x_dense = (hctl.fail & kEoFailX) && (size_t)hctl.n_x > (size_t)hctl.st.n_marks / 8;
+  // lists still long when the finisher takes over: more rounds as launches for the frames to come, while there is room
+  const bool more_bulk = (hctl.fail & kEoFailRounds) && !x_dense && c->eo_bulk_rounds < (int)kEoBulkMax;
+  if (more_bulk) want_at_least(c->eo_want_bulk, std::min((int)kEoBulkMax, c->eo_bulk_rounds + std::max(4, c->eo_bulk_rounds / 2)));
+  const bool dense = x_dense || ((hctl.fail & kEoFailRounds) && !more_bulk);
+  // (the count at the moment of the failure is a lower bound — the rounds stop there — and every growth costs the frames in
+  // flight a repetition on the host: grow generously, a node is 16 bytes)
+  if ((hctl.fail & kEoFailX) && !dense) want_at_least(c->eo_want_x, std::max<size_t>(16 * c->eo_cap_x, 8 * (size_t)hctl.n_x));
+  if (dense) c->eo_hopeless.fetch_add(1, std::memory_order_relaxed);
+  else if (!(hctl.fail & kEoFailChain)) c->eo_hopeless.store(0, std::memory_order_relaxed);
+}
+// The frame's emission once more, on the tail stream, counted in d_retry_counters (k_publish has cleared the slot's counters); the host
+// waits for it.  fix_point_first: the host-driven fix point, the frame's mark in the shared table and k_scan_local go in front (after a
+// fallback the slot holds no scan).  Leaves the repetition's err and n_pairs in *cnt and the table's tile count in *new_tiles.
+int repeat_emission(ks_ctx* c, FrameSlot& S, hipStream_t st, bool fix_point_first, Counters* cnt, uint32_t* new_tiles) {
+  Counters rcnt{};
+  rcnt.n_rays = cnt->n_rays;
+  HIPCHK(c, hipMemcpyAsync(c->d_retry_counters, &rcnt, sizeof(rcnt), hipMemcpyHostToDevice, st));
+  BatchView V{};
+  V.s[0] = slot_view(S, c->d_retry_counters);
+  if (fix_point_first) {
+    if (int rc = exact_early_out(c, S, st, c->d_retry_counters)) return rc;
+    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_eo_committed, (int)(S.F.eo_frame + 1u), 1, st));
+    hipLaunchKernelGGL(k_scan_local, dim3((uint32_t)((c->cap_points + kScanBlock - 1) / kScanBlock), 1), dim3(1024), 0, st, V);
+  }
+  launch_emit(c, V, 1, S.wide, st);
+  HIPCHK(c, hipMemcpyAsync(&rcnt, c->d_retry_counters, sizeof(rcnt), hipMemcpyDeviceToHost, st));
+  uint32_t nt = 0;
+  HIPCHK(c, hipMemcpyAsync(&nt, c->table.n_tiles, sizeof(nt), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  cnt->err = rcnt.err;
+  cnt->n_pairs = rcnt.n_pairs;
+  *new_tiles = std::min(nt, c->cfg.max_tiles);
+  return KS_OK;
+}
+// The device-driven fix point gave up (marks or X marks did not fit, the finisher ran out of rounds, or the frame
+// before this one fell back and had not entered its marks yet): the host-driven loop repeats the fix point from
+// whatever lengths the slot holds (any seed converges), enters the marks, and scan + emission run again — as after a
+// pair-buffer overflow, on the tail stream only.  Nothing was emitted and no tile was allocated by this frame.
+int repair_after_fallback(ks_ctx* c, FrameSlot& S, hipStream_t st, Counters* cnt, uint32_t* new_tiles) {
+  HIPCHK(c, hipStreamSynchronize(st));
+  EoCtl hctl;
+  HIPCHK(c, hipMemcpy(&hctl, S.d_eo_ctl, sizeof(hctl), hipMemcpyDeviceToHost));
+  eo_grow_after_fallback(c, hctl);
+  c->eo_fallbacks.fetch_add(1, std::memory_order_relaxed);
+  return repeat_emission(c, S, st, /*fix_point_first=*/true, cnt, new_tiles);
+}
+// The frame's pairs did not fit the buffer sized from earlier frames: nothing was written and no tile was allocated.  Grow it and
+// repeat the emission (the scan of the counts is still in the slot).  Later frames may already have allocated tiles; the emission
+// is a get-or-insert, so that is harmless.
+// (This runs on the helper thread while the caller may be capturing stage B of another slot on a march stream: nothing here may touch
+// a march stream.  None has to: S.ready has ordered this slot's stage B, the tail stream is this thread's own, and no other frame
+// reads this slot's pair buffer.)
+int repair_after_overflow(ks_ctx* c, FrameSlot& S, hipStream_t st, Counters* cnt, uint32_t* new_tiles) {
+  HIPCHK(c, hipStreamSynchronize(st));
+  if (int rc = ensure_pairs_in(c, S, (size_t)cnt->n_pairs + (size_t)cnt->n_pairs / 4)) return rc;
+  return repeat_emission(c, S, st, /*fix_point_first=*/false, cnt, new_tiles);
+}
+// the frame's error bits as the caller's error (the profile set is closed first)
+int take_error_exits(ks_ctx* c, int set, hipStream_t st, uint32_t err) {
+  skip_update_stages(c, set);
+  finish_prof(c, set, st, 0);
+  if (err & kErrLabel) {
+    c->err = "semantic label >= 21 (CHECK_LT in the reference)";
+    return KS_ERR_LABEL_RANGE;
+  }
+  c->fatal = true;
+  c->err = (err & kErrPool) ? "voxel tile pool exhausted: raise ks_config.max_tiles" : "voxel index out of the packed range / tile table full";
+  return (err & kErrPool) ? KS_ERR_POOL_FULL : KS_ERR_INDEX_RANGE;
+}
+// ---- the voxel update: k_apply / k_apply_runs on the tail stream, the long and xlong runs beside it ----------------------
+// one launch: timed by its own begin / end events, or plain (a macro: the functional model reports a launch by the kernel's name as written)
+#define KS_LAUNCH_TIMED_IF(timed, ev0, ev1, kernel, grid, block, stream, ...)                 \
+  if (timed) hipExtLaunchKernelGGL(kernel, grid, block, 0, stream, ev0, ev1, 0, __VA_ARGS__); \
+  else hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__)
+// what the update kernels of one frame are launched with, and their launches by colour mode and method
+struct UpdateLaunch {
+  ks_ctx* c;
+  const FrameSlot& S;
+  const FrameParams& F;
+  hipStream_t st, sl, sx;   // tail | long runs | xlong runs (null: the context has no xlong kernel)
+  int set, par;             // profile set (-1: none) | parity buffer set
+  uint64_t* sp;             // the sorted pairs
+  unsigned long long n_pairs, *d_long_list, *d_xlong_list;
+  bool by_runs, time_apply, lanes_on;
+  template <int MODE, bool MERGED> void apply() const {
+    if (by_runs) {
+      // k_apply_runs: 256 threads (tiles of 1024 pairs), not 512 (tiles of 2048).  Measured at 1280x720 / 2 cm beside the long-run
+      // kernels: 2.45 vs 3.08 ms, the frame 5.98 vs 6.26 ms (profiles/r06_c4_merged_ab.txt) — a workgroup of one wavefront per SIMD
+      // finds room where one of two per SIMD does not
+      const uint32_t rb = (uint32_t)((n_pairs + kRunPer * 256u - 1) / (kRunPer * 256u));
+      KS_LAUNCH_TIMED_IF(time_apply, c->pset[set].k0, c->pset[set].k1, (k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), st, F, n_pairs, sp,
+                         S.d_rays.get(), S.d_deltas.get(), c->table, c->pool, c->d_label_lut.get(), kLongRun);
+    } else {
+      const uint32_t ab = (uint32_t)((n_pairs + 255) / 256);
+      KS_LAUNCH_TIMED_IF(time_apply, c->pset[set].k0, c->pset[set].k1, (k_apply<MODE, MERGED>), dim3(ab), dim3(256), st, F, n_pairs, sp,
+                         S.d_rays.get(), S.d_deltas.get(), c->table, c->pool, c->d_label_lut.get(), d_long_list, S.d_counters);
+    }
+  }
+  template <int MODE> void xlong_runs() const {
+    const uint32_t xb = (uint32_t)std::min<unsigned long long>(n_pairs / kXLongRun + 1, 512);
+    if (c->xl_parallel && n_pairs >= c->xl_min_pairs) {
+      // the class sums and the weight of such runs as integer sums per chunk, chunks side by side (ks_k_apply_xl.h); what
+      // the shortcut cannot carry goes to k_apply_xlong through the fall-back list
+      hipLaunchKernelGGL(k_xl_measure<MODE>, dim3(kXlMaxRuns / 256), dim3(256), 0, sx, F, n_pairs, (const uint64_t*)sp, c->pool,
+                         (const unsigned long long*)d_xlong_list, (const Counters*)S.d_counters, c->d_xl_runs);
+      hipLaunchKernelGGL(k_xl_number, dim3(1), dim3(1024), 0, sx, (const unsigned long long*)d_xlong_list, (const Counters*)S.d_counters,
+                         c->d_xl_runs, c->d_xl_idx, c->d_xl_fb, c->d_xl_hdr, c->cap_xl_chunks);
+      hipLaunchKernelGGL(k_xl_chunks, dim3(4096), dim3(256), 0, sx, F, (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas,
+                         c->table, c->d_xl_runs, (const uint32_t*)c->d_xl_idx, (const XlHeader*)c->d_xl_hdr, c->d_xl_chunks);
+      hipLaunchKernelGGL(k_xl_walk<MODE>, dim3(2048), dim3(64), 0, sx, F, (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas,
+                         c->table, c->pool, (const uint32_t*)c->d_label_lut, c->d_xl_runs, (const uint32_t*)c->d_xl_idx, c->d_xl_hdr,
+                         (const XlChunk*)c->d_xl_chunks, c->d_xl_fb);
+      hipLaunchKernelGGL(k_apply_xlong<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut,
+                         (const unsigned long long*)c->d_xl_fb, (const uint32_t*)&c->d_xl_hdr->n_fallback);
+    } else {
+      hipLaunchKernelGGL(k_apply_xlong<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut,
+                         d_xlong_list, (const uint32_t*)&S.d_counters->n_xlong);
+    }
+  }
+  // the runs of kLongRun updates and more, a wavefront per run; with lanes_on, bucketed by length, a lane per run first
+  template <int MODE> void long_runs() const {
+    const uint32_t lb = (uint32_t)std::min<unsigned long long>(n_pairs / kLongRun + 1, 4096);
+    if (lanes_on) {
+      const uint32_t cap_long = (uint32_t)(n_pairs / (kLongRun + 1) + 1);
+      hipLaunchKernelGGL(k_long_measure, dim3((cap_long + 255) / 256), dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list,
+                         (const Counters*)S.d_counters, c->d_long_hdr_[par], kLongRun);
+      hipLaunchKernelGGL(k_long_bucket, dim3((cap_long + 255) / 256), dim3(256), 0, sl, (const unsigned long long*)d_long_list,
+                         (const Counters*)S.d_counters, c->d_long_hdr_[par], c->d_long_sorted_[par]);
+      hipLaunchKernelGGL((k_apply_long_lanes<MODE, 6u>), dim3((cap_long / 64 + kLongClasses + 3) / 4), dim3(256), 0, sl, F, (const uint64_t*)sp,
+                         (const RayDesc*)S.d_rays, (const float*)S.d_deltas, c->table, c->pool, (const uint32_t*)c->d_label_lut,
+                         (const LongHdr*)c->d_long_hdr_[par], (const unsigned long long*)c->d_long_sorted_[par]);
+      hipLaunchKernelGGL(k_apply_long<MODE>, dim3(std::min<uint32_t>(lb, 1024u)), dim3(128), 0, sl, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table,
+                         c->pool, c->d_label_lut, (const unsigned long long*)c->d_long_sorted_[par], (const Counters*)S.d_counters,
+                         (const LongHdr*)c->d_long_hdr_[par]);
+    } else {
+      hipLaunchKernelGGL(k_apply_long<MODE>, dim3(lb), dim3(128), 0, sl, F, n_pairs, sp, S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut,
+                         d_long_list, S.d_counters);
+    }
+  }
+  template <int MODE> void launch() const {
+    c->cfg.method == KS_METHOD_MERGED ? apply<MODE, true>() : apply<MODE, false>();
+    stage_mark(c, set, 9);
+    if (sx) xlong_runs<MODE>();
+    long_runs<MODE>();
+  }
+};
+#undef KS_LAUNCH_TIMED_IF
+// The frame's n_pairs updates into the map: sorted by voxel, then k_apply with the long and xlong runs forked off beside it
+int enqueue_update(ks_ctx* c, FrameSlot& S, hipStream_t st, unsigned long long n_pairs, uint32_t new_tiles, int set) {
+  if (n_pairs == 0) {
+    // a frame without updates still separates the frame before it from the one after it, which share a parity
+    // buffer set: the long runs of the previous frame end before anything later is enqueued on the tail stream
+    if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
+    c->pending_join = nullptr;
+    skip_update_stages(c, set);
+    return KS_OK;
+  }
+  const FrameParams& F = S.F;
+  int rc;
+  if ((rc = ensure_pairs_out(c, n_pairs))) return rc;
+  stage_mark(c, set, 7);
+  const unsigned end_bit = F.seq_bits + 9 + bits_for(new_tiles);
+  uint64_t* sp = nullptr;
+  // k_emit wrote the pairs in integration order; the stable sort only groups them by voxel (it skips
+  // the sequence bits), so every voxel replays its updates in the reference's single-thread order.
+  const int par = (int)(S.frame_no & 1u);
+  unsigned long long* const d_long_list = c->d_long_list_[par];
+  if ((rc = sort_keys(c, S.d_pairs.get(), c->d_pairs2_[par].get(), n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
+  stage_mark(c, set, 8);
+  const bool by_runs = n_pairs >= c->apply_runs_min_pairs;
+  const bool time_apply = set >= 0 && c->pset[set].apply;
+  if (time_apply) c->pset[set].applied = true;
+  // long runs (voxels next to the sensor) are listed first; then the two update kernels run side by side:
+  // k_apply on the tail stream, k_apply_long on its own stream (disjoint voxels)
+  hipStream_t sl = c->stream_long, sx = c->stream_xlong;
+  // Where the stream plan folds a side chain, its handle IS the tail stream: its kernels follow k_apply in stream order,
+  // which is the order every fork and join below stands for, so those events are neither recorded nor waited for (and the
+  // deferred join has nothing to defer: the next frame's sort simply follows on the same stream).
+  const bool long_beside = sl != st, xlong_beside = sx && sx != st;
+  unsigned long long* const d_xlong_list = sx ? d_long_list + (c->cap_pairs / kLongRunLanes + 64) : nullptr;
+  const bool lanes_on = by_runs && sx && c->long_lanes && n_pairs >= c->long_lanes_min_pairs;
+  // ("long" could begin at kLongRunLanes = 17 updates where the lanes kernel takes the long runs — k_find_long, k_long_measure and
+  // k_apply_runs take the threshold as an argument — but measured at 1280x720 / 2 cm it buys nothing: k_apply_runs 2.83 vs 2.79 ms,
+  // the lanes kernel 1.47 vs 0.93 ms, the frame 6.42 vs 6.24 ms: profiles/r06_c4_merged_ab.txt.)
+  // k_apply_runs decides which runs are its own by itself: the listing of the long runs (a pass over all pairs, 0.3 ms at
+  // 1280x720 / 2 cm) then runs BESIDE it, on the long-run stream, instead of in front of it
+  // (only where both side chains have streams of their own: on the tail stream it would run in front of k_apply_runs anyway)
+  const bool find_beside = by_runs && xlong_beside && long_beside;
+  const dim3 find_grid((uint32_t)((n_pairs + 256 * kFindLongItems - 1) / (256 * kFindLongItems)));
+  if (!find_beside)
+    hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, st, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
+                       S.d_counters, kLongRun);
+  // the previous frame's long runs end before any voxel of this frame is touched
+  if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
+  c->pending_join = nullptr;
+  if (long_beside || xlong_beside) HIPCHK(c, hipEventRecord(S.fork, st));
+  if (long_beside) HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
+  if (lanes_on) HIPCHK(c, hipMemsetAsync(c->d_long_hdr_[par], 0, sizeof(LongHdr), sl));
+  if (find_beside) {
+    hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
+                       S.d_counters, kLongRun);
+    HIPCHK(c, hipEventRecord(S.found, sl));
+    HIPCHK(c, hipStreamWaitEvent(sx, S.found, 0));
+  } else if (xlong_beside) {
+    HIPCHK(c, hipStreamWaitEvent(sx, S.fork, 0));
+  }
+  const UpdateLaunch U{c, S, F, st, sl, sx, set, par, sp, n_pairs, d_long_list, d_xlong_list, by_runs, time_apply, lanes_on};
+  switch (c->cfg.color_mode) {
+    case KS_COLOR_MODE_COLOR: U.launch<KS_COLOR_MODE_COLOR>(); break;
+    case KS_COLOR_MODE_SEMANTIC: U.launch<KS_COLOR_MODE_SEMANTIC>(); break;
+    default: U.launch<KS_COLOR_MODE_SEMANTIC_PROBABILITY>(); break;
+  }
+  if (xlong_beside) {  // S.join stands for both lists
+    HIPCHK(c, hipEventRecord(S.join_x, sx));
+    HIPCHK(c, hipStreamWaitEvent(sl, S.join_x, 0));
+  }
+  if (long_beside) {
+    HIPCHK(c, hipEventRecord(S.join, sl));
+    S.join_recorded = true;
+    // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
+    // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
+    if (!(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
+    else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
+  }   // (else: the long runs are on the tail stream, and S.tail_done below stands for them too)
+  return KS_OK;
+}
+
 int frame_tail(ks_ctx* c, FrameSlot& S) {
   if (!S.pending) return KS_OK;
   S.pending = false;
   // After a pool / index failure the table may hold entries without a tile: frames that were
   // already in flight are dropped, never applied (the error has been reported for the frame that hit it).
   if (c->fatal) return KS_OK;
-  if (!S.b_launched) {  // the frame's batch has not filled up (flush, or a lag shorter than the batch): it goes out as it is
-    if (int rc = launch_batch(c)) return rc;
-  }
+  int rc;
+  // (the frame's batch has not filled up — a flush, or a lag shorter than the batch: it goes out as it is)
+  if (!S.b_launched && (rc = launch_batch(c))) return rc;
   hipStream_t st = c->stream_tail;  // the host wait below orders the tail after the slot's front
-  const FrameParams& F = S.F;
-  {
-    const auto w0 = std::chrono::steady_clock::now();
-    HIPCHK(c, hipEventSynchronize(S.ready));  // the frame's only host wait
-    if (c->profiling) c->prof.host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
-  }
+  const auto w0 = std::chrono::steady_clock::now();
+  HIPCHK(c, hipEventSynchronize(S.ready));  // the frame's only host wait
+  if (c->profiling) c->prof.host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   Counters cnt = S.counters();
   uint32_t new_tiles = std::min(S.n_tiles(), c->cfg.max_tiles);
   const uint32_t tiles_before = c->tiles_initialised;
@@ -1632,290 +1893,28 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
   if (c->eo_device && !c->eo_device_off) {
     c->eo_frames += 1;
     c->eo_iterations += S.h_snap->pad[2];   // rounds of the event-driven fix point (k_publish)
+    if (!(cnt.err & kErrExact)) c->eo_hopeless.store(0, std::memory_order_relaxed);
   }
-  if (c->eo_device && !c->eo_device_off && !(cnt.err & kErrExact)) c->eo_hopeless.store(0, std::memory_order_relaxed);
-  if ((cnt.err & kErrExact) && !(cnt.err & (kErrLabel | kErrIndex))) {
-    // The device-driven fix point gave up (marks or X marks did not fit, the finisher ran out of rounds, or the frame
-    // before this one fell back and had not entered its marks yet): the host-driven loop repeats the fix point from
-    // whatever lengths the slot holds (any seed converges), enters the marks, and scan + emission run again — as after a
-    // pair-buffer overflow, on the tail stream only.  Nothing was emitted and no tile was allocated by this frame.
-    int rc;
-    HIPCHK(c, hipStreamSynchronize(st));
-    EoCtl hctl;
-    HIPCHK(c, hipMemcpy(&hctl, S.d_eo_ctl, sizeof(hctl), hipMemcpyDeviceToHost));
-    // (the largest request of the frames that failed since the buffers last grew: a later frame's smaller one must not replace it)
-    auto want_at_least = [](std::atomic<size_t>& w, size_t v) {
-      size_t cur = w.load(std::memory_order_relaxed);
-      while (cur < v && !w.compare_exchange_weak(cur, v, std::memory_order_relaxed)) {}
-    };
-    if (hctl.fail & kEoFailMarks)
-      want_at_least(c->eo_want_marks, std::max<size_t>(2 * c->eo_cap_marks, (size_t)hctl.st.n_marks + (size_t)hctl.st.n_marks / 4));
-    // X marks are for the few rays the seed stopped too early; a frame that wants more of them than an eighth of its
-    // marks (2 cm voxels / 10 m rays: the approximate set is overwhelmed, the seed is wrong on most rays) is not a sparse
-    // problem, and neither is one whose lists are still long after the bulk rounds
-    const bool x_dense = (hctl.fail & kEoFailX) && (size_t)hctl.n_x > (size_t)hctl.st.n_marks / 8;
-    // lists still long when the finisher takes over: more rounds as launches for the frames to come, while there is room
-    const bool more_bulk = (hctl.fail & kEoFailRounds) && !x_dense && c->eo_bulk_rounds < (int)kEoBulkMax;
-    if (more_bulk) {
-      const int w = std::min((int)kEoBulkMax, c->eo_bulk_rounds + std::max(4, c->eo_bulk_rounds / 2));
-      int cur = c->eo_want_bulk.load(std::memory_order_relaxed);
-      while (cur < w && !c->eo_want_bulk.compare_exchange_weak(cur, w, std::memory_order_relaxed)) {}
-    }
-    const bool dense = x_dense || ((hctl.fail & kEoFailRounds) && !more_bulk);
-    // (the count at the moment of the failure is a lower bound — the rounds stop there — and every growth costs the frames in
-    // flight a repetition on the host: grow generously, a node is 16 bytes)
-    if ((hctl.fail & kEoFailX) && !dense) want_at_least(c->eo_want_x, std::max<size_t>(16 * c->eo_cap_x, 8 * (size_t)hctl.n_x));
-    if (dense) c->eo_hopeless.fetch_add(1, std::memory_order_relaxed);
-    else if (!(hctl.fail & kEoFailChain)) c->eo_hopeless.store(0, std::memory_order_relaxed);
-    c->eo_fallbacks.fetch_add(1, std::memory_order_relaxed);
-    Counters rcnt{};
-    rcnt.n_rays = cnt.n_rays;
-    HIPCHK(c, hipMemcpyAsync(c->d_retry_counters, &rcnt, sizeof(rcnt), hipMemcpyHostToDevice, st));
-    if ((rc = exact_early_out(c, S, st, c->d_retry_counters))) return rc;
-    HIPCHK(c, hipMemsetD32Async((hipDeviceptr_t)c->d_eo_committed, (int)(S.F.eo_frame + 1u), 1, st));
-    {
-      BatchView V{};
-      V.s[0] = slot_view(S, c->d_retry_counters);
-      hipLaunchKernelGGL(k_scan_local, dim3((uint32_t)((c->cap_points + kScanBlock - 1) / kScanBlock), 1), dim3(1024), 0, st, V);
-      launch_emit(c, V, 1, S.wide, st);
-    }
-    HIPCHK(c, hipMemcpyAsync(&rcnt, c->d_retry_counters, sizeof(rcnt), hipMemcpyDeviceToHost, st));
-    uint32_t nt = 0;
-    HIPCHK(c, hipMemcpyAsync(&nt, c->table.n_tiles, sizeof(nt), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    cnt.err = rcnt.err;
-    cnt.n_pairs = rcnt.n_pairs;
-    new_tiles = std::min(nt, c->cfg.max_tiles);
-  }
+  if ((cnt.err & kErrExact) && !(cnt.err & (kErrLabel | kErrIndex)) && (rc = repair_after_fallback(c, S, st, &cnt, &new_tiles))) return rc;
   c->pairs_hint.store(std::max<size_t>(c->pairs_hint.load(std::memory_order_relaxed), cnt.n_pairs), std::memory_order_relaxed);
-  if ((cnt.err & kErrPairs) && !(cnt.err & ~kErrPairs)) {
-    // The frame's pairs did not fit the buffer sized from earlier frames: nothing was written and no tile
-    // was allocated.  Grow it and repeat the emission (the scan of the counts is still in the slot).
-    // Later frames may already have allocated tiles; the emission is a get-or-insert, so that is harmless.
-    // (This runs on the helper thread while the caller may be capturing stage B of another slot on a march
-    // stream: nothing here may touch a march stream.  None has to: S.ready has ordered this slot's stage B, the
-    // tail stream is this thread's own, and no other frame reads this slot's pair buffer.)
-    int rc;
-    HIPCHK(c, hipStreamSynchronize(st));
-    if ((rc = ensure_pairs_in(c, S, (size_t)cnt.n_pairs + (size_t)cnt.n_pairs / 4))) return rc;
-    Counters rcnt{};
-    rcnt.n_rays = cnt.n_rays;
-    HIPCHK(c, hipMemcpyAsync(c->d_retry_counters, &rcnt, sizeof(rcnt), hipMemcpyHostToDevice, st));
-    {
-      BatchView V{};
-      V.s[0] = slot_view(S, c->d_retry_counters);
-      launch_emit(c, V, 1, S.wide, st);
-    }
-    HIPCHK(c, hipMemcpyAsync(&rcnt, c->d_retry_counters, sizeof(rcnt), hipMemcpyDeviceToHost, st));
-    uint32_t nt = 0;
-    HIPCHK(c, hipMemcpyAsync(&nt, c->table.n_tiles, sizeof(nt), hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    cnt.err = rcnt.err;
-    cnt.n_pairs = rcnt.n_pairs;
-    new_tiles = std::min(nt, c->cfg.max_tiles);
-  }
+  if ((cnt.err & kErrPairs) && !(cnt.err & ~kErrPairs) && (rc = repair_after_overflow(c, S, st, &cnt, &new_tiles))) return rc;
   // tiles allocated by the front exist in the table whatever happens next: make them valid
   if (new_tiles > c->tiles_initialised) {
-    hipLaunchKernelGGL(k_init_tiles, dim3(new_tiles - c->tiles_initialised), dim3(512), 0, st, c->pool,
-                       c->tiles_initialised);
+    hipLaunchKernelGGL(k_init_tiles, dim3(new_tiles - c->tiles_initialised), dim3(512), 0, st, c->pool, c->tiles_initialised);
     c->tiles_initialised = new_tiles;
   }
-  auto finish_prof = [&](uint64_t n_pairs) {
-    if (set < 0) return;
-    ProfSet& P = c->pset[set];
-    P.n_pairs = n_pairs;
-    (void)hipEventRecord(P.ev[kStageEvents - 1], st);
-    P.complete = true;
-  };
-  if (cnt.err & kErrLabel) {
-    for (int e = 7; e < kStageEvents - 1; ++e) stage_mark(c, set, e);
-    finish_prof(0);
-    c->err = "semantic label >= 21 (CHECK_LT in the reference)";
-    return KS_ERR_LABEL_RANGE;
-  }
-  if (cnt.err) {
-    for (int e = 7; e < kStageEvents - 1; ++e) stage_mark(c, set, e);
-    finish_prof(0);
-    c->fatal = true;
-    if (cnt.err & kErrPool) {
-      c->err = "voxel tile pool exhausted: raise ks_config.max_tiles";
-      return KS_ERR_POOL_FULL;
-    }
-    c->err = "voxel index out of the packed range / tile table full";
-    return KS_ERR_INDEX_RANGE;
-  }
+  if (cnt.err) return take_error_exits(c, set, st, cnt.err);
   const unsigned long long n_pairs = cnt.n_pairs;
-  if (c->shard_export) {
-    // a marcher of ks_integrate_round_exact: the frame's updates leave as records, grouped by the rank that owns their tile
-    for (int e = 7; e < kStageEvents - 1; ++e) stage_mark(c, set, e);
-    if (int rc = shard_export_frame(c, S, n_pairs, st)) return rc;
-    finish_prof(n_pairs);
-    HIPCHK(c, hipEventRecord(S.tail_done, st));
-    S.tail_recorded = true;
-    c->owed.n_points += S.n;
-    c->owed.n_valid_points += cnt.n_valid;
-    c->owed.n_rays_cast += cnt.n_rays;
-    c->owed.n_voxel_updates += n_pairs;
-    return KS_OK;
-  }
-  if (n_pairs == 0 && c->pending_join) {
-    // a frame without updates still separates the frame before it from the one after it, which share a parity
-    // buffer set: the long runs of the previous frame end before anything later is enqueued on the tail stream
-    HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
-    c->pending_join = nullptr;
-  }
-  if (n_pairs > 0) {
-    int rc;
-    if ((rc = ensure_pairs_out(c, n_pairs))) return rc;
-    stage_mark(c, set, 7);
-    const unsigned end_bit = F.seq_bits + 9 + bits_for(new_tiles);
-    uint64_t* sp = nullptr;
-    // k_emit wrote the pairs in integration order; the stable sort only groups them by voxel (it skips
-    // the sequence bits), so every voxel replays its updates in the reference's single-thread order.
-    const int par = (int)(S.frame_no & 1u);
-    uint64_t* const d_pairs2 = c->d_pairs2_[par];
-    unsigned long long* const d_long_list = c->d_long_list_[par];
-    if ((rc = sort_keys(c, S.d_pairs.get(), d_pairs2, n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
-    stage_mark(c, set, 8);
-    const uint32_t ab = (uint32_t)((n_pairs + 255) / 256);
-    // k_apply_runs: 256 threads (tiles of 1024 pairs), not 512 (tiles of 2048).  Measured at 1280x720 / 2 cm beside the long-run
-    // kernels: 2.45 vs 3.08 ms, the frame 5.98 vs 6.26 ms (profiles/r06_c4_merged_ab.txt) — a workgroup of one wavefront per SIMD
-    // finds room where one of two per SIMD does not
-    const uint32_t rb = (uint32_t)((n_pairs + kRunPer * 256u - 1) / (kRunPer * 256u));
-    const bool by_runs = n_pairs >= c->apply_runs_min_pairs;
-    const uint32_t lb = (uint32_t)std::min<unsigned long long>(n_pairs / kLongRun + 1, 4096);
-    const bool time_apply = set >= 0 && c->pset[set].apply;
-    if (time_apply) c->pset[set].applied = true;
-    // long runs (voxels next to the sensor) are listed first; then the two update kernels run side by side:
-    // k_apply on the tail stream, k_apply_long on its own stream (disjoint voxels)
-    hipStream_t sl = c->stream_long;
-    hipStream_t sx = c->stream_xlong;
-    // Where the stream plan folds a side chain, its handle IS the tail stream: its kernels follow k_apply in stream order,
-    // which is the order every fork and join below stands for, so those events are neither recorded nor waited for (and the
-    // deferred join has nothing to defer: the next frame's sort simply follows on the same stream).
-    const bool long_beside = sl != st, xlong_beside = sx && sx != st;
-    unsigned long long* const d_xlong_list = sx ? d_long_list + (c->cap_pairs / kLongRunLanes + 64) : nullptr;
-    const bool lanes_on = by_runs && sx && c->long_lanes && n_pairs >= c->long_lanes_min_pairs;
-    // ("long" could begin at kLongRunLanes = 17 updates where the lanes kernel takes the long runs — k_find_long, k_long_measure and
-    // k_apply_runs take the threshold as an argument — but measured at 1280x720 / 2 cm it buys nothing: k_apply_runs 2.83 vs 2.79 ms,
-    // the lanes kernel 1.47 vs 0.93 ms, the frame 6.42 vs 6.24 ms: profiles/r06_c4_merged_ab.txt.)
-    // k_apply_runs decides which runs are its own by itself: the listing of the long runs (a pass over all pairs, 0.3 ms at
-    // 1280x720 / 2 cm) then runs BESIDE it, on the long-run stream, instead of in front of it
-    // (only where both side chains have streams of their own: on the tail stream it would run in front of k_apply_runs anyway)
-    const bool find_beside = by_runs && xlong_beside && long_beside;
-    const dim3 find_grid((uint32_t)((n_pairs + 256 * kFindLongItems - 1) / (256 * kFindLongItems)));
-    if (!find_beside)
-      hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, st, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
-                         S.d_counters, kLongRun);
-    const uint32_t xb = (uint32_t)std::min<unsigned long long>(n_pairs / kXLongRun + 1, 512);
-    // the previous frame's long runs end before any voxel of this frame is touched
-    if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
-    c->pending_join = nullptr;
-    if (long_beside || xlong_beside) HIPCHK(c, hipEventRecord(S.fork, st));
-    if (long_beside) HIPCHK(c, hipStreamWaitEvent(sl, S.fork, 0));
-    if (lanes_on) HIPCHK(c, hipMemsetAsync(c->d_long_hdr_[par], 0, sizeof(LongHdr), sl));
-    if (find_beside) {
-      hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, sl, F.seq_bits, n_pairs, (const uint64_t*)sp, d_long_list, d_xlong_list,
-                         S.d_counters, kLongRun);
-      HIPCHK(c, hipEventRecord(S.found, sl));
-      HIPCHK(c, hipStreamWaitEvent(sx, S.found, 0));
-    } else if (xlong_beside) {
-      HIPCHK(c, hipStreamWaitEvent(sx, S.fork, 0));
-    }
-#define KS_LAUNCH_APPLY_M(MODE, MERGED)                                                                              \
-  if (by_runs && time_apply)                                                                                         \
-    hipExtLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, c->pset[set].k0,           \
-                          c->pset[set].k1, 0, F, n_pairs, sp, S.d_rays.get(), S.d_deltas.get(), c->table, c->pool,     \
-                          c->d_label_lut.get(), kLongRun);                                                             \
-  else if (by_runs)                                                                                                  \
-    hipLaunchKernelGGL((k_apply_runs<MODE, MERGED, 256u>), dim3(rb), dim3(256), 0, st, F, n_pairs, sp, S.d_rays,     \
-                       S.d_deltas, c->table, c->pool, c->d_label_lut, kLongRun);                                      \
-  else if (time_apply)                                                                                               \
-    hipExtLaunchKernelGGL((k_apply<MODE, MERGED>), dim3(ab), dim3(256), 0, st, c->pset[set].k0, c->pset[set].k1, 0,   \
-                          F, n_pairs, sp, S.d_rays.get(), S.d_deltas.get(), c->table, c->pool, c->d_label_lut.get(),  \
-                          d_long_list, S.d_counters);                                                                 \
-  else                                                                                                               \
-    hipLaunchKernelGGL((k_apply<MODE, MERGED>), dim3(ab), dim3(256), 0, st, F, n_pairs, sp, S.d_rays, S.d_deltas,     \
-                       c->table, c->pool, c->d_label_lut, d_long_list, S.d_counters)
-#define KS_LAUNCH_APPLY(MODE)                                                                                        \
-  if (c->cfg.method == KS_METHOD_MERGED) {                                                                           \
-    KS_LAUNCH_APPLY_M(MODE, true);                                                                                   \
-  } else {                                                                                                           \
-    KS_LAUNCH_APPLY_M(MODE, false);                                                                                  \
-  }                                                                                                                  \
-  stage_mark(c, set, 9);                                                                                             \
-  if (sx && c->xl_parallel && n_pairs >= c->xl_min_pairs) {                                                          \
-    /* the class sums and the weight of such runs as integer sums per chunk, chunks side by side (ks_k_apply_xl.h); what \
-       the shortcut cannot carry goes to k_apply_xlong through the fall-back list */                                    \
-    hipLaunchKernelGGL(k_xl_measure<MODE>, dim3(kXlMaxRuns / 256), dim3(256), 0, sx, F, n_pairs, (const uint64_t*)sp,  \
-                       c->pool, (const unsigned long long*)d_xlong_list, (const Counters*)S.d_counters, c->d_xl_runs); \
-    hipLaunchKernelGGL(k_xl_number, dim3(1), dim3(1024), 0, sx, (const unsigned long long*)d_xlong_list,               \
-                       (const Counters*)S.d_counters, c->d_xl_runs, c->d_xl_idx, c->d_xl_fb, c->d_xl_hdr,              \
-                       c->cap_xl_chunks);                                                                               \
-    hipLaunchKernelGGL(k_xl_chunks, dim3(4096), dim3(256), 0, sx, F, (const uint64_t*)sp, (const RayDesc*)S.d_rays,    \
-                       (const float*)S.d_deltas, c->table, c->d_xl_runs, (const uint32_t*)c->d_xl_idx,                 \
-                       (const XlHeader*)c->d_xl_hdr, c->d_xl_chunks);                                                   \
-    hipLaunchKernelGGL(k_xl_walk<MODE>, dim3(2048), dim3(64), 0, sx, F, (const uint64_t*)sp, (const RayDesc*)S.d_rays, \
-                       (const float*)S.d_deltas, c->table, c->pool, (const uint32_t*)c->d_label_lut, c->d_xl_runs,     \
-                       (const uint32_t*)c->d_xl_idx, c->d_xl_hdr, (const XlChunk*)c->d_xl_chunks, c->d_xl_fb);         \
-    hipLaunchKernelGGL(k_apply_xlong<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, sp, S.d_rays, S.d_deltas,          \
-                       c->table, c->pool, c->d_label_lut, (const unsigned long long*)c->d_xl_fb,                        \
-                       (const uint32_t*)&c->d_xl_hdr->n_fallback);                                                      \
-  } else if (sx)                                                                                                     \
-    hipLaunchKernelGGL(k_apply_xlong<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, sp, S.d_rays, S.d_deltas,            \
-                       c->table, c->pool, c->d_label_lut, d_xlong_list, (const uint32_t*)&S.d_counters->n_xlong);      \
-  if (lanes_on) {                                                                                                    \
-    const uint32_t cap_long = (uint32_t)(n_pairs / (kLongRun + 1) + 1);                                               \
-    hipLaunchKernelGGL(k_long_measure, dim3((cap_long + 255) / 256), dim3(256), 0, sl, F.seq_bits, n_pairs,           \
-                       (const uint64_t*)sp, d_long_list, (const Counters*)S.d_counters, c->d_long_hdr_[par], kLongRun); \
-    hipLaunchKernelGGL(k_long_bucket, dim3((cap_long + 255) / 256), dim3(256), 0, sl,                                 \
-                       (const unsigned long long*)d_long_list, (const Counters*)S.d_counters, c->d_long_hdr_[par],    \
-                       c->d_long_sorted_[par]);                                                                        \
-    hipLaunchKernelGGL((k_apply_long_lanes<MODE, 6u>), dim3((cap_long / 64 + kLongClasses + 3) / 4), dim3(256), 0, sl, F,   \
-                       (const uint64_t*)sp, (const RayDesc*)S.d_rays, (const float*)S.d_deltas, c->table, c->pool,     \
-                       (const uint32_t*)c->d_label_lut, (const LongHdr*)c->d_long_hdr_[par],                           \
-                       (const unsigned long long*)c->d_long_sorted_[par]);                                             \
-    hipLaunchKernelGGL(k_apply_long<MODE>, dim3(std::min<uint32_t>(lb, 1024u)), dim3(128), 0, sl, F, n_pairs, sp,     \
-                       S.d_rays, S.d_deltas, c->table, c->pool, c->d_label_lut,                                        \
-                       (const unsigned long long*)c->d_long_sorted_[par], (const Counters*)S.d_counters,               \
-                       (const LongHdr*)c->d_long_hdr_[par]);                                                           \
-  } else                                                                                                             \
-  hipLaunchKernelGGL(k_apply_long<MODE>, dim3(lb), dim3(128), 0, sl, F, n_pairs, sp, S.d_rays, S.d_deltas,               \
-                     c->table, c->pool, c->d_label_lut, d_long_list, S.d_counters)
-    switch (c->cfg.color_mode) {
-      case KS_COLOR_MODE_COLOR: KS_LAUNCH_APPLY(KS_COLOR_MODE_COLOR); break;
-      case KS_COLOR_MODE_SEMANTIC: KS_LAUNCH_APPLY(KS_COLOR_MODE_SEMANTIC); break;
-      default: KS_LAUNCH_APPLY(KS_COLOR_MODE_SEMANTIC_PROBABILITY); break;
-    }
-#undef KS_LAUNCH_APPLY
-#undef KS_LAUNCH_APPLY_M
-    if (xlong_beside) {  // S.join stands for both lists
-      HIPCHK(c, hipEventRecord(S.join_x, sx));
-      HIPCHK(c, hipStreamWaitEvent(sl, S.join_x, 0));
-    }
-    if (long_beside) {
-      HIPCHK(c, hipEventRecord(S.join, sl));
-      S.join_recorded = true;
-      // deferred: the tail stream goes on with the next frame's tile initialisation, pair sort and long-run
-      // listing (none of which touches voxels or this frame's buffer set) and waits before its k_apply
-      if (!(set >= 0 && c->pset[set].stages)) c->pending_join = S.join;
-      else HIPCHK(c, hipStreamWaitEvent(st, S.join, 0));
-    }   // (else: the long runs are on the tail stream, and S.tail_done below stands for them too)
-  } else {
-    stage_mark(c, set, 7);
-    stage_mark(c, set, 8);
-    stage_mark(c, set, 9);
-  }
-  finish_prof(n_pairs);
+  // a marcher of ks_integrate_round_exact: the frame's updates leave as records, grouped by the rank that owns their tile
+  const bool marcher = c->shard_export;
+  if (marcher) skip_update_stages(c, set);
+  if ((rc = marcher ? shard_export_frame(c, S, n_pairs, st) : enqueue_update(c, S, st, n_pairs, new_tiles, set))) return rc;
+  finish_prof(c, set, st, n_pairs);
   HIPCHK(c, hipEventRecord(S.tail_done, st));
   S.tail_recorded = true;
-  HIPCHK(c, hipGetLastError());
-  c->owed.n_points += S.n;
-  c->owed.n_valid_points += cnt.n_valid;
-  c->owed.n_rays_cast += cnt.n_rays;
-  c->owed.n_voxel_updates += n_pairs;
-  c->owed.n_blocks_allocated += new_tiles > tiles_before ? new_tiles - tiles_before : 0u;  // (marches of later frames run ahead)
-  if (c->use_bundle_rank && !c->bo_hint_fixed) {
+  if (!marcher) HIPCHK(c, hipGetLastError());
+  owe_stats(c, S, cnt, n_pairs, !marcher && new_tiles > tiles_before ? new_tiles - tiles_before : 0u);  // (marches of later frames run ahead)
+  if (c->use_bundle_rank && !c->bo_hint_fixed && !marcher) {
     // the bundle count the next frames' epochs are launched for: this frame's rays (= bundles of both maps) + 25 % + 2048, decaying slowly
     const uint32_t want = cnt.n_rays + cnt.n_rays / 4u + 2048u;
     const uint32_t cur = c->bo_hint.load(std::memory_order_relaxed);

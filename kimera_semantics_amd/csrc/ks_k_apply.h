@@ -298,7 +298,7 @@ __global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long
 // ------------------------------------------------------------------------------------------
 constexpr uint32_t kRunPer = 4;       // pairs per thread: a tile is 4 x THREADS pairs
 constexpr uint32_t kRunThreads = 512; // eight wavefronts, tiles of 2048 pairs (~ 6 - 12 tasks of 64 runs); what bounds the kernel is how many
-                                      // wavefronts a CU holds against the latency of gather -> record -> steps.  frame_tail launches THREADS = 256
+                                      // wavefronts a CU holds against the latency of gather -> record -> steps.  UpdateLaunch::apply (ks_hip.hip) launches THREADS = 256
                                       // (tiles of 1024): half the LDS and one wavefront per SIMD per workgroup — packs better beside the long-run kernels
 constexpr uint32_t kRunTile = kRunPer * kRunThreads;
 constexpr uint32_t kRunHalo = 32;     // = kLongRun: the longest run this kernel takes

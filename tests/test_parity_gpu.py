@@ -924,3 +924,36 @@ def test_batched_stage_b_equals_unpipelined(method, pipe):
     ub += b.flush().n_voxel_updates
     assert ua == ub
     compare_maps(a, b, exact=True)
+
+
+@pytest.mark.parametrize("pipe", [0, 3])
+@pytest.mark.parametrize("method,big", [(0, (160, 120)), (1, (320, 240))])
+def test_pair_buffer_overflow_repeats_the_emission(method, big, pipe):
+    """A frame whose pairs do not fit the pair buffer sized from the frames before it: the tail grows the buffer and repeats
+    the emission, for both methods, pipelined and not.  The buffer's floor is 2^20 pairs and small frames never raise it, so
+    a frame of more than 2^20 updates is certain to overflow it; max_points is the big frame's size, so no growth of the
+    point buffers is mixed in."""
+    kw = dict(COMMON, method=method)
+    if method == 0:
+        kw["max_consecutive_ray_collisions"] = NO_EARLY_OUT
+    max_points = big[0] * big[1]
+    assert 1.25 * 4 * max_points < 2**20   # whatever the small frames leave as a hint stays under the floor
+    o = O.Oracle(O.default_config(**kw))
+    h = B.HipIntegrator(B.default_config(max_tiles=4096, max_points=max_points, pipeline_frames=pipe, **kw))
+    sc = synth.make_scene("room")
+    frames = [synth.render_frame(sc, synth.trajectory_pose(4 * k), 16, 12, seed=3100 + k) for k in range(4)]
+    frames.insert(2, synth.render_frame(sc, synth.trajectory_pose(0), big[0], big[1], seed=1))
+    fields = ("n_points", "n_valid_points", "n_rays_cast", "n_voxel_updates")
+    tot_o, tot_h = dict.fromkeys(fields, 0), dict.fromkeys(fields, 0)
+    for k, f in enumerate(frames):
+        so = o.integrate(f.T_G_C, f.xyz, f.rgba, f.labels)
+        if k == 2:
+            assert so.n_voxel_updates > 2**20, so.n_voxel_updates
+        for s, tot in ((so, tot_o), (h.integrate(f.T_G_C, f.xyz, f.rgba, f.labels), tot_h)):
+            for name in fields:
+                tot[name] += getattr(s, name)
+    s = h.flush()
+    for name in fields:
+        tot_h[name] += getattr(s, name)
+    assert tot_h == tot_o, (tot_h, tot_o)
+    compare_maps(o, h, exact=True)

@@ -370,10 +370,13 @@ inline std::vector<ProfEntry>& prof_table() { static std::vector<ProfEntry> t; r
 inline void prof_dump() {
   for (const ProfEntry& e : prof_table()) fprintf(stderr, "emu: %9.3f s  %6llu launches  %10llu work-items  %s\n", e.s, e.launches, e.threads, e.name);
 }
-inline void launch_named(const char* name, dim3 grid, dim3 block, const std::function<void()>& body) {
+// EMU_TRACE=1: every launch, before it runs (which kernel was it?), with the ordinal of its stream (creation order, 0 = the
+// null stream), and every stream / event operation that orders work: what was enqueued where, and what waits for what.
+// Two host threads enqueue side by side, so only the order WITHIN a stream is defined: compare traces per stream.
+inline bool tracing() { static const bool trace = getenv("EMU_TRACE") != nullptr; return trace; }
+inline void launch_named(const char* name, dim3 grid, dim3 block, long stream, const std::function<void()>& body) {
   static const bool on = getenv("EMU_PROFILE") != nullptr;
-  static const bool trace = getenv("EMU_TRACE") != nullptr;   // EMU_TRACE=1: every launch, before it runs (which kernel was it?)
-  if (trace) fprintf(stderr, "emu: launch %s grid %u x %u block %u\n", name, grid.x, grid.y, block.x);
+  if (tracing()) fprintf(stderr, "emu: launch %s grid %u x %u block %u stream %ld\n", name, grid.x, grid.y, block.x, stream);
   if (!on) { launch(grid, block, body); return; }
   static bool registered = false;
   if (!registered) { registered = true; atexit(prof_dump); }
@@ -479,10 +482,13 @@ typedef enum { hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2
 // buffer handed from one host thread's launches to another's without such an edge is reported as the race it would be on
 // the GPU.  (Launches of ONE host thread run one after the other here: races between streams fed by the same thread
 // cannot be seen.)
-struct ihipStream_t { std::atomic<long> sync{0}; };
-struct ihipEvent_t { std::atomic<long> sync{0}; };
+struct ihipStream_t { std::atomic<long> sync{0}; long ordinal = 0; };
+struct ihipEvent_t { std::atomic<long> sync{0}; long ordinal = 0; };
 namespace emu {
 inline ihipStream_t g_null_stream;
+inline std::atomic<long> g_stream_ordinals{0}, g_event_ordinals{0};
+inline long ordinal(const ihipStream_t* s) { return s ? s->ordinal : 0; }
+inline long ordinal(const ihipEvent_t* e) { return e ? e->ordinal : 0; }
 inline void touch(ihipStream_t* s) { (s ? s : &g_null_stream)->sync.fetch_add(1, std::memory_order_acq_rel); }
 inline void touch(ihipEvent_t* e) { if (e) e->sync.fetch_add(1, std::memory_order_acq_rel); }
 }  // namespace emu
@@ -517,21 +523,39 @@ struct Ledger {
 };
 inline Ledger g_ledger;
 }  // namespace emu
-inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new ihipStream_t; ++emu::g_ledger.streams; return hipSuccess; }
+inline hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned) { *s = new ihipStream_t; (*s)->ordinal = ++emu::g_stream_ordinals; ++emu::g_ledger.streams; return hipSuccess; }
 inline hipError_t hipStreamDestroy(hipStream_t s) { delete s; --emu::g_ledger.streams; return hipSuccess; }
-inline hipError_t hipStreamSynchronize(hipStream_t s) { emu::touch(s); return hipSuccess; }
-inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) { emu::touch(e); emu::touch(s); return hipSuccess; }
+inline hipError_t hipStreamSynchronize(hipStream_t s) {
+  if (emu::tracing()) fprintf(stderr, "emu: stream_sync stream %ld\n", emu::ordinal(s));
+  emu::touch(s);
+  return hipSuccess;
+}
+inline hipError_t hipStreamWaitEvent(hipStream_t s, hipEvent_t e, unsigned) {
+  if (emu::tracing()) fprintf(stderr, "emu: wait event %ld stream %ld\n", emu::ordinal(e), emu::ordinal(s));
+  emu::touch(e);
+  emu::touch(s);
+  return hipSuccess;
+}
 inline hipError_t hipStreamBeginCapture(hipStream_t, hipStreamCaptureMode) { return hipErrorNotSupported; }
 inline hipError_t hipStreamEndCapture(hipStream_t, hipGraph_t* g) { *g = nullptr; return hipErrorNotSupported; }
 inline hipError_t hipGraphInstantiate(hipGraphExec_t*, hipGraph_t, void*, void*, size_t) { return hipErrorNotSupported; }
 inline hipError_t hipGraphLaunch(hipGraphExec_t, hipStream_t) { return hipErrorNotSupported; }
 inline hipError_t hipGraphDestroy(hipGraph_t) { return hipSuccess; }
 inline hipError_t hipGraphExecDestroy(hipGraphExec_t) { return hipSuccess; }
-inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new ihipEvent_t; ++emu::g_ledger.events; return hipSuccess; }
+inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = new ihipEvent_t; (*e)->ordinal = ++emu::g_event_ordinals; ++emu::g_ledger.events; return hipSuccess; }
 inline hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
 inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; --emu::g_ledger.events; return hipSuccess; }
-inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) { emu::touch(s); emu::touch(e); return hipSuccess; }
-inline hipError_t hipEventSynchronize(hipEvent_t e) { emu::touch(e); return hipSuccess; }
+inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
+  if (emu::tracing()) fprintf(stderr, "emu: record event %ld stream %ld\n", emu::ordinal(e), emu::ordinal(s));
+  emu::touch(s);
+  emu::touch(e);
+  return hipSuccess;
+}
+inline hipError_t hipEventSynchronize(hipEvent_t e) {
+  if (emu::tracing()) fprintf(stderr, "emu: event_sync event %ld\n", emu::ordinal(e));
+  emu::touch(e);
+  return hipSuccess;
+}
 inline hipError_t hipEventElapsedTime(float* ms, hipEvent_t, hipEvent_t) { *ms = 0.f; return hipSuccess; }
 // (exactly `bytes`, 256-byte aligned like the device allocator: a sanitizer build sees every overrun)
 inline void* emu_alloc(size_t bytes) {
@@ -562,11 +586,24 @@ template <typename T> inline hipError_t hipHostMalloc(T** p, size_t bytes, unsig
 inline hipError_t hipFree(void* p) { emu_free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void* p) { emu_free(p); return hipSuccess; }
 inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { emu::touch((ihipStream_t*)nullptr); memmove(d, s, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
-inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st = nullptr) { emu::touch(st); memmove(d, s, n); emu::touch(st); return hipSuccess; }
+inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st = nullptr) {
+  if (emu::tracing()) fprintf(stderr, "emu: memcpy kind %d bytes %zu stream %ld\n", (int)kind, n, emu::ordinal(st));
+  emu::touch(st);
+  memmove(d, s, n);
+  emu::touch(st);
+  return hipSuccess;
+}
 inline hipError_t hipMemset(void* d, int v, size_t n) { emu::touch((ihipStream_t*)nullptr); memset(d, v, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
-inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { emu::touch(st); memset(d, v, n); emu::touch(st); return hipSuccess; }
+inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) {
+  if (emu::tracing()) fprintf(stderr, "emu: memset bytes %zu stream %ld\n", n, emu::ordinal(st));
+  emu::touch(st);
+  memset(d, v, n);
+  emu::touch(st);
+  return hipSuccess;
+}
 typedef void* hipDeviceptr_t;
 inline hipError_t hipMemsetD32Async(hipDeviceptr_t d, int v, size_t count, hipStream_t st = nullptr) {
+  if (emu::tracing()) fprintf(stderr, "emu: memset bytes %zu stream %ld\n", 4 * count, emu::ordinal(st));
   emu::touch(st);
   for (size_t i = 0; i < count; ++i) ((int*)d)[i] = v;
   emu::touch(st);
@@ -579,6 +616,6 @@ inline hipError_t hipPointerGetAttributes(hipPointerAttribute_t* a, const void* 
   return hipSuccess;
 }
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) \
-  (emu::touch(stream), emu::launch_named(#kernel, dim3(grid), dim3(block), [&] { kernel(__VA_ARGS__); }), emu::touch(stream))
+  (emu::touch(stream), emu::launch_named(#kernel, dim3(grid), dim3(block), emu::ordinal(stream), [&] { kernel(__VA_ARGS__); }), emu::touch(stream))
 #define hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, ev0, ev1, flags, ...) \
-  (emu::touch(stream), emu::launch_named(#kernel, dim3(grid), dim3(block), [&] { kernel(__VA_ARGS__); }), emu::touch(stream))
+  (emu::touch(stream), emu::launch_named(#kernel, dim3(grid), dim3(block), emu::ordinal(stream), [&] { kernel(__VA_ARGS__); }), emu::touch(stream))
