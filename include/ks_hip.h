@@ -294,6 +294,49 @@ int ks_mesh_download(ks_ctx* ctx, ks_mesh_block* blocks, size_t cap_blocks, floa
                      uint8_t* labels, size_t cap_vertices);
 int ks_mesh_changed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n);
 
+/* ---- batch ESDF with nearest-surface labels on the device (new: the reference's offline program ends with
+ * EsdfServer::updateEsdfBatch on the host layers, kimera_semantics_rosbag.cpp:147-167; here the distances are made where
+ * the voxels are) ----
+ * The contract is DESIGN.md, section "ESDF" (no parity with Voxblox's EsdfIntegrator is claimed: it is not part of the
+ * reference tree and its result depends on queue order).  In short, with R = (int)ceilf(max_distance_m / voxel_size) <= 255:
+ * a voxel of a resident tile with weight >= min_weight is OBSERVED; an observed voxel with |distance| < min_distance_m is a
+ * SITE (Voxblox's fixed band) and keeps its TSDF distance and its own arg-max label.  Every other observed voxel v takes the
+ * minimum, over the sites u of v's sign (distance < 0: negative) with |u - v| <= R on every axis in voxel indices, of the
+ * key  d2 << 40 | bits(|distance_u|) << 8 | label_u  (d2 = squared index distance): the nearest site by centre distance,
+ * ties to the smaller |distance|, then to the smaller label.  Its distance is
+ * sign * fminf(max_distance_m, voxel_size * sqrtf((float)d2) + |distance_u|) (one multiply, one add, no contraction) and its
+ * nearest label label_u; without such a site sign * max_distance_m and label 255.  Anything else is {0.0f, flags 0, label
+ * 255}.  flags = observed | fixed << 1.  A label of 255 in the map (never updated) shows as 0, as in ks_download_blocks.
+ * ks_esdf_update   computes the ESDF of the map as it is after the frames in flight have completed and stores it beside the
+ *                  tiles (8 bytes per voxel): a SNAPSHOT — later integrate calls do not change it, tiles that join the map
+ *                  later read as default records, ks_clear / ks_clear_voxels drop it.  The work space is a dense box of
+ *                  voxels, the bounding box of the resident tiles (32 bytes per voxel plus 4 per tile); when it exceeds
+ *                  max_workspace_bytes the call returns KS_ERR_UNSUPPORTED with stats->workspace_bytes and
+ *                  stats->box_voxels filled in.  With use_region only the voxels of the host-layout blocks region_min ..
+ *                  region_max (inclusive) get results — every other voxel holds a default record — and the box is the
+ *                  region's tiles dilated by ceil(R / 8) tiles, clipped to that bounding box: sites outside the region
+ *                  still count.  stats: voxels_observed / voxels_fixed among the voxels that got results, voxels_clamped =
+ *                  observed voxels outside the band whose |distance| is max_distance_m.
+ * ks_esdf_download_blocks   records of n host-layout blocks, vps^3 each in x + vps * (y + vps * z) order.
+ * ks_esdf_query    the record of the voxel that contains each point (the point-to-voxel rule of the integrator for a ray's
+ *                  end point); no interpolation.
+ * Errors: KS_ERR_INVALID_ARG (a parameter that is not a finite positive number, R > 255, region_min > region_max, download
+ * or query before any update), KS_ERR_UNSUPPORTED (work space; a marcher context of ks_integrate_round_exact), KS_ERR_HIP.
+ * Multi-GPU: each context computes over the tiles it holds; seams between the tiles of different owners are not handled. */
+typedef struct ks_esdf_config {
+  float min_weight, min_distance_m, max_distance_m;
+  int32_t use_region;
+  int32_t region_min[3], region_max[3];
+  uint64_t max_workspace_bytes;
+} ks_esdf_config;
+typedef struct ks_esdf_stats { uint64_t voxels_observed, voxels_fixed, voxels_clamped, box_voxels[3], workspace_bytes; } ks_esdf_stats;
+#define KS_ESDF_RECORD_BYTES 8 /* { f32 distance; u8 flags; u8 nearest_label; u8 pad[2] } */
+int ks_esdf_default_config(ks_esdf_config* cfg); /* 1e-6, 0.2 m, 2.0 m, no region, 8 GiB */
+int ks_esdf_update(ks_ctx* ctx, const ks_esdf_config* cfg, ks_esdf_stats* stats /* may be NULL */);
+int ks_esdf_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, void* out /* n * vps^3 * 8 B, host block layout */);
+int ks_esdf_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, float* distance, uint8_t* flags,
+                  uint8_t* label /* any may be NULL */);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

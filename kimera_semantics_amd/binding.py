@@ -38,6 +38,7 @@ ABI_SYMBOLS = [
     "ks_debug_radix_sort", "ks_synchronize", "ks_flush", "ks_stream",
     "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
+    "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
 ]
 
 
@@ -88,6 +89,20 @@ class KsMeshStats(C.Structure):
 MESH_BLOCK_DTYPE = np.dtype([("block", "<i4", (3,)), ("first_vertex", "<u4"), ("n_vertices", "<u4")])
 
 
+class KsEsdfConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("min_distance_m", C.c_float), ("max_distance_m", C.c_float), ("use_region", C.c_int32),
+                ("region_min", C.c_int32 * 3), ("region_max", C.c_int32 * 3), ("max_workspace_bytes", C.c_uint64)]
+
+
+class KsEsdfStats(C.Structure):
+    _fields_ = [("voxels_observed", C.c_uint64), ("voxels_fixed", C.c_uint64), ("voxels_clamped", C.c_uint64),
+                ("box_voxels", C.c_uint64 * 3), ("workspace_bytes", C.c_uint64)]
+
+
+# KS_ESDF_RECORD_BYTES = 8; flags = observed | fixed << 1; label 255 = no site within reach (or a default record)
+ESDF_DTYPE = np.dtype([("distance", "<f4"), ("flags", "u1"), ("label", "u1"), ("pad", "u1", (2,))])
+
+
 class KsProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("frames", C.c_uint64),
                 ("updates", C.c_uint64), ("points", C.c_uint64), ("apply_kernel_ms", C.c_double),
@@ -99,7 +114,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -169,6 +184,10 @@ def lib():
         L.ks_mesh_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.ks_mesh_download.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.c_size_t]
         L.ks_mesh_changed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_esdf_default_config.argtypes = [C.POINTER(KsEsdfConfig)]
+        L.ks_esdf_update.argtypes = [vp, C.POINTER(KsEsdfConfig), C.POINTER(KsEsdfStats)]
+        L.ks_esdf_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_esdf_query.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         _lib = L
     return _lib
 
@@ -340,6 +359,52 @@ class HipIntegrator:
         out = np.zeros((n.value, 3), dtype=np.int32)
         if n.value:
             self._chk(lib().ks_mesh_changed_blocks(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def esdf_update(self, region=None, **cfg) -> dict:
+        """ks_esdf_update: computes the batch ESDF of the map as it is now and stores it on the device.  cfg: min_weight,
+        min_distance_m, max_distance_m, max_workspace_bytes; region = (block_min[3], block_max[3]), inclusive.  Returns the
+        stats; a KsError raised here carries them too (stats: the work space a refused call would have needed)."""
+        ec, st = KsEsdfConfig(), KsEsdfStats()
+        lib().ks_esdf_default_config(C.byref(ec))
+        for k, v in cfg.items():
+            if k not in ("min_weight", "min_distance_m", "max_distance_m", "max_workspace_bytes"):
+                raise AttributeError(k)
+            setattr(ec, k, v)
+        if region is not None:
+            ec.use_region = 1
+            for a in range(3):
+                ec.region_min[a], ec.region_max[a] = int(region[0][a]), int(region[1][a])
+        rc = lib().ks_esdf_update(self._h, C.byref(ec), C.byref(st))
+        stats = {k: ([int(v) for v in getattr(st, k)] if k == "box_voxels" else int(getattr(st, k))) for k, _ in KsEsdfStats._fields_}
+        if rc != 0:
+            err = KsError(rc, lib().ks_last_error(self._h).decode())
+            err.stats = stats
+            raise err
+        return stats
+
+    def esdf(self, region=None, **cfg):
+        """Batch ESDF with nearest-surface labels of the whole map: (block_indices (N, 3) i32 ascending, records (N, vps^3)
+        ESDF_DTYPE in host block layout, stats).  The contract is DESIGN.md, section "ESDF"."""
+        stats = self.esdf_update(region=region, **cfg)
+        idx = self.block_indices()
+        return idx, self.esdf_blocks(idx), stats
+
+    def esdf_blocks(self, indices) -> np.ndarray:
+        """Records of the stored ESDF (the snapshot of the last esdf() / esdf_update()) for host-layout blocks."""
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((len(indices), self.vps ** 3), dtype=ESDF_DTYPE)
+        self._chk(lib().ks_esdf_download_blocks(self._h, _ptr(indices), len(indices), _ptr(out)))
+        return out
+
+    def esdf_query(self, xyz) -> np.ndarray:
+        """The stored record of the voxel that contains each world point (nearest voxel, no interpolation): (n,) ESDF_DTYPE."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        n = len(xyz)
+        d, f, l = np.zeros(n, np.float32), np.zeros(n, np.uint8), np.zeros(n, np.uint8)
+        self._chk(lib().ks_esdf_query(self._h, _ptr(xyz), n, _ptr(d), _ptr(f), _ptr(l)))
+        out = np.zeros(n, dtype=ESDF_DTYPE)
+        out["distance"], out["flags"], out["label"] = d, f, l
         return out
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----

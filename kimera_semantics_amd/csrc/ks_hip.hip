@@ -69,6 +69,7 @@ using namespace ksd;
 #include "ks_k_shard_merged.h"
 #include "ks_k_io.h"
 #include "ks_k_mesh.h"
+#include "ks_k_esdf.h"
 
 using namespace ksk;
 
@@ -483,6 +484,17 @@ struct ks_ctx {
   std::vector<ks_mesh_block> mesh_dir;     // one entry per element of mesh_blocks as of the last update (n_vertices may be 0)
   std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
   DevBuf<uint8_t> d_mesh_buf[10];          // grow-only scratch of the passes (mesh_scratch)
+  // ks_esdf_update (ks_k_esdf.h).  The store holds 512 records per tile slot, a snapshot of the map at the last update;
+  // everything grows only.
+  DevBuf<EsdfRecord> esdf_store;           // [esdf_tiles][512]
+  DevBuf<uint64_t> esdf_keys[2];           // the two key buffers of the passes: [sign][box voxel] each
+  DevBuf<uint32_t> esdf_slots;             // dense slot grid of the box
+  DevBuf<unsigned long long> esdf_counters;
+  DevBuf<EsdfRecord> esdf_out;             // staging of download and query
+  DevBuf<int32_t> esdf_idx;
+  DevBuf<float> esdf_xyz;
+  bool esdf_valid = false;                 // an update has run since the map was last cleared
+  uint32_t esdf_tiles = 0;                 // tiles that were resident at that update
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -3076,6 +3088,215 @@ int ks_mesh_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
   return KS_OK;
 }
 
+// ---- batch ESDF (ks_k_esdf.h) ----------------------------------------------------------------------------
+int ks_esdf_default_config(ks_esdf_config* e) {
+  if (!e) return KS_ERR_INVALID_ARG;
+  std::memset(e, 0, sizeof(*e));
+  e->min_weight = 1e-6f;        // Voxblox's EsdfIntegrator::Config
+  e->min_distance_m = 0.2f;
+  e->max_distance_m = 2.0f;
+  e->max_workspace_bytes = 8ull << 30;
+  return KS_OK;
+}
+
+int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
+  if (!c || !e) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  auto positive = [](float v) { return v > 0.0f && std::isfinite(v); };
+  if (!positive(e->min_weight) || !positive(e->min_distance_m) || !positive(e->max_distance_m)) {
+    c->err = "ks_esdf_update: min_weight, min_distance_m and max_distance_m must be finite positive numbers";
+    return KS_ERR_INVALID_ARG;
+  }
+  const float reach = ceilf(e->max_distance_m / c->cfg.voxel_size);
+  if (!(reach <= (float)kEsdfMaxR)) {
+    c->err = "ks_esdf_update: max_distance_m reaches further than 255 voxels";
+    return KS_ERR_INVALID_ARG;
+  }
+  const int R = (int)reach;
+  if (e->use_region)
+    for (int a = 0; a < 3; ++a)
+      if (e->region_min[a] > e->region_max[a]) {
+        c->err = "ks_esdf_update: region_min exceeds region_max";
+        return KS_ERR_INVALID_ARG;
+      }
+  if (c->shard_export) {
+    c->err = "ks_esdf_update: a marcher context of ks_integrate_round_exact holds no voxel data";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->tiles_initialised;
+  int rc;
+  // 1) the bounding box of the resident tiles, in tiles; with a region: its tiles dilated by ceil(R / 8), clipped to that box
+  std::vector<uint64_t> keys(nt);
+  if (nt) HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  auto tile_of = [](uint64_t k, int t[3]) {
+    t[0] = (int)((k >> 36) & 0x3ffffu) - kTileBias;
+    t[1] = (int)((k >> 18) & 0x3ffffu) - kTileBias;
+    t[2] = (int)(k & 0x3ffffu) - kTileBias;
+  };
+  int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};   // tiles [lo, hi]
+  for (uint32_t s = 0; s < nt; ++s) {
+    int t[3];
+    tile_of(keys[s], t);
+    for (int a = 0; a < 3; ++a) {
+      if (s == 0 || t[a] < lo[a]) lo[a] = t[a];
+      if (s == 0 || t[a] > hi[a]) hi[a] = t[a];
+    }
+  }
+  int64_t r0[3], r1[3];   // voxels [r0, r1) that get results, in world voxel indices
+  for (int a = 0; a < 3; ++a) {
+    r0[a] = (int64_t)lo[a] * 8;
+    r1[a] = ((int64_t)hi[a] + 1) * 8;
+  }
+  if (e->use_region && nt) {
+    const int tpb = c->cfg.voxels_per_side / 8, grow = (R + 7) / 8;
+    for (int a = 0; a < 3; ++a) {
+      const int64_t t0 = (int64_t)e->region_min[a] * tpb, t1 = ((int64_t)e->region_max[a] + 1) * tpb - 1;   // tiles [t0, t1]
+      r0[a] = std::max<int64_t>(r0[a], t0 * 8);
+      r1[a] = std::min<int64_t>(r1[a], (t1 + 1) * 8);
+      lo[a] = (int)std::max<int64_t>(lo[a], t0 - grow);
+      hi[a] = (int)std::min<int64_t>(hi[a], t1 + grow);
+    }
+  }
+  bool empty = nt == 0;
+  for (int a = 0; a < 3; ++a) empty = empty || hi[a] < lo[a] || r1[a] <= r0[a];
+  uint64_t nbt[3] = {0, 0, 0};   // tiles of the box
+  if (!empty)
+    for (int a = 0; a < 3; ++a) nbt[a] = (uint64_t)(hi[a] - lo[a] + 1);
+  const uint64_t box_tiles = nbt[0] * nbt[1] * nbt[2], box_voxels = box_tiles * 512;
+  const uint64_t workspace = box_voxels * 32 + box_tiles * 4;   // two key buffers of two planes of 8 bytes; the slot grid
+  if (stats) {
+    for (int a = 0; a < 3; ++a) stats->box_voxels[a] = nbt[a] * 8;
+    stats->workspace_bytes = workspace;
+  }
+  if (workspace > e->max_workspace_bytes) {
+    c->err = "ks_esdf_update: the dense box of " + std::to_string(nbt[0] * 8) + " x " + std::to_string(nbt[1] * 8) + " x " +
+             std::to_string(nbt[2] * 8) + " voxels needs " + std::to_string(workspace) + " bytes of work space, more than max_workspace_bytes = " +
+             std::to_string(e->max_workspace_bytes) + ": raise it, or compute part of the map with use_region";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (nbt[0] * 8 >= (1ull << 20) || nbt[1] * 8 >= 65536ull || nbt[2] * 8 >= 65536ull) {   // launch grid limits, far beyond any work space
+    c->err = "ks_esdf_update: the box is too large for one call; use use_region";
+    return KS_ERR_UNSUPPORTED;
+  }
+  // 2) the store: default records for every resident tile
+  c->esdf_valid = false;   // (a failure below leaves no half-written snapshot readable)
+  if ((rc = c->esdf_store.reserve(c, (size_t)nt * kTileVoxels, ((size_t)nt + nt / 2 + 64) * kTileVoxels))) return rc;
+  if ((rc = c->esdf_counters.reserve(c, 3, 3))) return rc;
+  HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
+  if (nt)
+    hipLaunchKernelGGL(k_esdf_fill, dim3((uint32_t)(((size_t)nt * kTileVoxels + 255) / 256)), dim3(256), 0, st, c->esdf_store.get(),
+                       (size_t)nt * kTileVoxels);
+  unsigned long long counts[3] = {0, 0, 0};
+  if (!empty) {
+    // 3) the dense slot grid of the box
+    std::vector<uint32_t> grid(box_tiles, 0xffffffffu);
+    for (uint32_t s = 0; s < nt; ++s) {
+      int t[3];
+      tile_of(keys[s], t);
+      if (t[0] < lo[0] || t[0] > hi[0] || t[1] < lo[1] || t[1] > hi[1] || t[2] < lo[2] || t[2] > hi[2]) continue;
+      grid[((size_t)(t[2] - lo[2]) * nbt[1] + (size_t)(t[1] - lo[1])) * nbt[0] + (size_t)(t[0] - lo[0])] = s;
+    }
+    if ((rc = c->esdf_slots.reserve(c, box_tiles, box_tiles + box_tiles / 2))) return rc;
+    for (auto& K : c->esdf_keys)
+      if ((rc = K.reserve(c, 2 * box_voxels, 2 * box_voxels + box_voxels / 2))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->esdf_slots, grid.data(), box_tiles * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    EsdfBox B{};
+    B.nx = (int)(nbt[0] * 8);
+    B.ny = (int)(nbt[1] * 8);
+    B.nz = (int)(nbt[2] * 8);
+    const int org[3] = {lo[0] * 8, lo[1] * 8, lo[2] * 8}, dim[3] = {B.nx, B.ny, B.nz};
+    for (int a = 0; a < 3; ++a) {
+      B.r0[a] = (int)std::max<int64_t>(r0[a] - org[a], 0);
+      B.r1[a] = (int)std::min<int64_t>(r1[a] - org[a], dim[a]);
+    }
+    B.R = R;
+    B.voxel_size = c->cfg.voxel_size;
+    B.min_weight = e->min_weight;
+    B.min_distance = e->min_distance_m;
+    B.max_distance = e->max_distance_m;
+    B.slots = c->esdf_slots;
+    const uint32_t along = 16 * kEsdfPer;
+    hipLaunchKernelGGL(k_esdf_x, dim3((uint32_t)((B.nx + 63) / 64), (uint32_t)((B.ny + 3) / 4), (uint32_t)B.nz), dim3(256), 0, st, B, c->pool,
+                       c->esdf_keys[0].get());
+    hipLaunchKernelGGL(k_esdf_axis<0>, dim3((uint32_t)((B.nx + 15) / 16), (uint32_t)((B.ny + along - 1) / along), (uint32_t)B.nz), dim3(256), 0, st,
+                       B, c->pool, (const uint64_t*)c->esdf_keys[0].get(), c->esdf_keys[1].get(), (EsdfRecord*)nullptr,
+                       (unsigned long long*)nullptr);
+    hipLaunchKernelGGL(k_esdf_axis<1>, dim3((uint32_t)((B.nx + 15) / 16), (uint32_t)((B.nz + along - 1) / along), (uint32_t)B.ny), dim3(256), 0, st,
+                       B, c->pool, (const uint64_t*)c->esdf_keys[1].get(), (uint64_t*)nullptr, c->esdf_store.get(), c->esdf_counters.get());
+    HIPCHK(c, hipMemcpyAsync(counts, c->esdf_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->esdf_valid = true;
+  c->esdf_tiles = nt;
+  if (stats) {
+    stats->voxels_observed = counts[0];
+    stats->voxels_fixed = counts[1];
+    stats->voxels_clamped = counts[2];
+  }
+  return KS_OK;
+}
+
+static int esdf_ready(ks_ctx* c, const char* who) {
+  if (c->esdf_valid) return KS_OK;
+  c->err = std::string(who) + ": no ESDF is stored (ks_esdf_update has not run since the map was created or cleared)";
+  return KS_ERR_INVALID_ARG;
+}
+
+int ks_esdf_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, void* out) {
+  if (!c || (n && (!idx || !out))) return KS_ERR_INVALID_ARG;
+  if (int rc = esdf_ready(c, "ks_esdf_download_blocks")) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const int vps = c->cfg.voxels_per_side;
+  const size_t nv = (size_t)vps * vps * vps;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(64) << 20) / (nv * sizeof(EsdfRecord))), 65535);   // <= 64 MiB staged at a time
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->esdf_out.reserve(c, m_max * nv, m_max * nv))) return rc;
+  if ((rc = c->esdf_idx.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->esdf_idx, idx + 3 * off, m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_esdf_download, dim3((uint32_t)((nv + 255) / 256), (uint32_t)m), dim3(256), 0, c->stream, c->table,
+                       (const EsdfRecord*)c->esdf_store.get(), c->esdf_tiles, (const int32_t*)c->esdf_idx.get(), vps, c->esdf_out.get());
+    HIPCHK(c, hipMemcpyAsync((uint8_t*)out + off * nv * sizeof(EsdfRecord), c->esdf_out, m * nv * sizeof(EsdfRecord), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_esdf_query(ks_ctx* c, const float* xyz, size_t n, float* distance, uint8_t* flags, uint8_t* label) {
+  if (!c || (n && !xyz)) return KS_ERR_INVALID_ARG;
+  if (int rc = esdf_ready(c, "ks_esdf_query")) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const size_t chunk = size_t(1) << 22;
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->esdf_out.reserve(c, m_max, m_max))) return rc;
+  if ((rc = c->esdf_xyz.reserve(c, m_max * 3, m_max * 3))) return rc;
+  std::vector<EsdfRecord> rec(m_max);
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->esdf_xyz, xyz + 3 * off, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_esdf_query, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, (const EsdfRecord*)c->esdf_store.get(),
+                       c->esdf_tiles, (const float*)c->esdf_xyz.get(), m, c->voxel_size_inv, c->esdf_out.get());
+    HIPCHK(c, hipMemcpyAsync(rec.data(), c->esdf_out, m * sizeof(EsdfRecord), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (size_t i = 0; i < m; ++i) {
+      if (distance) distance[off + i] = rec[i].distance;
+      if (flags) flags[off + i] = (uint8_t)(rec[i].tail & 0xffu);
+      if (label) label[off + i] = (uint8_t)((rec[i].tail >> 8) & 0xffu);
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
 // ---- voxel-level host sync -------------------------------------------------------------------------------
 // Device-side address of a host allocation the GPU can write (hipHostMalloc'ed: ks_host_alloc), else nullptr.
 static void* device_view_of_pinned(void* p) {
@@ -3768,6 +3989,8 @@ static void mesh_reset(ks_ctx* c) {
   c->mesh_dir.clear();
   c->mesh_changed.clear();
   c->mesh_tiles_seen = 0;
+  c->esdf_valid = false;   // the ESDF is a snapshot of the map that goes
+  c->esdf_tiles = 0;
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {

@@ -181,6 +181,35 @@ int main(int argc, char** argv) {
     std::printf("adapter_demo: updateMesh %.3f ms, %u blocks, %zu triangles\n", ms, n_mesh_blocks, n_vertices / 3);
   }
 
+  // KS_DEMO_ESDF=<file>: the batch ESDF with nearest-surface labels, made on the device without any layer sync (updateEsdf,
+  // min_distance_m 0.1, max_distance_m 0.4), written as
+  // { u32 blocks, u32 voxels_per_side; per block: i32 index[3], vps^3 x { f32 distance, u8 flags, u8 nearest_label, u8 pad[2] } }
+  if (const char* esdf_path = std::getenv("KS_DEMO_ESDF")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->updateEsdf(eo, &esdf);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* ef = std::fopen(esdf_path, "wb");
+    if (!ef) return 9;
+    const uint32_t n_esdf_blocks = esdf.size(), esdf_vps = tsdf_layer.voxels_per_side();
+    std::fwrite(&n_esdf_blocks, 4, 1, ef);
+    std::fwrite(&esdf_vps, 4, 1, ef);
+    for (const auto& eb : esdf) {
+      const int32_t idx[3] = {eb.index.x(), eb.index.y(), eb.index.z()};
+      std::fwrite(idx, 4, 3, ef);
+      std::fwrite(eb.voxels.data(), sizeof(eb.voxels[0]), eb.voxels.size(), ef);
+    }
+    std::fclose(ef);
+    const ks_esdf_stats& es = hip->lastEsdfStats();
+    std::printf("adapter_demo: updateEsdf %.3f ms, %u blocks, %llu observed voxels, %llu in the band\n", ms, n_esdf_blocks,
+                (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
+  }
+
   vxb::BlockIndexList blocks;
   tsdf_layer.getAllAllocatedBlocks(&blocks);
   std::sort(blocks.begin(), blocks.end(), [](const vxb::BlockIndex& a, const vxb::BlockIndex& b) {

@@ -261,6 +261,38 @@ bool HipSemanticTsdfIntegrator::updateMesh(bool only_mesh_updated_blocks, std::v
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::updateEsdf(const EsdfOptions& options, std::vector<EsdfBlock>* out) {
+  CHECK_NOTNULL(out);
+  out->clear();
+  static_assert(sizeof(EsdfVoxel) == KS_ESDF_RECORD_BYTES, "ESDF record layout");
+  ks_esdf_config ec;
+  ks_esdf_default_config(&ec);
+  ec.min_weight = options.min_weight;
+  ec.min_distance_m = options.min_distance_m;
+  ec.max_distance_m = options.max_distance_m;
+  ec.max_workspace_bytes = options.max_workspace_bytes;
+  ec.use_region = options.use_region ? 1 : 0;
+  for (int a = 0; a < 3; ++a) {
+    ec.region_min[a] = options.region_min[a];
+    ec.region_max[a] = options.region_max[a];
+  }
+  check(ks_esdf_update(ctx_, &ec, &last_esdf_stats_), "ks_esdf_update");
+  size_t n = 0;
+  check(ks_get_block_indices(ctx_, nullptr, 0, &n), "ks_get_block_indices");
+  if (n == 0) return false;
+  std::vector<int32_t> idx(3 * n);
+  check(ks_get_block_indices(ctx_, idx.data(), n, &n), "ks_get_block_indices");
+  const size_t vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
+  std::vector<EsdfVoxel> all(n * nv);
+  check(ks_esdf_download_blocks(ctx_, idx.data(), n, all.data()), "ks_esdf_download_blocks");
+  out->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    (*out)[i].index = vxb::BlockIndex(idx[3 * i], idx[3 * i + 1], idx[3 * i + 2]);
+    (*out)[i].voxels.assign(all.begin() + i * nv, all.begin() + (i + 1) * nv);
+  }
+  return true;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

@@ -110,6 +110,31 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// server ("Mesh without a layer sync").
   bool updateMesh(bool only_mesh_updated_blocks, std::vector<MeshBlock>* changed);
   const ks_mesh_stats& lastMeshStats() const { return last_mesh_stats_; }
+
+  /// Batch ESDF with nearest-surface labels (ks_esdf_update; the contract is DESIGN.md, "ESDF") in this adapter's own types:
+  /// there is no Voxblox EsdfVoxel behind it and no parity with vxb::EsdfIntegrator is claimed.  Defaults as
+  /// vxb::EsdfIntegrator::Config.  With use_region only the blocks region_min .. region_max (inclusive) get results.
+  struct EsdfOptions {
+    float min_weight = 1e-6f, min_distance_m = 0.2f, max_distance_m = 2.0f;
+    uint64_t max_workspace_bytes = 8ull << 30;
+    bool use_region = false;
+    vxb::BlockIndex region_min = vxb::BlockIndex(0, 0, 0), region_max = vxb::BlockIndex(0, 0, 0);
+  };
+  struct EsdfVoxel {         ///< one record of ks_esdf_download_blocks
+    float distance;          ///< signed, |distance| <= max_distance_m; a site keeps its TSDF distance
+    uint8_t flags;           ///< observed | fixed << 1
+    uint8_t nearest_label;   ///< label of the nearest surface voxel; 255: none within reach (or not observed)
+    uint8_t pad[2];
+  };
+  struct EsdfBlock {
+    vxb::BlockIndex index;
+    std::vector<EsdfVoxel> voxels;   ///< voxels_per_side^3, x + vps * (y + vps * z)
+  };
+  /// Computes the ESDF of the whole map ON THE DEVICE, as it is after the frames in flight, and hands back every block of
+  /// the map (ascending by x, y, z).  Needs NO syncLayers().  Batch only: what EsdfServer::updateEsdfBatch does at the end
+  /// of the reference's offline program ("ESDF").  Returns true when `out` is not empty.
+  bool updateEsdf(const EsdfOptions& options, std::vector<EsdfBlock>* out);
+  const ks_esdf_stats& lastEsdfStats() const { return last_esdf_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -122,6 +147,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   DeviceOptions options_;
   ks_frame_stats last_stats_{};
   ks_mesh_stats last_mesh_stats_{};
+  ks_esdf_stats last_esdf_stats_{};
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand
   struct Staging {

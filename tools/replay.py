@@ -3,9 +3,10 @@
 (kimera_semantics_ros/src/kimera_semantics_rosbag.cpp:83-141) for the path this repository accelerates: read a ROS1
 bag (or generate the synthetic stand-in), compose T_G_C = T_G_B * T_B_C per depth image, integrate depth + labels on
 the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  The semantic mesh — what the reference's executable
-generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every; ESDF and
-map saving stay on the host side of the drop-in boundary (out of scope).
-  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5]
+generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every, and the
+batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf; map saving stays on the host side of the
+drop-in boundary (out of scope).
+  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -37,6 +38,10 @@ def main():
     ap.add_argument("--pipeline-frames", type=int, default=4)
     ap.add_argument("--mesh", metavar="OUT.ply", help="extract the semantic mesh at the end of the replay and write it (binary PLY with a label property)")
     ap.add_argument("--mesh-every", type=int, default=0, metavar="N", help="refresh the mesh on the device (only_stale) every N frames")
+    ap.add_argument("--esdf", metavar="OUT.npz", help="compute the batch ESDF with nearest-surface labels at the end of the replay and write it "
+                    "(block_indices (N, 3), distance / flags / label (N, vps^3) in host block layout, voxel_size, voxels_per_side)")
+    ap.add_argument("--esdf-max-distance", type=float, default=2.0, metavar="M")
+    ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
     a = ap.parse_args()
     if a.bag:
         seq = FS.read_rosbag(a.bag, a.depth_topic, a.semantic_topic, a.camera_info_topic, a.sensor_frame, a.base_link_frame, a.world_frame)
@@ -91,6 +96,14 @@ def main():
         write_ply(a.mesh, m)
         print(f"mesh: {m.n_triangles} triangles in {len(m.blocks)} blocks, labels {sorted(set(m.labels.tolist()))}, "
               f"{t_mesh * 1e3:.2f} ms (extraction + download) -> {a.mesh}")
+    if a.esdf:
+        t1 = time.perf_counter()
+        idx, rec, st = integ.esdf(min_distance_m=a.esdf_min_distance, max_distance_m=a.esdf_max_distance)
+        t_esdf = time.perf_counter() - t1
+        np.savez_compressed(a.esdf, block_indices=idx, distance=rec["distance"], flags=rec["flags"], label=rec["label"],
+                            voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+        print(f"esdf: {st['voxels_observed']} observed voxels ({st['voxels_fixed']} in the band, {st['voxels_clamped']} at +-{a.esdf_max_distance} m), "
+              f"box {st['box_voxels']}, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_esdf * 1e3:.2f} ms (update + download) -> {a.esdf}")
 
 
 if __name__ == "__main__":
