@@ -308,8 +308,9 @@ int ks_mesh_changed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n)
  * nearest label label_u; without such a site sign * max_distance_m and label 255.  Anything else is {0.0f, flags 0, label
  * 255}.  flags = observed | fixed << 1.  A label of 255 in the map (never updated) shows as 0, as in ks_download_blocks.
  * ks_esdf_update   computes the ESDF of the map as it is after the frames in flight have completed and stores it beside the
- *                  tiles (8 bytes per voxel): a SNAPSHOT — later integrate calls do not change it, tiles that join the map
- *                  later read as default records, ks_clear / ks_clear_voxels drop it.  The work space is a dense box of
+ *                  tiles (8 bytes per voxel).  Later integrate calls do not change the stored ESDF by themselves, and tiles
+ *                  that join the map read as default records, until ks_esdf_refresh (below) brings it up to date;
+ *                  ks_clear / ks_clear_voxels drop it.  The work space is a dense box of
  *                  voxels, the bounding box of the resident tiles (32 bytes per voxel plus 4 per tile); when it exceeds
  *                  max_workspace_bytes the call returns KS_ERR_UNSUPPORTED with stats->workspace_bytes and
  *                  stats->box_voxels filled in.  With use_region only the voxels of the host-layout blocks region_min ..
@@ -317,6 +318,28 @@ int ks_mesh_changed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n)
  *                  region's tiles dilated by ceil(R / 8) tiles, clipped to that bounding box: sites outside the region
  *                  still count.  stats: voxels_observed / voxels_fixed among the voxels that got results, voxels_clamped =
  *                  observed voxels outside the band whose |distance| is max_distance_m.
+ * ks_esdf_refresh  brings the stored ESDF up to date: afterwards it is, byte for byte and for every voxel of every resident
+ *                  tile, what ks_esdf_update would store now with the configuration (min_weight, the two distances,
+ *                  use_region and the region) of the update that made it — the refresh takes no ESDF parameters and so cannot
+ *                  disagree with the store.  Every write to a tile's voxels (integrate, shard apply, upload, merge, reset)
+ *                  marks the tile stale for the ESDF; the mark is a bit of its own, so the mesher (only_stale) and the two host
+ *                  syncs neither consume it nor are consumed by it.  With g = ceil(R / 8), S = the resident tiles marked
+ *                  stale and A = the resident tiles (inside the stored region, if any) whose tile index differs from one of
+ *                  S by at most g on every axis: whole tiles of A are recomputed and nothing else is written (sufficient
+ *                  because |u - v| <= R in voxels puts the tiles of u and v within floor((R + 7) / 8) = g; a record that did
+ *                  not need it comes out with the same bytes).  Sites are read from every resident tile within 2 g of S.
+ *                  A successful ks_esdf_update or ks_esdf_refresh clears the marks of all resident tiles; a call that fails,
+ *                  a refusal for work space included, clears none and leaves the store as it was.  Work space: 8 KiB per
+ *                  listed tile position of passes x and y (A dilated by g along z, and along y and z, less the positions
+ *                  that can hold no key) plus 8 bytes per listed position and 4 per tile of A — it follows the stale tiles,
+ *                  never a bounding box, and there is no fallback to the dense path: beyond max_workspace_bytes (0: that of
+ *                  the stored update) the call returns KS_ERR_UNSUPPORTED with the stats filled in.  stats: tiles_stale = |S|,
+ *                  tiles_recomputed = |A|, tiles_total = resident tiles; the three voxel counts describe the whole stored
+ *                  ESDF after the call and equal what a from-scratch ks_esdf_update would report.  With nothing stale
+ *                  nothing is launched over the map.  Errors: KS_ERR_INVALID_ARG (no stored ESDF), KS_ERR_UNSUPPORTED (work
+ *                  space; a marcher context), KS_ERR_HIP (as in ks_esdf_update: no ESDF is stored afterwards).
+ * ks_esdf_changed_blocks   the host-layout blocks that hold a tile the LAST ks_esdf_refresh recomputed, ascending by
+ *                  (x, y, z) like ks_get_block_indices; empty after a ks_esdf_update until the next refresh.
  * ks_esdf_download_blocks   records of n host-layout blocks, vps^3 each in x + vps * (y + vps * z) order.
  * ks_esdf_query    the record of the voxel that contains each point (the point-to-voxel rule of the integrator for a ray's
  *                  end point); no interpolation.
@@ -333,6 +356,13 @@ typedef struct ks_esdf_stats { uint64_t voxels_observed, voxels_fixed, voxels_cl
 #define KS_ESDF_RECORD_BYTES 8 /* { f32 distance; u8 flags; u8 nearest_label; u8 pad[2] } */
 int ks_esdf_default_config(ks_esdf_config* cfg); /* 1e-6, 0.2 m, 2.0 m, no region, 8 GiB */
 int ks_esdf_update(ks_ctx* ctx, const ks_esdf_config* cfg, ks_esdf_stats* stats /* may be NULL */);
+typedef struct ks_esdf_refresh_stats {
+  uint64_t tiles_stale, tiles_recomputed, tiles_total;
+  uint64_t voxels_observed, voxels_fixed, voxels_clamped; /* of the whole stored ESDF after the call */
+  uint64_t workspace_bytes;
+} ks_esdf_refresh_stats; /* 56 bytes */
+int ks_esdf_refresh(ks_ctx* ctx, uint64_t max_workspace_bytes /* 0: the stored update's */, ks_esdf_refresh_stats* stats /* may be NULL */);
+int ks_esdf_changed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n);
 int ks_esdf_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, void* out /* n * vps^3 * 8 B, host block layout */);
 int ks_esdf_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, float* distance, uint8_t* flags,
                   uint8_t* label /* any may be NULL */);

@@ -39,6 +39,7 @@ ABI_SYMBOLS = [
     "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
+    "ks_esdf_refresh", "ks_esdf_changed_blocks",
 ]
 
 
@@ -97,6 +98,12 @@ class KsEsdfConfig(C.Structure):
 class KsEsdfStats(C.Structure):
     _fields_ = [("voxels_observed", C.c_uint64), ("voxels_fixed", C.c_uint64), ("voxels_clamped", C.c_uint64),
                 ("box_voxels", C.c_uint64 * 3), ("workspace_bytes", C.c_uint64)]
+
+
+class KsEsdfRefreshStats(C.Structure):
+    _fields_ = [("tiles_stale", C.c_uint64), ("tiles_recomputed", C.c_uint64), ("tiles_total", C.c_uint64),
+                ("voxels_observed", C.c_uint64), ("voxels_fixed", C.c_uint64), ("voxels_clamped", C.c_uint64),
+                ("workspace_bytes", C.c_uint64)]
 
 
 # KS_ESDF_RECORD_BYTES = 8; flags = observed | fixed << 1; label 255 = no site within reach (or a default record)
@@ -188,6 +195,8 @@ def lib():
         L.ks_esdf_update.argtypes = [vp, C.POINTER(KsEsdfConfig), C.POINTER(KsEsdfStats)]
         L.ks_esdf_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_esdf_query.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
+        L.ks_esdf_refresh.argtypes = [vp, C.c_uint64, C.POINTER(KsEsdfRefreshStats)]
+        L.ks_esdf_changed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -390,8 +399,30 @@ class HipIntegrator:
         idx = self.block_indices()
         return idx, self.esdf_blocks(idx), stats
 
+    def esdf_refresh(self, max_workspace_bytes=0) -> dict:
+        """ks_esdf_refresh: brings the stored ESDF up to date with the map, recomputing only the tiles that the tiles written
+        since the last update or refresh can reach; it uses the configuration of the update that made the store.
+        max_workspace_bytes 0: that update's.  Returns the stats; a KsError raised here carries them too."""
+        st = KsEsdfRefreshStats()
+        rc = lib().ks_esdf_refresh(self._h, int(max_workspace_bytes), C.byref(st))
+        stats = {k: int(getattr(st, k)) for k, _ in KsEsdfRefreshStats._fields_}
+        if rc != 0:
+            err = KsError(rc, lib().ks_last_error(self._h).decode())
+            err.stats = stats
+            raise err
+        return stats
+
+    def esdf_changed_blocks(self) -> np.ndarray:
+        """Blocks that hold a tile the last esdf_refresh() recomputed, ascending; empty after an esdf_update()."""
+        n = C.c_size_t()
+        self._chk(lib().ks_esdf_changed_blocks(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            self._chk(lib().ks_esdf_changed_blocks(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
     def esdf_blocks(self, indices) -> np.ndarray:
-        """Records of the stored ESDF (the snapshot of the last esdf() / esdf_update()) for host-layout blocks."""
+        """Records of the stored ESDF (as of the last esdf() / esdf_update() / esdf_refresh()) for host-layout blocks."""
         indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
         out = np.zeros((len(indices), self.vps ** 3), dtype=ESDF_DTYPE)
         self._chk(lib().ks_esdf_download_blocks(self._h, _ptr(indices), len(indices), _ptr(out)))

@@ -484,8 +484,8 @@ struct ks_ctx {
   std::vector<ks_mesh_block> mesh_dir;     // one entry per element of mesh_blocks as of the last update (n_vertices may be 0)
   std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
   DevBuf<uint8_t> d_mesh_buf[10];          // grow-only scratch of the passes (mesh_scratch)
-  // ks_esdf_update (ks_k_esdf.h).  The store holds 512 records per tile slot, a snapshot of the map at the last update;
-  // everything grows only.
+  // ks_esdf_update / ks_esdf_refresh (ks_k_esdf.h).  The store holds 512 records per tile slot: the ESDF of the map as it
+  // was at the last update or refresh; everything grows only.
   DevBuf<EsdfRecord> esdf_store;           // [esdf_tiles][512]
   DevBuf<uint64_t> esdf_keys[2];           // the two key buffers of the passes: [sign][box voxel] each
   DevBuf<uint32_t> esdf_slots;             // dense slot grid of the box
@@ -494,7 +494,13 @@ struct ks_ctx {
   DevBuf<int32_t> esdf_idx;
   DevBuf<float> esdf_xyz;
   bool esdf_valid = false;                 // an update has run since the map was last cleared
-  uint32_t esdf_tiles = 0;                 // tiles that were resident at that update
+  uint32_t esdf_tiles = 0;                 // tiles that were resident at that update (or at the last refresh)
+  ks_esdf_config esdf_cfg{};               // of the update that made the stored ESDF: what a refresh recomputes with
+  uint64_t esdf_totals[3] = {0, 0, 0};     // voxels observed | fixed | clamped of the whole store
+  std::vector<int32_t> esdf_changed;       // blocks that hold a tile the last refresh recomputed
+  DevBuf<uint64_t> esdf_bricks[2];         // refresh: the bricks of lists X and Y
+  DevBuf<uint64_t> esdf_lists;             // ... the sorted positions of X | Y | Z
+  DevBuf<uint32_t> esdf_zslots;            // ... the pool slot of each position of Z
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -2888,7 +2894,7 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
   std::vector<uint8_t> stale(nt);
   if (nt) {
     HIPCHK(c, hipMemcpy(stale.data(), c->pool.mesh_stale(), nt, hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemsetAsync(c->pool.mesh_stale(), 0, nt, st));
+    hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleMesh);   // (the ESDF's bit stays)
   }
   auto tile_block = [&](uint64_t k) {
     const int tx = (int)((k >> 36) & 0x3ffffu) - kTileBias, ty = (int)((k >> 18) & 0x3ffffu) - kTileBias, tz = (int)(k & 0x3ffffu) - kTileBias;
@@ -2916,14 +2922,14 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
     R = B;
   } else {
     bool any = false;
-    for (uint32_t s = 0; s < nt && !any; ++s) any = stale[s] != 0;
+    for (uint32_t s = 0; s < nt && !any; ++s) any = (stale[s] & kStaleMesh) != 0;
     if (any && keys.empty()) {
       keys.resize(nt);
       HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
     }
     std::vector<uint64_t> cand;
     for (uint32_t s = 0; s < nt; ++s) {
-      if (!stale[s]) continue;
+      if (!(stale[s] & kStaleMesh)) continue;
       int32_t b[3];
       mesh_block_of(tile_block(keys[s]), b);
       for (int o = 0; o < 8; ++o) cand.push_back(mesh_block_key(b[0] - (o & 1), b[1] - ((o >> 1) & 1), b[2] - (o >> 2)));
@@ -3227,10 +3233,15 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
                        B, c->pool, (const uint64_t*)c->esdf_keys[1].get(), (uint64_t*)nullptr, c->esdf_store.get(), c->esdf_counters.get());
     HIPCHK(c, hipMemcpyAsync(counts, c->esdf_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
   }
+  // the snapshot is current everywhere: no tile is stale for ks_esdf_refresh
+  if (nt) hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleEsdf);
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
   c->esdf_valid = true;
   c->esdf_tiles = nt;
+  c->esdf_cfg = *e;
+  for (int k = 0; k < 3; ++k) c->esdf_totals[k] = counts[k];
+  c->esdf_changed.clear();
   if (stats) {
     stats->voxels_observed = counts[0];
     stats->voxels_fixed = counts[1];
@@ -3243,6 +3254,226 @@ static int esdf_ready(ks_ctx* c, const char* who) {
   if (c->esdf_valid) return KS_OK;
   c->err = std::string(who) + ": no ESDF is stored (ks_esdf_update has not run since the map was created or cleared)";
   return KS_ERR_INVALID_ARG;
+}
+
+// ---- incremental refresh of the stored ESDF ("ESDF", incremental refresh) ----
+// The lists of a refresh: pure arithmetic over tile positions (esdf_pos of ks_k_esdf.h; every vector ascending).
+struct EsdfLists {
+  std::vector<uint64_t> X, Y, Z;   // positions of passes x, y and z; Z = A, the tiles that are recomputed
+  std::vector<uint32_t> z_slots;   // pool slot of each tile of Z
+  uint64_t n_stale = 0;            // |S|
+};
+static inline void esdf_pos_of(uint64_t p, int t[3]) {
+  t[0] = (int)((p >> 42) & 0x1fffffu) - kEsdfPosBias;
+  t[1] = (int)((p >> 21) & 0x1fffffu) - kEsdfPosBias;
+  t[2] = (int)(p & 0x1fffffu) - kEsdfPosBias;
+}
+// every position within g of a listed one along `axis`
+static std::vector<uint64_t> esdf_dilate(const std::vector<uint64_t>& in, int axis, int g) {
+  std::vector<uint64_t> out;
+  out.reserve(in.size() * (size_t)(2 * g + 1));
+  for (uint64_t p : in) {
+    int t[3];
+    esdf_pos_of(p, t);
+    for (int d = -g; d <= g; ++d) {
+      int u[3] = {t[0], t[1], t[2]};
+      u[axis] += d;
+      out.push_back(esdf_pos(u[0], u[1], u[2]));
+    }
+  }
+  std::sort(out.begin(), out.end());
+  out.erase(std::unique(out.begin(), out.end()), out.end());
+  return out;
+}
+// the positions of `in` that have one of `have` (ascending) within g along `axis`
+static std::vector<uint64_t> esdf_keep_near(const std::vector<uint64_t>& in, const std::vector<uint64_t>& have, int axis, int g) {
+  std::vector<uint64_t> out;
+  for (uint64_t p : in) {
+    int t[3];
+    esdf_pos_of(p, t);
+    bool near = false;
+    for (int d = -g; d <= g && !near; ++d) {
+      int u[3] = {t[0], t[1], t[2]};
+      u[axis] += d;
+      near = std::binary_search(have.begin(), have.end(), esdf_pos(u[0], u[1], u[2]));
+    }
+    if (near) out.push_back(p);
+  }
+  return out;
+}
+// keys: slot -> packed tile key; stale: slot -> stale for the ESDF; region: tiles [lo, hi] per axis that hold results.
+//   S = the stale tiles;  Z = A = the resident tiles of the region within g of S on every axis;
+//   Y = A dilated by g along z, X = Y dilated by g along y — less the positions whose brick can hold no real key: a brick of X
+//   has one only with a resident tile within g along x, a brick of Y only with a kept position of X within g along y.  A dropped
+//   brick would hold kEsdfNone throughout, which is what a miss reads as.
+static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& stale, int g, bool use_region,
+                               const int64_t region_lo[3], const int64_t region_hi[3], EsdfLists* L) {
+  const size_t nt = keys.size();
+  std::vector<std::pair<uint64_t, uint32_t>> resident(nt);
+  std::vector<uint64_t> S;
+  for (size_t s = 0; s < nt; ++s) {
+    const uint64_t k = keys[s];
+    const uint64_t p = esdf_pos((int)((k >> 36) & 0x3ffffu) - kTileBias, (int)((k >> 18) & 0x3ffffu) - kTileBias, (int)(k & 0x3ffffu) - kTileBias);
+    resident[s] = {p, (uint32_t)s};
+    if (stale[s]) S.push_back(p);
+  }
+  std::sort(resident.begin(), resident.end());
+  std::sort(S.begin(), S.end());
+  L->n_stale = S.size();
+  const std::vector<uint64_t> reach = esdf_dilate(esdf_dilate(esdf_dilate(S, 0, g), 1, g), 2, g);
+  std::vector<uint64_t> all(nt);
+  for (size_t i = 0; i < nt; ++i) {
+    all[i] = resident[i].first;
+    int t[3];
+    esdf_pos_of(all[i], t);
+    bool in = std::binary_search(reach.begin(), reach.end(), all[i]);
+    for (int a = 0; a < 3 && in && use_region; ++a) in = t[a] >= region_lo[a] && t[a] <= region_hi[a];
+    if (!in) continue;
+    L->Z.push_back(all[i]);
+    L->z_slots.push_back(resident[i].second);
+  }
+  const std::vector<uint64_t> y_all = esdf_dilate(L->Z, 2, g);
+  L->X = esdf_keep_near(esdf_dilate(y_all, 1, g), all, 0, g);
+  L->Y = esdf_keep_near(y_all, L->X, 1, g);
+}
+
+int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (c->shard_export) {
+    c->err = "ks_esdf_refresh: a marcher context of ks_integrate_round_exact holds no voxel data";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (int rc = esdf_ready(c, "ks_esdf_refresh")) return rc;
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const ks_esdf_config& e = c->esdf_cfg;
+  if (max_workspace_bytes == 0) max_workspace_bytes = e.max_workspace_bytes;
+  const uint32_t nt = c->tiles_initialised, nt_old = c->esdf_tiles;
+  const int R = (int)ceilf(e.max_distance_m / c->cfg.voxel_size), g = (R + 7) / 8;
+  int rc;
+  // 1) the stale tiles (a tile that joined the map since has no records yet: stale whatever its mark says) and the lists
+  std::vector<uint64_t> keys(nt);
+  std::vector<uint8_t> stale(nt);
+  if (nt) {
+    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(stale.data(), c->pool.mesh_stale(), nt, hipMemcpyDeviceToHost));
+  }
+  for (uint32_t s = 0; s < nt; ++s) stale[s] = (stale[s] & kStaleEsdf) || s >= nt_old;
+  int64_t region_lo[3] = {0, 0, 0}, region_hi[3] = {0, 0, 0};
+  const int tpb = c->cfg.voxels_per_side / 8;
+  for (int a = 0; a < 3; ++a) {
+    region_lo[a] = (int64_t)e.region_min[a] * tpb;
+    region_hi[a] = ((int64_t)e.region_max[a] + 1) * tpb - 1;
+  }
+  EsdfLists L;
+  esdf_refresh_lists(keys, stale, g, e.use_region != 0, region_lo, region_hi, &L);
+  const size_t nx = L.X.size(), ny = L.Y.size(), nz = L.Z.size();
+  const uint64_t workspace = (uint64_t)(nx + ny) * kEsdfBrickKeys * 8 + (uint64_t)(nx + ny + nz) * 8 + (uint64_t)nz * 4;
+  if (stats) {
+    stats->tiles_stale = L.n_stale;
+    stats->tiles_recomputed = nz;
+    stats->tiles_total = nt;
+    stats->voxels_observed = c->esdf_totals[0];
+    stats->voxels_fixed = c->esdf_totals[1];
+    stats->voxels_clamped = c->esdf_totals[2];
+    stats->workspace_bytes = L.n_stale ? workspace : 0;
+  }
+  if (L.n_stale == 0) {   // nothing to do: the totals of the store as it is
+    c->esdf_changed.clear();
+    return KS_OK;
+  }
+  if (workspace > max_workspace_bytes) {
+    c->err = "ks_esdf_refresh: " + std::to_string(nz) + " tiles to recompute need " + std::to_string(workspace) +
+             " bytes of work space, more than max_workspace_bytes = " + std::to_string(max_workspace_bytes);
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (nx >= (1ull << 31) || ny >= (1ull << 31)) {
+    c->err = "ks_esdf_refresh: too many tiles for one call";
+    return KS_ERR_UNSUPPORTED;
+  }
+  // 2) room for the tiles that joined: the store keeps its records when it moves
+  DevBuf<EsdfRecord> grown;
+  if ((size_t)nt * kTileVoxels > c->esdf_store.size())
+    if ((rc = grown.alloc(c, ((size_t)nt + nt / 2 + 64) * kTileVoxels))) return rc;
+  if ((rc = c->esdf_bricks[0].reserve(c, nx * kEsdfBrickKeys, (nx + nx / 2) * kEsdfBrickKeys)) ||
+      (rc = c->esdf_bricks[1].reserve(c, ny * kEsdfBrickKeys, (ny + ny / 2) * kEsdfBrickKeys)) ||
+      (rc = c->esdf_lists.reserve(c, nx + ny + nz, (nx + ny + nz) * 3 / 2)) || (rc = c->esdf_zslots.reserve(c, nz, nz * 3 / 2)) ||
+      (rc = c->esdf_counters.reserve(c, 3, 3)))
+    return rc;
+  c->esdf_valid = false;   // (a failure below leaves no half-written store readable)
+  if (grown.get()) {
+    if (nt_old) HIPCHK(c, hipMemcpyAsync(grown.get(), c->esdf_store.get(), (size_t)nt_old * kTileVoxels * sizeof(EsdfRecord), hipMemcpyDeviceToDevice, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    c->esdf_store = std::move(grown);
+  }
+  if (nt > nt_old)
+    hipLaunchKernelGGL(k_esdf_fill, dim3((uint32_t)(((size_t)(nt - nt_old) * kTileVoxels + 255) / 256)), dim3(256), 0, st,
+                       c->esdf_store.get() + (size_t)nt_old * kTileVoxels, (size_t)(nt - nt_old) * kTileVoxels);
+  unsigned long long counts[3] = {c->esdf_totals[0], c->esdf_totals[1], c->esdf_totals[2]};
+  if (nz) {
+    // 3) the three passes over the lists, then the totals from the records
+    uint64_t* d_x = c->esdf_lists.get();
+    uint64_t *d_y = d_x + nx, *d_z = d_y + ny;
+    if (nx) HIPCHK(c, hipMemcpyAsync(d_x, L.X.data(), nx * 8, hipMemcpyHostToDevice, st));
+    if (ny) HIPCHK(c, hipMemcpyAsync(d_y, L.Y.data(), ny * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_z, L.Z.data(), nz * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->esdf_zslots, L.z_slots.data(), nz * 4, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
+    EsdfRefresh E{R, c->cfg.voxel_size, e.min_weight, e.min_distance_m, e.max_distance_m};
+    if (nx)
+      hipLaunchKernelGGL(k_esdf_brick<0>, dim3((uint32_t)nx), dim3(256), 0, st, E, c->table, c->pool, nt, (const uint64_t*)d_x,
+                         (const uint64_t*)nullptr, 0u, (const uint64_t*)nullptr, c->esdf_bricks[0].get(), (const uint32_t*)nullptr,
+                         (EsdfRecord*)nullptr);
+    if (ny)
+      hipLaunchKernelGGL(k_esdf_brick<1>, dim3((uint32_t)ny), dim3(256), 0, st, E, c->table, c->pool, nt, (const uint64_t*)d_y,
+                         (const uint64_t*)d_x, (uint32_t)nx, (const uint64_t*)c->esdf_bricks[0].get(), c->esdf_bricks[1].get(),
+                         (const uint32_t*)nullptr, (EsdfRecord*)nullptr);
+    hipLaunchKernelGGL(k_esdf_brick<2>, dim3((uint32_t)nz), dim3(256), 0, st, E, c->table, c->pool, nt, (const uint64_t*)d_z,
+                       (const uint64_t*)d_y, (uint32_t)ny, (const uint64_t*)c->esdf_bricks[1].get(), (uint64_t*)nullptr,
+                       (const uint32_t*)c->esdf_zslots.get(), c->esdf_store.get());
+    const size_t nrec = (size_t)nt * kTileVoxels;
+    hipLaunchKernelGGL(k_esdf_count, dim3((uint32_t)((nrec + 1023) / 1024)), dim3(256), 0, st, (const EsdfRecord*)c->esdf_store.get(), nrec,
+                       e.max_distance_m, c->esdf_counters.get());
+    HIPCHK(c, hipMemcpyAsync(counts, c->esdf_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+  }
+  hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleEsdf);
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->esdf_valid = true;
+  c->esdf_tiles = nt;
+  for (int k = 0; k < 3; ++k) c->esdf_totals[k] = counts[k];
+  // 4) the blocks of the recomputed tiles
+  const int sh = c->vps_shift;
+  std::vector<uint64_t> blocks(nz);
+  for (size_t i = 0; i < nz; ++i) {
+    int t[3];
+    esdf_pos_of(L.Z[i], t);
+    blocks[i] = mesh_block_key(t[0] >> sh, t[1] >> sh, t[2] >> sh);
+  }
+  std::sort(blocks.begin(), blocks.end());
+  blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
+  c->esdf_changed.resize(3 * blocks.size());
+  for (size_t i = 0; i < blocks.size(); ++i) mesh_block_of(blocks[i], &c->esdf_changed[3 * i]);
+  if (stats) {
+    stats->voxels_observed = counts[0];
+    stats->voxels_fixed = counts[1];
+    stats->voxels_clamped = counts[2];
+  }
+  return KS_OK;
+}
+
+int ks_esdf_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
+  *n = c->esdf_changed.size() / 3;
+  if (out_xyz) {
+    if (cap < *n) {
+      c->err = "ks_esdf_changed_blocks: output buffer too small";
+      return KS_ERR_INVALID_ARG;
+    }
+    std::memcpy(out_xyz, c->esdf_changed.data(), c->esdf_changed.size() * sizeof(int32_t));
+  }
+  return KS_OK;
 }
 
 int ks_esdf_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, void* out) {
@@ -3989,8 +4220,9 @@ static void mesh_reset(ks_ctx* c) {
   c->mesh_dir.clear();
   c->mesh_changed.clear();
   c->mesh_tiles_seen = 0;
-  c->esdf_valid = false;   // the ESDF is a snapshot of the map that goes
+  c->esdf_valid = false;   // the stored ESDF goes with the map
   c->esdf_tiles = 0;
+  c->esdf_changed.clear();
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {

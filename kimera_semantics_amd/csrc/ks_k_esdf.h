@@ -1,6 +1,6 @@
-// ks_k_esdf.h — batch ESDF with nearest-surface labels from the device-resident map.  The contract (observed voxels, sites,
-// the integer window, the 64-bit key, the final f32 rule) is DESIGN.md, section "ESDF"; tests/esdf_model.py restates it in
-// NumPy and the kernels are compared with it bit for bit.
+// ks_k_esdf.h — ESDF with nearest-surface labels from the device-resident map: the batch update and the incremental
+// refresh.  The contract (observed voxels, sites, the integer window, the 64-bit key, the final f32 rule) is DESIGN.md,
+// section "ESDF"; tests/esdf_model.py restates it in NumPy and the kernels are compared with it bit for bit.
 //
 // The key of a site is  d2 << 40 | bits(|distance|) << 8 | label  and the result of a voxel is the MINIMUM key over the
 // same-sign sites of its (2R+1)^3 window.  d2 = dx^2 + dy^2 + dz^2 and adding dx^2 << 40 keeps the order of the rest, so
@@ -15,6 +15,8 @@
 //   k_esdf_axis<1>   pass z: the same walk along z over the plane of the voxel's own sign, then the final rule and the
 //                    8-byte record into the store of the voxel's tile (resident tiles, inside the region, only)
 //   k_esdf_download  host-layout blocks of records;  k_esdf_query  nearest-voxel lookup of world points
+//   k_esdf_brick<0|1|2>  the same three passes over lists of tile positions, for the incremental refresh (further down);
+//   k_esdf_count     the totals of a store from its records
 //
 // A plane never holds all-ones for "no site": kEsdfNone = 1 << 62 is above every real key (d2 <= 3 * 255^2 < 2^18) and
 // stays below 2^63 after the three additions, so the passes need no special case.
@@ -275,6 +277,205 @@ __global__ void __launch_bounds__(256) k_esdf_query(TileTable T, const EsdfRecor
     if (slot < n_tiles) rec = store[(size_t)slot * kTileVoxels + esdf_local(vx, vy, vz)];
   }
   out[i] = rec;
+}
+
+// ---- incremental refresh (ks_esdf_refresh; DESIGN.md, "ESDF", incremental refresh) -----------------------------------------
+// The same three passes over LISTS of tile positions instead of a box.  A listed position owns a BRICK: the two key planes of
+// its 8^3 voxels, [sign][z][y][x], 8 KiB.  Pass x (AXIS 0) makes the bricks of list X from the records of the resident tiles
+// beside each position along x (found through the context's tile table), pass y the bricks of list Y from those of X, pass z
+// the final records of the tiles of list Z from those of Y; a brick is found by bisection in the sorted positions of the list
+// it belongs to, and a miss reads as "no sites".  One workgroup per position.  The window along the axis is walked one
+// neighbour brick at a time through LDS, so LDS does not depend on R: s_key[sign][index along the axis][the other two].  The
+// passes read it with lanes on consecutive 8-byte words.  Staging a brick writes it transposed; an 8-byte LDS write goes 16
+// lanes at a time over 32 banks, and the rows are padded so that those 16 lanes fall on 16 different words: pass x stages
+// 8 indices along the axis times 2 rows across (row stride = 2 words mod 16: 66), pass y 2 along times 8 across (8 mod 16: 72).
+constexpr int kEsdfPosBias = 1 << 20;   // list positions are tile coordinates dilated by up to 2 * 32 tiles: 21-bit fields
+constexpr int kEsdfBrickKeys = 2 * kTileVoxels;
+
+__host__ __device__ __forceinline__ uint64_t esdf_pos(int tx, int ty, int tz) {
+  return ((uint64_t)(uint32_t)(tx + kEsdfPosBias) << 42) | ((uint64_t)(uint32_t)(ty + kEsdfPosBias) << 21) |
+         (uint64_t)(uint32_t)(tz + kEsdfPosBias);
+}
+
+struct EsdfRefresh {
+  int R;
+  float voxel_size, min_weight, min_distance, max_distance;
+};
+
+__device__ __forceinline__ uint32_t esdf_find(const uint64_t* __restrict__ keys, uint32_t n, uint64_t k) {
+  uint32_t lo = 0, hi = n;
+  while (lo < hi) {
+    const uint32_t mid = (lo + hi) >> 1;
+    if (keys[mid] < k) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && keys[lo] == k ? lo : 0xffffffffu;
+}
+
+// element e of a brick (x + 8 * (y + 8 * z)) -> its index along AXIS and over the other two coordinates, and back
+template <int AXIS>
+__device__ __forceinline__ void esdf_split(uint32_t e, uint32_t& along, uint32_t& across) {
+  if (AXIS == 0) { along = e & 7u; across = e >> 3; }
+  else if (AXIS == 1) { along = (e >> 3) & 7u; across = (e & 7u) | ((e >> 6) << 3); }
+  else { along = e >> 6; across = e & 63u; }
+}
+
+// grid (positions of the list), 256 work-items: lane = the voxel's index across the axis, wavefront w = outputs 2w and 2w + 1
+// along it.  pos: the list (sorted); AXIS 0: n_tiles = resident tiles, in / in_pos unused; AXIS 1, 2: in = the bricks of the
+// list in_pos[n_in]; AXIS 0, 1: out = this list's bricks; AXIS 2: slots = pool slot of each position, store = the records.
+template <int AXIS>
+__global__ void __launch_bounds__(256) k_esdf_brick(EsdfRefresh E, TileTable T, Pool P, uint32_t n_tiles, const uint64_t* __restrict__ pos,
+                                                    const uint64_t* __restrict__ in_pos, uint32_t n_in, const uint64_t* __restrict__ in,
+                                                    uint64_t* __restrict__ out, const uint32_t* __restrict__ slots,
+                                                    EsdfRecord* __restrict__ store) {
+  constexpr int kRow = AXIS == 0 ? 66 : 72;
+  __shared__ uint64_t s_key[2][8][kRow];
+  const uint32_t b = blockIdx.x, across = lane_id(), wave = threadIdx.x >> 6;
+  const uint64_t p = pos[b];
+  const int tx = (int)((p >> 42) & 0x1fffffu) - kEsdfPosBias, ty = (int)((p >> 21) & 0x1fffffu) - kEsdfPosBias,
+            tz = (int)(p & 0x1fffffu) - kEsdfPosBias;
+  const int R = E.R, g = (R + 7) >> 3;
+  // pass z: the voxel's own record decides the plane it reads
+  uint32_t slot = 0;
+  int plane[2] = {0, 0};
+  float dist[2] = {0.0f, 0.0f};
+  bool observed[2] = {false, false}, site[2] = {false, false};
+  uint32_t own_label[2] = {0u, 0u};
+  if (AXIS == 2) {
+    slot = slots[b];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const uint4 q = P.vox[((size_t)slot * kTileVoxels + across + 64u * (2u * wave + (uint32_t)j)) * 8];
+      const float d = __uint_as_float(q.x), w = __uint_as_float(q.y);
+      dist[j] = d;
+      observed[j] = w >= E.min_weight;
+      site[j] = observed[j] && fabsf(d) < E.min_distance;
+      plane[j] = d < 0.0f ? 1 : 0;
+      own_label[j] = q.w == 255u ? 0u : (q.w & 0xffu);
+    }
+  }
+  uint64_t m0[2] = {kEsdfNone, kEsdfNone}, m1[2] = {kEsdfNone, kEsdfNone};
+  for (int dt = -g; dt <= g; ++dt) {   // (every neighbour within g tiles has an offset within R: 8 * g - 7 <= R)
+    // the neighbour's keys: the same for every work-item, so the branches below do not diverge
+    const int nx = tx + (AXIS == 0 ? dt : 0), ny = ty + (AXIS == 1 ? dt : 0), nz = tz + (AXIS == 2 ? dt : 0);
+    uint32_t src;
+    if (AXIS == 0) {
+      src = 0xffffffffu;
+      if (nx >= -kTileBias && nx < kTileBias && ny >= -kTileBias && ny < kTileBias && nz >= -kTileBias && nz < kTileBias)
+        src = tile_lookup(T, pack_tile(nx, ny, nz));
+      if (src >= n_tiles) continue;
+    } else {
+      src = esdf_find(in_pos, n_in, esdf_pos(nx, ny, nz));
+      if (src == 0xffffffffu) continue;
+    }
+    __syncthreads();   // (the brick staged before this one has been read)
+    for (uint32_t e = threadIdx.x; e < (uint32_t)kTileVoxels; e += 256u) {
+      uint64_t k0 = kEsdfNone, k1 = kEsdfNone;
+      if (AXIS == 0) {
+        const uint4 q = P.vox[((size_t)src * kTileVoxels + e) * 8];
+        const float d = __uint_as_float(q.x), w = __uint_as_float(q.y);
+        if (w >= E.min_weight && fabsf(d) < E.min_distance) {
+          const uint32_t label = q.w == 255u ? 0u : (q.w & 0xffu);
+          const uint64_t k = ((uint64_t)__float_as_uint(fabsf(d)) << 8) | (uint64_t)label;
+          if (d < 0.0f) k1 = k;
+          else k0 = k;
+        }
+      } else {
+        k0 = in[(size_t)src * kEsdfBrickKeys + e];
+        k1 = in[(size_t)src * kEsdfBrickKeys + kTileVoxels + e];
+      }
+      uint32_t i, c;
+      esdf_split<AXIS>(e, i, c);
+      s_key[0][i][c] = k0;
+      s_key[1][i][c] = k1;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int a = 2 * (int)wave + j;
+      uint64_t ma = m0[j], mb = m1[j];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) {
+        const int o = dt * 8 + i - a;
+        if (o < -R || o > R) continue;
+        const uint64_t add = (uint64_t)(uint32_t)(o * o) << 40;
+        if (AXIS == 2) {
+          const uint64_t k = s_key[plane[j]][i][across] + add;
+          ma = k < ma ? k : ma;
+        } else {
+          const uint64_t ka = s_key[0][i][across] + add, kb = s_key[1][i][across] + add;
+          ma = ka < ma ? ka : ma;
+          mb = kb < mb ? kb : mb;
+        }
+      }
+      m0[j] = ma;
+      m1[j] = mb;
+    }
+  }
+  if (AXIS != 2) {
+    // through LDS once more, so that the brick leaves in its own order: consecutive work-items, consecutive words
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      s_key[0][2 * wave + j][across] = m0[j];
+      s_key[1][2 * wave + j][across] = m1[j];
+    }
+    __syncthreads();
+    for (uint32_t e = threadIdx.x; e < (uint32_t)kTileVoxels; e += 256u) {
+      uint32_t i, c;
+      esdf_split<AXIS>(e, i, c);
+      out[(size_t)b * kEsdfBrickKeys + e] = s_key[0][i][c];
+      out[(size_t)b * kEsdfBrickKeys + kTileVoxels + e] = s_key[1][i][c];
+    }
+  } else {
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      EsdfRecord rec{0.0f, kEsdfDefaultTail};
+      if (site[j]) {
+        rec.distance = dist[j];
+        rec.tail = 3u | (own_label[j] << 8);
+      } else if (observed[j]) {
+        const uint64_t k = m0[j];
+        float d = E.max_distance;
+        uint32_t label = 255u;
+        if (k < kEsdfNone) {
+          const float centre = E.voxel_size * sqrtf((float)(uint32_t)(k >> 40));
+          const float sum = centre + __uint_as_float((uint32_t)(k >> 8));
+          d = fminf(E.max_distance, sum);
+          label = (uint32_t)(k & 0xffu);
+        }
+        rec.distance = plane[j] ? -d : d;
+        rec.tail = 1u | (label << 8);
+      }
+      store[(size_t)slot * kTileVoxels + across + 64u * (2u * wave + (uint32_t)j)] = rec;
+    }
+  }
+}
+
+// voxels observed | fixed | clamped of a store, from its records (the totals ks_esdf_update counts while it writes them):
+// 1024 records per workgroup
+__global__ void __launch_bounds__(256) k_esdf_count(const EsdfRecord* __restrict__ store, size_t n, float max_distance,
+                                                    unsigned long long* __restrict__ counters) {
+  uint32_t n_obs = 0, n_fix = 0, n_clamp = 0;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    const size_t i = (size_t)blockIdx.x * 1024u + (size_t)j * 256u + threadIdx.x;
+    bool obs = false, fix = false, clamped = false;
+    if (i < n) {
+      const EsdfRecord r = store[i];
+      obs = (r.tail & 1u) != 0u;
+      fix = (r.tail & 2u) != 0u;
+      clamped = obs && !fix && fabsf(r.distance) == max_distance;
+    }
+    n_obs += (uint32_t)__popcll(__ballot(obs));
+    n_fix += (uint32_t)__popcll(__ballot(fix));
+    n_clamp += (uint32_t)__popcll(__ballot(clamped));
+  }
+  if (lane_id() == 0) {
+    if (n_obs) atomicAdd(&counters[0], (unsigned long long)n_obs);
+    if (n_fix) atomicAdd(&counters[1], (unsigned long long)n_fix);
+    if (n_clamp) atomicAdd(&counters[2], (unsigned long long)n_clamp);
+  }
 }
 
 }  // namespace ksk

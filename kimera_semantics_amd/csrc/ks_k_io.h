@@ -33,8 +33,14 @@ __global__ void __launch_bounds__(512) k_reset_tiles(Pool P, const uint32_t* __r
   if (threadIdx.x == 0) {
     P.updated[slot] = 1;
     P.dirty[slot] = 0;
-    P.mesh_stale()[slot] = 1;
+    P.mesh_stale()[slot] = kStaleAll;
   }
+}
+
+// a consumer of the stale byte (Pool::mesh_stale) takes its own bit off the first n tiles; the context is quiesced
+__global__ void __launch_bounds__(256) k_stale_clear(uint8_t* __restrict__ stale, uint32_t n, uint8_t bit) {
+  const uint32_t slot = blockIdx.x * blockDim.x + threadIdx.x;
+  if (slot < n) stale[slot] = (uint8_t)(stale[slot] & ~bit);
 }
 
 // pool growth: the tile table is rebuilt at twice the capacity; slot numbers are kept
@@ -101,7 +107,7 @@ __global__ void __launch_bounds__(512) k_merge_tiles(TileTable T, Pool P, const 
   const uint32_t slot = tile_lookup(T, ukeys[blockIdx.x]);
   if (slot == 0xffffffffu) return;
   const uint32_t j0 = offs[blockIdx.x], j1 = offs[blockIdx.x + 1];
-  if (threadIdx.x == 0) P.mesh_stale()[slot] = 1;   // (neither of the two sync flags: the merge has consumers of its own for them)
+  if (threadIdx.x == 0) P.mesh_stale()[slot] = kStaleAll;   // (neither of the two sync flags: the merge has consumers of its own for them)
   uint4* dst = P.vox + (size_t)slot * kTileVoxels * 8;
   const uint32_t lane = lane_id(), sub = lane & 7u;
   const uint32_t cbase = (sub - 1u) * 4u;
@@ -437,7 +443,7 @@ __global__ void __launch_bounds__(256) k_upload(TileTable T, Pool P, const int32
   if (slot == 0xffffffffu) return;
   const uint32_t local = (uint32_t)(vx & 7) + 8u * ((uint32_t)(vy & 7) + 8u * (uint32_t)(vz & 7));
   uint32_t* rec = (uint32_t*)(P.vox + ((size_t)slot * kTileVoxels + local) * 8);
-  if (local == 0) P.mesh_stale()[slot] = 1;   // the mesher's flag only: the host has what it uploads
+  if (local == 0) P.mesh_stale()[slot] = kStaleAll;   // the mesher's flag only: the host has what it uploads
   const size_t o = (size_t)b * nv + l;
   if (tsdf_in) {
     const uint32_t* t = (const uint32_t*)(tsdf_in + o * 12);

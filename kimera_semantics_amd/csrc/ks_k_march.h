@@ -799,7 +799,7 @@ __global__ void __launch_bounds__(256) k_emit(BatchView V, TileTable T, Pool P) 
         }
       }
       slot = got;
-      if (slot < T.max_tiles) { P.updated[slot] = 1; P.dirty[slot] = 1; P.mesh_stale()[slot] = 1; }
+      if (slot < T.max_tiles) { P.updated[slot] = 1; P.dirty[slot] = 1; P.mesh_stale()[slot] = kStaleAll; }
       else atomicOr(&C->err, kErrPool);  // pool exhausted (now or in an earlier frame): this frame is not applied
     }
     const uint64_t em = G.bits(__ballot(emit));
@@ -881,7 +881,7 @@ __global__ void __launch_bounds__(256) k_emit_lane(BatchView V, TileTable T, Poo
         got = kSlotBad;
       }
     }
-    if (got < T.max_tiles) { P.updated[got] = 1; P.dirty[got] = 1; P.mesh_stale()[got] = 1; }
+    if (got < T.max_tiles) { P.updated[got] = 1; P.dirty[got] = 1; P.mesh_stale()[got] = kStaleAll; }
     else atomicOr(&C->err, kErrPool);  // pool exhausted (now or in an earlier frame): this frame is not applied
     return got;
   };
@@ -1020,7 +1020,7 @@ __global__ void __launch_bounds__(512) k_init_tiles(Pool P, uint32_t first_slot)
     else v = make_uint4(0u, 0u, 0u, 0u);
     tile[q] = v;
   }
-  if (threadIdx.x == 0) { P.updated[slot] = 1; P.mesh_stale()[slot] = 1; }
+  if (threadIdx.x == 0) { P.updated[slot] = 1; P.mesh_stale()[slot] = kStaleAll; }
 }
 
 }  // namespace ksk

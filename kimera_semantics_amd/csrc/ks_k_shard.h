@@ -105,7 +105,7 @@ __global__ void __launch_bounds__(256) k_shard_import(uint32_t n, TileTable T, P
   const uint32_t s = seq[i];
   P.updated[slot] = 1;
   P.dirty[slot] = 1;
-  P.mesh_stale()[slot] = 1;
+  P.mesh_stale()[slot] = kStaleAll;
   pairs[i] = ((uint64_t)(s >> kShardSeqBits) << 56) | ((uint64_t)(slot * (uint32_t)kTileVoxels + (uint32_t)(g & 511u)) << kShardSeqBits) |
              (uint64_t)(s & ((1u << kShardSeqBits) - 1u));
   vals[i] = i;

@@ -143,9 +143,11 @@ struct Pool {
   // per tile: a voxel's distance, weight, colour or label written since ks_mesh_update last meshed it (set wherever the other
   // two flags are, and by upload and merge; cleared by the mesher alone).  A second plane of the `updated` allocation, at the
   // fixed offset kFlagPlane (the pool never holds that many tiles), so that Pool — a kernel argument of the whole hot path —
-  // keeps its size.
+  // keeps its size.  The byte holds one bit per consumer: every writer stores kStaleAll (one store, as before), the mesher
+  // tests and clears kStaleMesh, ks_esdf_update / ks_esdf_refresh kStaleEsdf — each while the context is quiesced (k_stale_clear).
   __host__ __device__ __forceinline__ uint8_t* mesh_stale() const { return updated + kFlagPlane; }
 };
+constexpr uint8_t kStaleMesh = 1, kStaleEsdf = 2, kStaleAll = kStaleMesh | kStaleEsdf;
 
 struct FrameParams {
   Pose T;

@@ -9,11 +9,13 @@
 // in.bin : u32 n_frames, then per frame { f32 T[7]; u32 n; f32 xyz[3n]; u8 rgba[4n] }
 // out.bin: u32 n_blocks, u32 vps, then per block { i32 idx[3]; tsdf vps^3*12 B; semantic vps^3*92 B }
 #include <algorithm>
+#include <array>
 #include <chrono>
 #include <voxblox/utils/timing.h>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -97,7 +99,23 @@ int main(int argc, char** argv) {
   const int restart_after = argc > 7 ? std::atoi(argv[7]) : -1;
   double integrate_ms = 0.0, tail_ms = 0.0;
   uint32_t tail_frames = 0;
+  // KS_DEMO_ESDF_REFRESH=<file>: an ESDF kept up to date while frames stream in — updateEsdf after the first half of the
+  // frames, refreshEsdf after the last, which hands back only the blocks it recomputed
+  const char* esdf_refresh_path = std::getenv("KS_DEMO_ESDF_REFRESH");
+  using EsdfBlock = kimera::HipSemanticTsdfIntegrator::EsdfBlock;
+  std::map<std::array<int32_t, 3>, EsdfBlock> esdf_kept;   // (ascending by x, y, z)
   for (uint32_t f = 0; f < n_frames; ++f) {
+    if (esdf_refresh_path && f == n_frames / 2) {
+      auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+      if (!hip) return 8;
+      kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+      eo.min_distance_m = 0.1f;
+      eo.max_distance_m = 0.4f;
+      std::vector<EsdfBlock> esdf;
+      hip->updateEsdf(eo, &esdf);
+      for (auto& eb : esdf) esdf_kept[{eb.index.x(), eb.index.y(), eb.index.z()}] = std::move(eb);
+      std::printf("adapter_demo: updateEsdf after %u frames, %zu blocks\n", f, esdf_kept.size());
+    }
     if ((int)f == restart_after) {
       if (pipeline)   // (a server syncs before it lets go of the integrator: the Layers are what the next one starts from)
         if (auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get())) hip->syncLayers();
@@ -208,6 +226,31 @@ int main(int argc, char** argv) {
     const ks_esdf_stats& es = hip->lastEsdfStats();
     std::printf("adapter_demo: updateEsdf %.3f ms, %u blocks, %llu observed voxels, %llu in the band\n", ms, n_esdf_blocks,
                 (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
+  }
+
+  // ... the blocks of the refresh replace or join the ones kept since the update; the file has the format of KS_DEMO_ESDF
+  if (esdf_refresh_path) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    std::vector<EsdfBlock> changed;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->refreshEsdf(&changed);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const size_t n_changed = changed.size(), n_before = esdf_kept.size();
+    for (auto& eb : changed) esdf_kept[{eb.index.x(), eb.index.y(), eb.index.z()}] = std::move(eb);
+    FILE* ef = std::fopen(esdf_refresh_path, "wb");
+    if (!ef) return 9;
+    const uint32_t n_esdf_blocks = esdf_kept.size(), esdf_vps = tsdf_layer.voxels_per_side();
+    std::fwrite(&n_esdf_blocks, 4, 1, ef);
+    std::fwrite(&esdf_vps, 4, 1, ef);
+    for (const auto& kv : esdf_kept) {
+      std::fwrite(kv.first.data(), 4, 3, ef);
+      std::fwrite(kv.second.voxels.data(), sizeof(kv.second.voxels[0]), kv.second.voxels.size(), ef);
+    }
+    std::fclose(ef);
+    const ks_esdf_refresh_stats& rs = hip->lastEsdfRefreshStats();
+    std::printf("adapter_demo: refreshEsdf %.3f ms, %zu blocks changed, %zu kept from the update, %llu of %llu tiles recomputed (%llu stale)\n", ms,
+                n_changed, n_before, (unsigned long long)rs.tiles_recomputed, (unsigned long long)rs.tiles_total, (unsigned long long)rs.tiles_stale);
   }
 
   vxb::BlockIndexList blocks;

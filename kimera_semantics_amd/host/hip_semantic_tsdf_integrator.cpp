@@ -282,7 +282,25 @@ bool HipSemanticTsdfIntegrator::updateEsdf(const EsdfOptions& options, std::vect
   if (n == 0) return false;
   std::vector<int32_t> idx(3 * n);
   check(ks_get_block_indices(ctx_, idx.data(), n, &n), "ks_get_block_indices");
-  const size_t vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
+  downloadEsdfBlocks(idx, out);
+  return true;
+}
+
+bool HipSemanticTsdfIntegrator::refreshEsdf(std::vector<EsdfBlock>* changed) {
+  CHECK_NOTNULL(changed);
+  changed->clear();
+  check(ks_esdf_refresh(ctx_, 0, &last_esdf_refresh_stats_), "ks_esdf_refresh");
+  size_t n = 0;
+  check(ks_esdf_changed_blocks(ctx_, nullptr, 0, &n), "ks_esdf_changed_blocks");
+  if (n == 0) return false;
+  std::vector<int32_t> idx(3 * n);
+  check(ks_esdf_changed_blocks(ctx_, idx.data(), n, &n), "ks_esdf_changed_blocks");
+  downloadEsdfBlocks(idx, changed);
+  return true;
+}
+
+void HipSemanticTsdfIntegrator::downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out) {
+  const size_t n = idx.size() / 3, vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
   std::vector<EsdfVoxel> all(n * nv);
   check(ks_esdf_download_blocks(ctx_, idx.data(), n, all.data()), "ks_esdf_download_blocks");
   out->resize(n);
@@ -290,7 +308,6 @@ bool HipSemanticTsdfIntegrator::updateEsdf(const EsdfOptions& options, std::vect
     (*out)[i].index = vxb::BlockIndex(idx[3 * i], idx[3 * i + 1], idx[3 * i + 2]);
     (*out)[i].voxels.assign(all.begin() + i * nv, all.begin() + (i + 1) * nv);
   }
-  return true;
 }
 
 HipSemanticTsdfIntegrator::Workers::~Workers() {

@@ -131,10 +131,17 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
     std::vector<EsdfVoxel> voxels;   ///< voxels_per_side^3, x + vps * (y + vps * z)
   };
   /// Computes the ESDF of the whole map ON THE DEVICE, as it is after the frames in flight, and hands back every block of
-  /// the map (ascending by x, y, z).  Needs NO syncLayers().  Batch only: what EsdfServer::updateEsdfBatch does at the end
-  /// of the reference's offline program ("ESDF").  Returns true when `out` is not empty.
+  /// the map (ascending by x, y, z).  Needs NO syncLayers().  What EsdfServer::updateEsdfBatch does at the end of the
+  /// reference's offline program ("ESDF"), and the first call of a server that keeps an ESDF up to date.
+  /// Returns true when `out` is not empty.
   bool updateEsdf(const EsdfOptions& options, std::vector<EsdfBlock>* out);
   const ks_esdf_stats& lastEsdfStats() const { return last_esdf_stats_; }
+  /// Brings the ESDF of the last updateEsdf() up to date with the map ON THE DEVICE (ks_esdf_refresh: only the tiles that
+  /// the tiles written since can reach are recomputed, with the options of that updateEsdf()) and hands back only the blocks
+  /// that hold a recomputed tile, with their records (ascending by x, y, z): what the timer of an ESDF server calls.  The
+  /// records of every other block are what they were.  Returns true when `changed` is not empty.
+  bool refreshEsdf(std::vector<EsdfBlock>* changed);
+  const ks_esdf_refresh_stats& lastEsdfRefreshStats() const { return last_esdf_refresh_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -148,6 +155,8 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_frame_stats last_stats_{};
   ks_mesh_stats last_mesh_stats_{};
   ks_esdf_stats last_esdf_stats_{};
+  ks_esdf_refresh_stats last_esdf_refresh_stats_{};
+  void downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out);
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand
   struct Staging {

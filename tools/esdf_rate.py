@@ -10,6 +10,9 @@ stream synchronisation of its own):
         rocprofv3 --kernel-trace --stats -d DIR -- python tools/esdf_rate.py --trace-child
         python tools/esdf_rate.py --merge-kernel-stats DIR/**/*kernel_stats.csv
       with the box size and the fraction of the 8 TB/s roofline the box traffic of each pass amounts to.
+  (5) the incremental refresh: one more frame of the ring is integrated (not timed), then ks_esdf_refresh is timed and after it
+      a full ks_esdf_update of the same map, --reps times with a new frame each; the share of the tiles the refresh recomputed
+      and its work space beside the medians.  (The order is fixed: an update before the refresh would leave it nothing to do.)
 Nothing is gated on these numbers.  Writes profiles/esdf_rate.json (or --out)."""
 import argparse
 import csv
@@ -134,6 +137,27 @@ def main():
             for k, v in got.items():
                 t[k].append(v)
     stats = {k: ([int(v) for v in getattr(st, k)] if k == "box_voxels" else int(getattr(st, k))) for k, _ in B.KsEsdfStats._fields_}
+    # (5): the store is current after the loop above; every repetition integrates the next frame of the ring
+    more = bench.make_frames(bench.WORKLOADS["C2"], range(a.frames, a.frames + a.warmup + a.reps))
+    rs = B.KsEsdfRefreshStats()
+    t5 = dict(refresh=[], update=[])
+    shares, rooms, stale = [], [], []
+    for r, f in enumerate(more):
+        g.integrate(f.T_G_C, f.xyz, f.rgba, f.labels)
+        got = dict(refresh=timed(lambda: L.ks_esdf_refresh(g._h, 0, C.byref(rs))))
+        got["update"] = timed(lambda: L.ks_esdf_update(g._h, C.byref(ec), C.byref(st)))
+        assert all(getattr(rs, k) == getattr(st, k) for k in ("voxels_observed", "voxels_fixed", "voxels_clamped")), "refresh and update disagree"
+        if r >= a.warmup:
+            for k, v in got.items():
+                t5[k].append(v)
+            shares.append(rs.tiles_recomputed / max(rs.tiles_total, 1))
+            stale.append(rs.tiles_stale / max(rs.tiles_total, 1))
+            rooms.append(int(rs.workspace_bytes))
+    v = {"refresh_ms": med(t5["refresh"]), "update_ms": med(t5["update"]),
+         "refresh_over_update": round(statistics.median(t5["refresh"]) / statistics.median(t5["update"]), 4),
+         "tiles_stale_over_total": round(statistics.median(stale), 4), "tiles_recomputed_over_total": round(statistics.median(shares), 4),
+         "workspace_bytes": int(statistics.median(rooms)), "update_workspace_bytes": int(st.workspace_bytes), "tiles_total": int(rs.tiles_total),
+         "note": "one more ring frame integrated before every refresh; the update after it recomputes the same map from scratch"}
     ii = med([u + d for u, d in zip(t["update"], t["download"])])
     out = {
         "workload": "C2", "frames_integrated": a.frames, "reps": a.reps, "warmup": a.warmup,
@@ -143,6 +167,7 @@ def main():
         "stats": stats,
         "i_esdf_update_ms": med(t["update"]), "esdf_download_ms": med(t["download"]), "ii_update_plus_download_ms": ii,
         "iii_ks_download_blocks_ms": med(t["layers"]), "ii_below_iii": ii < med(t["layers"]),
+        "v_refresh_after_one_frame": v,
         "note": "wall-clock around synchronous calls, candidates alternating in one process; (iii) is existing code, unchanged by the ESDF",
     }
     for p in (p_esdf, p_tsdf, p_sem):

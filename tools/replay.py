@@ -4,9 +4,9 @@
 bag (or generate the synthetic stand-in), compose T_G_C = T_G_B * T_B_C per depth image, integrate depth + labels on
 the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  The semantic mesh — what the reference's executable
 generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every, and the
-batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf; map saving stays on the host side of the
-drop-in boundary (out of scope).
-  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz]
+batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf, and kept up to date while frames stream in
+(ks_esdf_refresh) with --esdf-every; map saving stays on the host side of the drop-in boundary (out of scope).
+  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -40,6 +40,8 @@ def main():
     ap.add_argument("--mesh-every", type=int, default=0, metavar="N", help="refresh the mesh on the device (only_stale) every N frames")
     ap.add_argument("--esdf", metavar="OUT.npz", help="compute the batch ESDF with nearest-surface labels at the end of the replay and write it "
                     "(block_indices (N, 3), distance / flags / label (N, vps^3) in host block layout, voxel_size, voxels_per_side)")
+    ap.add_argument("--esdf-every", type=int, default=0, metavar="N", help="keep an ESDF up to date on the device: ks_esdf_update at the first tick, "
+                    "ks_esdf_refresh every N frames after it (with --esdf the file holds the refreshed ESDF)")
     ap.add_argument("--esdf-max-distance", type=float, default=2.0, metavar="M")
     ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
     a = ap.parse_args()
@@ -66,11 +68,21 @@ def main():
     upd = 0
 
     refresh_s, refreshes, n_seen = 0.0, [], 0
+    esdf_s, esdf_ticks = 0.0, []
+    esdf_cfg = dict(min_distance_m=a.esdf_min_distance, max_distance_m=a.esdf_max_distance)
 
     def acc(fr, T, st):
-        nonlocal upd, refresh_s, n_seen
+        nonlocal upd, refresh_s, n_seen, esdf_s
         upd += st.n_voxel_updates
         n_seen += 1
+        if a.esdf_every and n_seen % a.esdf_every == 0:
+            t1 = time.perf_counter()
+            if esdf_ticks:
+                es = integ.esdf_refresh()
+            else:
+                es = dict(integ.esdf_update(**esdf_cfg), tiles_recomputed=None)
+            esdf_s += time.perf_counter() - t1
+            esdf_ticks.append(es)
         if a.mesh_every and n_seen % a.mesh_every == 0:
             t1 = time.perf_counter()
             m = integ.mesh(only_stale=True)        # (completes the frames in flight, like every query)
@@ -88,6 +100,10 @@ def main():
         print(f"{len(refreshes)} mesh refreshes (only_stale, incl. the download) in {refresh_s * 1e3:.1f} ms of the above: "
               f"{refresh_s / len(refreshes) * 1e3:.2f} ms each; last: {refreshes[-1][0]} of {refreshes[-1][1]} blocks re-meshed, "
               f"{refreshes[-1][2]} triangles")
+    if len(esdf_ticks) > 1:
+        last = esdf_ticks[-1]
+        print(f"1 ESDF update and {len(esdf_ticks) - 1} refreshes in {esdf_s * 1e3:.1f} ms of the above; last refresh: {last['tiles_recomputed']} of "
+              f"{last['tiles_total']} tiles recomputed ({last['tiles_stale']} stale), work space {last['workspace_bytes'] / 2 ** 20:.1f} MiB")
     if a.mesh:
         from kimera_semantics_amd.mesh import write_ply
         t1 = time.perf_counter()
@@ -98,12 +114,18 @@ def main():
               f"{t_mesh * 1e3:.2f} ms (extraction + download) -> {a.mesh}")
     if a.esdf:
         t1 = time.perf_counter()
-        idx, rec, st = integ.esdf(min_distance_m=a.esdf_min_distance, max_distance_m=a.esdf_max_distance)
+        if esdf_ticks:   # the stored ESDF brought up to date with the last frames
+            st = integ.esdf_refresh()
+            idx = integ.block_indices()
+            rec = integ.esdf_blocks(idx)
+        else:
+            idx, rec, st = integ.esdf(**esdf_cfg)
         t_esdf = time.perf_counter() - t1
         np.savez_compressed(a.esdf, block_indices=idx, distance=rec["distance"], flags=rec["flags"], label=rec["label"],
                             voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+        how = f"{st['tiles_recomputed']} of {st['tiles_total']} tiles recomputed" if esdf_ticks else f"box {st['box_voxels']}"
         print(f"esdf: {st['voxels_observed']} observed voxels ({st['voxels_fixed']} in the band, {st['voxels_clamped']} at +-{a.esdf_max_distance} m), "
-              f"box {st['box_voxels']}, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_esdf * 1e3:.2f} ms (update + download) -> {a.esdf}")
+              f"{how}, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_esdf * 1e3:.2f} ms ({'refresh' if esdf_ticks else 'update'} + download) -> {a.esdf}")
 
 
 if __name__ == "__main__":
