@@ -367,6 +367,43 @@ int ks_esdf_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, void*
 int ks_esdf_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, float* distance, uint8_t* flags,
                   uint8_t* label /* any may be NULL */);
 
+/* ---- view rendering: what the map looks like from a camera pose (new: the reference has no such product; a caller of it
+ * downloads the layers and ray-casts on the host) ----
+ * The contract is DESIGN.md, section "View rendering"; every operation is f32 in the order written there.  In short, for
+ * pixel (u, v) of a width x height image, index v * width + u, with constant_x = (float)(1.0 / (double)fx) (the f32 format of
+ * ks_integrate_depth), constant_y alike: dc = (((float)u - cx) * constant_x, ((float)v - cy) * constant_y, 1), uc = dc / |dc|,
+ * dg = uc rotated by T_G_C, o = its translation, p(r) = o + r * dg.
+ * SAMPLE S(p): g = p * voxel_size_inv - 0.5, i = floorf(g), f = g - i per axis; the eight voxels i + {0, 1}; VALID if every
+ * corner index lies inside the packed range (|index| < 2^20 - 1, as ks_esdf_query), in a resident tile, with weight >=
+ * min_weight; the value interpolates the distances along x, then y, then z, each step a + f * (b - a).
+ * MARCH: r = min_range_m; while r <= max_range_m: s = S(p(r)); a valid s <= 0 right after a valid s_prev > 0 (at r_prev) is a
+ * HIT at r_hit = r_prev + (r - r_prev) * (s_prev / (s_prev - s)); otherwise r += (valid and s > 0) ? fmaxf(s, voxel_size) :
+ * voxel_size.  A NaN distance counts as invalid.  A ray that starts behind a surface, or leaves one, reports nothing there.
+ * AT A HIT, p_hit = p(r_hit): depth = r_hit * uc.z (z-depth in the camera frame, what ks_integrate_depth takes); label and
+ * rgba = dword 3 and dword 2 of the record of the voxel whose cell contains p_hit (floorf(p * voxel_size_inv + 1e-6), as
+ * ks_esdf_query; a label of 255 shows as 0; both 0 if that tile is not resident); normal (world frame) = g / |g| with
+ * g_k = S(p_hit + h e_k) - S(p_hit - h e_k), h = voxel_size, |g|^2 = (gx gx + gy gy) + gz gz — (0, 0, 0) if one of the six
+ * samples is invalid or |g|^2 is not > 0; it points towards positive distance.
+ * A MISS: depth = NaN, label = 255, rgba = 0, normal = 0 — the depth image can go straight back to ks_integrate_depth, which
+ * drops non-finite pixels.  stats: pixels_hit + pixels_missed = width * height; samples = march samples over all pixels (an
+ * integer sum).  Two calls on the same map give the same bytes.  Rendering only READS the map: the `updated` and `dirty`
+ * flags, both stale bits, the stored mesh and the stored ESDF stay as they were.
+ * ks_render_view          host outputs (any of the four may be NULL, not all); completes the frames in flight first.
+ * ks_render_view_device   the same into DEVICE buffers, enqueued on ks_stream(ctx) after the frames in flight have completed;
+ *                         the host waits for the kernel only when stats is non-NULL.
+ * Errors: KS_ERR_INVALID_ARG (width or height outside 1..8192; a non-finite K, fx or fy not positive; min_weight, min_range_m
+ * or max_range_m not a finite positive number; min_range_m >= max_range_m; max_range_m / voxel_size > 4096; all four outputs
+ * NULL), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact), KS_ERR_HIP.  An empty map is no error: every
+ * pixel misses.  Multi-GPU: each context renders the tiles it holds; a ray sees nothing of the tiles of other owners. */
+typedef struct ks_render_config { float min_weight, min_range_m, max_range_m; } ks_render_config;
+typedef struct ks_render_stats { uint64_t pixels_hit, pixels_missed, samples; } ks_render_stats;
+int ks_render_default_config(ks_render_config* cfg); /* 1e-4, 0.1 m, 10 m */
+int ks_render_view(ks_ctx* ctx, const float T_G_C[7], const float K[4] /* fx, fy, cx, cy */, int width, int height,
+                   const ks_render_config* cfg, float* depth, uint8_t* labels, uint8_t* rgba /* 4 per pixel */,
+                   float* normals /* 3 per pixel */, ks_render_stats* stats /* may be NULL */);
+int ks_render_view_device(ks_ctx* ctx, const float T_G_C[7], const float K[4], int width, int height, const ks_render_config* cfg,
+                          float* d_depth, uint8_t* d_labels, uint8_t* d_rgba, float* d_normals, ks_render_stats* stats);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
     "ks_esdf_refresh", "ks_esdf_changed_blocks",
+    "ks_render_default_config", "ks_render_view", "ks_render_view_device",
 ]
 
 
@@ -110,6 +111,14 @@ class KsEsdfRefreshStats(C.Structure):
 ESDF_DTYPE = np.dtype([("distance", "<f4"), ("flags", "u1"), ("label", "u1"), ("pad", "u1", (2,))])
 
 
+class KsRenderConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("min_range_m", C.c_float), ("max_range_m", C.c_float)]
+
+
+class KsRenderStats(C.Structure):
+    _fields_ = [("pixels_hit", C.c_uint64), ("pixels_missed", C.c_uint64), ("samples", C.c_uint64)]
+
+
 class KsProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("frames", C.c_uint64),
                 ("updates", C.c_uint64), ("points", C.c_uint64), ("apply_kernel_ms", C.c_double),
@@ -121,7 +130,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -197,6 +206,9 @@ def lib():
         L.ks_esdf_query.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         L.ks_esdf_refresh.argtypes = [vp, C.c_uint64, C.POINTER(KsEsdfRefreshStats)]
         L.ks_esdf_changed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_render_default_config.argtypes = [C.POINTER(KsRenderConfig)]
+        L.ks_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
+        L.ks_render_view_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
         _lib = L
     return _lib
 
@@ -437,6 +449,40 @@ class HipIntegrator:
         out = np.zeros(n, dtype=ESDF_DTYPE)
         out["distance"], out["flags"], out["label"] = d, f, l
         return out
+
+    def render_config(self, **cfg) -> KsRenderConfig:
+        rc = KsRenderConfig()
+        lib().ks_render_default_config(C.byref(rc))
+        for k, v in cfg.items():
+            if k not in ("min_weight", "min_range_m", "max_range_m"):
+                raise AttributeError(k)
+            if v is not None:
+                setattr(rc, k, v)
+        return rc
+
+    def render(self, T_G_C, K, width, height, min_weight=None, min_range_m=None, max_range_m=None, normals=True):
+        """ks_render_view: the map seen from the camera pose T_G_C with intrinsics K = (fx, fy, cx, cy).  Returns
+        (depth (H, W) f32 z-depth, NaN at a miss; labels (H, W) u8, 255 at a miss; rgba (H, W, 4) u8; normals (H, W, 3) f32 in
+        the world frame, or None with normals=False; stats dict).  The contract is DESIGN.md, section "View rendering"."""
+        T = np.ascontiguousarray(T_G_C, dtype=np.float32)
+        Kc = np.ascontiguousarray(K, dtype=np.float32)
+        rc, st = self.render_config(min_weight=min_weight, min_range_m=min_range_m, max_range_m=max_range_m), KsRenderStats()
+        w, h = int(width), int(height)
+        shape = (max(h, 0), max(w, 0))
+        depth, labels, rgba = np.zeros(shape, np.float32), np.zeros(shape, np.uint8), np.zeros(shape + (4,), np.uint8)
+        nrm = np.zeros(shape + (3,), np.float32) if normals else None
+        self._chk(lib().ks_render_view(self._h, _ptr(T), _ptr(Kc), w, h, C.byref(rc), _ptr(depth), _ptr(labels), _ptr(rgba), _ptr(nrm), C.byref(st)))
+        return depth, labels, rgba, nrm, {k: int(getattr(st, k)) for k, _ in KsRenderStats._fields_}
+
+    def render_device(self, T_G_C, K, width, height, d_depth: int, d_labels: int, d_rgba: int, d_normals: int, stats=True, **cfg):
+        """ks_render_view_device: raw device addresses (e.g. torch.Tensor.data_ptr()); 0 / None = not wanted.  The kernel is
+        enqueued on self.stream; with stats=False the host does not wait for it and None is returned."""
+        T = np.ascontiguousarray(T_G_C, dtype=np.float32)
+        Kc = np.ascontiguousarray(K, dtype=np.float32)
+        rc, st = self.render_config(**cfg), KsRenderStats()
+        self._chk(lib().ks_render_view_device(self._h, _ptr(T), _ptr(Kc), int(width), int(height), C.byref(rc), d_depth or None, d_labels or None,
+                                              d_rgba or None, d_normals or None, C.byref(st) if stats else None))
+        return {k: int(getattr(st, k)) for k, _ in KsRenderStats._fields_} if stats else None
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----
     TILE_BYTES = 65536

@@ -70,6 +70,7 @@ using namespace ksd;
 #include "ks_k_io.h"
 #include "ks_k_mesh.h"
 #include "ks_k_esdf.h"
+#include "ks_k_render.h"
 
 using namespace ksk;
 
@@ -501,6 +502,11 @@ struct ks_ctx {
   DevBuf<uint64_t> esdf_bricks[2];         // refresh: the bricks of lists X and Y
   DevBuf<uint64_t> esdf_lists;             // ... the sorted positions of X | Y | Z
   DevBuf<uint32_t> esdf_zslots;            // ... the pool slot of each position of Z
+  // ks_render_view (ks_k_render.h): the images of the host-pointer call before they are copied out, and the three counters
+  DevBuf<float> render_depth, render_normals;
+  DevBuf<uint32_t> render_rgba;
+  DevBuf<uint8_t> render_labels;
+  DevBuf<unsigned long long> render_counters;
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -3525,6 +3531,108 @@ int ks_esdf_query(ks_ctx* c, const float* xyz, size_t n, float* distance, uint8_
     }
   }
   HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+// ---- view rendering ("View rendering"; ks_k_render.h) -------------------------------------------
+int ks_render_default_config(ks_render_config* r) {
+  if (!r) return KS_ERR_INVALID_ARG;
+  r->min_weight = 1e-4f;
+  r->min_range_m = 0.1f;
+  r->max_range_m = 10.0f;
+  return KS_OK;
+}
+
+// the checks of both calls, then the kernel on the context's stream into DEVICE images; the host is not waited for here
+static int render_enqueue(ks_ctx* c, const char* who, const float T[7], const float K[4], int width, int height, const ks_render_config* r,
+                          float* d_depth, uint8_t* d_labels, uint8_t* d_rgba, float* d_normals) {
+  auto refuse = [&](const char* why) {
+    c->err = std::string(who) + ": " + why;
+    return KS_ERR_INVALID_ARG;
+  };
+  if (width < 1 || width > 8192 || height < 1 || height > 8192) return refuse("width and height must lie in 1..8192");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(K[k])) return refuse("K must be finite");
+  if (!(K[0] > 0.0f) || !(K[1] > 0.0f)) return refuse("fx and fy must be positive");
+  const float par[3] = {r->min_weight, r->min_range_m, r->max_range_m};
+  for (float v : par)
+    if (!std::isfinite(v) || !(v > 0.0f)) return refuse("min_weight, min_range_m and max_range_m must be finite positive numbers");
+  if (r->min_range_m >= r->max_range_m) return refuse("min_range_m must be below max_range_m");
+  if (r->max_range_m / c->cfg.voxel_size > 4096.0f) return refuse("max_range_m is more than 4096 voxels");
+  if (!d_depth && !d_labels && !d_rgba && !d_normals) return refuse("all four outputs are NULL");
+  if (c->shard_export) {
+    c->err = std::string(who) + ": a marcher context of ks_integrate_round_exact holds no voxel data";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (int rc = quiesce(c)) return rc;
+  if (int rc = c->render_counters.reserve(c, 3, 3)) return rc;
+  RenderView V{};
+  V.T.w = T[0];
+  V.T.v = {T[1], T[2], T[3]};
+  V.T.t = {T[4], T[5], T[6]};
+  V.cx = K[2];
+  V.cy = K[3];
+  V.constant_x = (float)(1.0 / (double)K[0]);   // as the f32 depth format of ks_integrate_depth
+  V.constant_y = (float)(1.0 / (double)K[1]);
+  V.width = width;
+  V.height = height;
+  V.voxel_size = c->cfg.voxel_size;
+  V.voxel_size_inv = c->voxel_size_inv;
+  V.min_weight = r->min_weight;
+  V.min_range = r->min_range_m;
+  V.max_range = r->max_range_m;
+  V.n_tiles = c->tiles_initialised;
+  V.depth = d_depth;
+  V.labels = d_labels;
+  V.rgba = (uint32_t*)d_rgba;
+  V.normals = d_normals;
+  V.counters = c->render_counters;
+  HIPCHK(c, hipMemsetAsync(c->render_counters, 0, 3 * sizeof(unsigned long long), c->stream));
+  hipLaunchKernelGGL(k_render_view, dim3((uint32_t)((width + 15) / 16), (uint32_t)((height + 15) / 16)), dim3(256), 0, c->stream, c->table, c->pool, V);
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+// waits for the stream and reads the three counters
+static int render_stats(ks_ctx* c, ks_render_stats* stats) {
+  unsigned long long counts[3] = {0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(counts, c->render_counters, sizeof(counts), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  stats->pixels_hit = counts[0];
+  stats->pixels_missed = counts[1];
+  stats->samples = counts[2];
+  return KS_OK;
+}
+
+int ks_render_view_device(ks_ctx* c, const float T[7], const float K[4], int width, int height, const ks_render_config* r, float* d_depth,
+                          uint8_t* d_labels, uint8_t* d_rgba, float* d_normals, ks_render_stats* stats) {
+  if (!c || !T || !K || !r) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (int rc = render_enqueue(c, "ks_render_view_device", T, K, width, height, r, d_depth, d_labels, d_rgba, d_normals)) return rc;
+  return stats ? render_stats(c, stats) : KS_OK;
+}
+
+int ks_render_view(ks_ctx* c, const float T[7], const float K[4], int width, int height, const ks_render_config* r, float* depth,
+                   uint8_t* labels, uint8_t* rgba, float* normals, ks_render_stats* stats) {
+  if (!c || !T || !K || !r) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const size_t n = width > 0 && height > 0 && width <= 8192 && height <= 8192 ? (size_t)width * (size_t)height : 0;   // (0: refused below)
+  int rc;
+  if (n && depth && (rc = c->render_depth.reserve(c, n, n))) return rc;
+  if (n && labels && (rc = c->render_labels.reserve(c, n, n))) return rc;
+  if (n && rgba && (rc = c->render_rgba.reserve(c, n, n))) return rc;
+  if (n && normals && (rc = c->render_normals.reserve(c, 3 * n, 3 * n))) return rc;
+  if ((rc = render_enqueue(c, "ks_render_view", T, K, width, height, r, depth ? c->render_depth.get() : nullptr,
+                           labels ? c->render_labels.get() : nullptr, rgba ? (uint8_t*)c->render_rgba.get() : nullptr,
+                           normals ? c->render_normals.get() : nullptr)))
+    return rc;
+  hipStream_t st = c->stream;
+  if (depth) HIPCHK(c, hipMemcpyAsync(depth, c->render_depth, n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (labels) HIPCHK(c, hipMemcpyAsync(labels, c->render_labels, n, hipMemcpyDeviceToHost, st));
+  if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->render_rgba, n * 4, hipMemcpyDeviceToHost, st));
+  if (normals) HIPCHK(c, hipMemcpyAsync(normals, c->render_normals, 3 * n * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (stats) return render_stats(c, stats);
+  HIPCHK(c, hipStreamSynchronize(st));
   return KS_OK;
 }
 

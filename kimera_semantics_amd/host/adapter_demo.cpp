@@ -104,6 +104,7 @@ int main(int argc, char** argv) {
   const char* esdf_refresh_path = std::getenv("KS_DEMO_ESDF_REFRESH");
   using EsdfBlock = kimera::HipSemanticTsdfIntegrator::EsdfBlock;
   std::map<std::array<int32_t, 3>, EsdfBlock> esdf_kept;   // (ascending by x, y, z)
+  float last_T[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // pose of the last frame read (KS_DEMO_RENDER)
   for (uint32_t f = 0; f < n_frames; ++f) {
     if (esdf_refresh_path && f == n_frames / 2) {
       auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
@@ -138,6 +139,7 @@ int main(int argc, char** argv) {
     float T[7];
     uint32_t n;
     if (std::fread(T, 4, 7, in) != 7 || std::fread(&n, 4, 1, in) != 1) return 3;
+    std::memcpy(last_T, T, sizeof(T));
     vxb::Pointcloud pts(n);
     vxb::Colors cols(n);
     std::vector<float> xyz(3 * size_t(n));
@@ -226,6 +228,37 @@ int main(int argc, char** argv) {
     const ks_esdf_stats& es = hip->lastEsdfStats();
     std::printf("adapter_demo: updateEsdf %.3f ms, %u blocks, %llu observed voxels, %llu in the band\n", ms, n_esdf_blocks,
                 (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
+  }
+
+  // KS_DEMO_RENDER=<file>: the map seen from the LAST frame's pose, made on the device without any layer sync (renderView;
+  // 128 x 96 pixels, fx = fy = 64, cx = 63.5, cy = 47.5), written as { u32 width, height; f32 T_G_C[7]; f32 K[4];
+  // f32 depth[w h]; u8 label[w h]; Color[w h]; Point normal[w h]; u64 pixels_hit, pixels_missed, samples }
+  if (const char* render_path = std::getenv("KS_DEMO_RENDER")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip || n_frames == 0) return 8;
+    const uint32_t rw = 128, rh = 96;
+    const float K[4] = {64.0f, 64.0f, 63.5f, 47.5f};
+    kimera::HipSemanticTsdfIntegrator::RenderedView view;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->renderView(vxb::Transformation(last_T[0], last_T[1], last_T[2], last_T[3], vxb::Point(last_T[4], last_T[5], last_T[6])), K[0], K[1],
+                    K[2], K[3], rw, rh, kimera::HipSemanticTsdfIntegrator::RenderOptions(), &view);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* rf = std::fopen(render_path, "wb");
+    if (!rf) return 9;
+    const ks_render_stats& rs = hip->lastRenderStats();
+    const uint64_t counts[3] = {rs.pixels_hit, rs.pixels_missed, rs.samples};
+    std::fwrite(&rw, 4, 1, rf);
+    std::fwrite(&rh, 4, 1, rf);
+    std::fwrite(last_T, 4, 7, rf);
+    std::fwrite(K, 4, 4, rf);
+    std::fwrite(view.depth.data(), 4, view.depth.size(), rf);
+    std::fwrite(view.labels.data(), 1, view.labels.size(), rf);
+    std::fwrite(view.colors.data(), sizeof(vxb::Color), view.colors.size(), rf);
+    std::fwrite(view.normals.data(), sizeof(vxb::Point), view.normals.size(), rf);
+    std::fwrite(counts, 8, 3, rf);
+    std::fclose(rf);
+    std::printf("adapter_demo: renderView %.3f ms, %u x %u pixels, %llu hit, %.1f samples per pixel\n", ms, rw, rh,
+                (unsigned long long)rs.pixels_hit, (double)rs.samples / (double)(rw * rh));
   }
 
   // ... the blocks of the refresh replace or join the ones kept since the update; the file has the format of KS_DEMO_ESDF

@@ -310,6 +310,31 @@ void HipSemanticTsdfIntegrator::downloadEsdfBlocks(const std::vector<int32_t>& i
   }
 }
 
+bool HipSemanticTsdfIntegrator::renderView(const vxb::Transformation& T_G_C, float fx, float fy, float cx, float cy, int width, int height,
+                                           const RenderOptions& options, RenderedView* out) {
+  CHECK_NOTNULL(out);
+  static_assert(sizeof(vxb::Point) == 12 && sizeof(vxb::Color) == 4, "image element layout");
+  const float T[7] = {T_G_C.qw(),          T_G_C.qvec().x(),        T_G_C.qvec().y(),       T_G_C.qvec().z(),
+                      T_G_C.getPosition().x(), T_G_C.getPosition().y(), T_G_C.getPosition().z()};
+  const float K[4] = {fx, fy, cx, cy};
+  ks_render_config rc;
+  ks_render_default_config(&rc);
+  rc.min_weight = options.min_weight;
+  rc.min_range_m = options.min_range_m;
+  rc.max_range_m = options.max_range_m;
+  const size_t n = width > 0 && height > 0 ? static_cast<size_t>(width) * static_cast<size_t>(height) : 0;
+  out->width = width;
+  out->height = height;
+  out->depth.assign(n, 0.0f);
+  out->labels.assign(n, 0);
+  out->colors.assign(n, vxb::Color());
+  out->normals.assign(options.normals ? n : 0, vxb::Point(0.0f, 0.0f, 0.0f));
+  check(ks_render_view(ctx_, T, K, width, height, &rc, out->depth.data(), out->labels.data(), reinterpret_cast<uint8_t*>(out->colors.data()),
+                       options.normals ? reinterpret_cast<float*>(out->normals.data()) : nullptr, &last_render_stats_),
+        "ks_render_view");
+  return last_render_stats_.pixels_hit != 0;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

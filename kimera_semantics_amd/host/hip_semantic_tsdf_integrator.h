@@ -142,6 +142,25 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// records of every other block are what they were.  Returns true when `changed` is not empty.
   bool refreshEsdf(std::vector<EsdfBlock>* changed);
   const ks_esdf_refresh_stats& lastEsdfRefreshStats() const { return last_esdf_refresh_stats_; }
+  /// What the map looks like from a camera pose (ks_render_view; the contract is DESIGN.md, "View rendering"): one ray per
+  /// pixel through the resident tiles ON THE DEVICE, as the map is after the frames in flight.  Needs NO syncLayers(): the
+  /// voxels stay in HBM, only the images travel.  depth is z-depth in the camera frame, NaN where the ray found no surface
+  /// (label 255, colour and normal 0 there); normals are in the world frame and stay empty with options.normals = false.
+  struct RenderOptions {
+    float min_weight = 1e-4f, min_range_m = 0.1f, max_range_m = 10.0f;
+    bool normals = true;
+  };
+  struct RenderedView {
+    int width = 0, height = 0;             ///< pixel (u, v) at v * width + u
+    std::vector<float> depth;
+    std::vector<uint8_t> labels;
+    std::vector<vxb::Color> colors;
+    std::vector<vxb::Point> normals;
+  };
+  /// Returns true when at least one pixel hit a surface.
+  bool renderView(const vxb::Transformation& T_G_C, float fx, float fy, float cx, float cy, int width, int height,
+                  const RenderOptions& options, RenderedView* out);
+  const ks_render_stats& lastRenderStats() const { return last_render_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -156,6 +175,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_mesh_stats last_mesh_stats_{};
   ks_esdf_stats last_esdf_stats_{};
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
+  ks_render_stats last_render_stats_{};
   void downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out);
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand

@@ -5,8 +5,10 @@ bag (or generate the synthetic stand-in), compose T_G_C = T_G_B * T_B_C per dept
 the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  The semantic mesh — what the reference's executable
 generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every, and the
 batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf, and kept up to date while frames stream in
-(ks_esdf_refresh) with --esdf-every; map saving stays on the host side of the drop-in boundary (out of scope).
-  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5]
+(ks_esdf_refresh) with --esdf-every; --render-every writes what the map looks like from the frame's own pose and intrinsics
+(ks_render_view: depth, labels, colours, normals) every N frames; map saving stays on the host side of the drop-in boundary (out of scope).
+  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
+      [--render-every 10 --render-out views/]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -44,7 +46,13 @@ def main():
                     "ks_esdf_refresh every N frames after it (with --esdf the file holds the refreshed ESDF)")
     ap.add_argument("--esdf-max-distance", type=float, default=2.0, metavar="M")
     ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
+    ap.add_argument("--render-every", type=int, default=0, metavar="N", help="render the map on the device from the frame's own pose and intrinsics "
+                    "every N frames (ks_render_view; completes the frames in flight)")
+    ap.add_argument("--render-out", metavar="DIR", help="where --render-every writes view_<frame>.npz (depth, labels, rgba, normals, T_G_C, K)")
+    ap.add_argument("--render-max-range", type=float, default=10.0, metavar="M")
     a = ap.parse_args()
+    if a.render_every and not a.render_out:
+        ap.error("--render-every needs --render-out")
     if a.bag:
         seq = FS.read_rosbag(a.bag, a.depth_topic, a.semantic_topic, a.camera_info_topic, a.sensor_frame, a.base_link_frame, a.world_frame)
     else:
@@ -70,9 +78,12 @@ def main():
     refresh_s, refreshes, n_seen = 0.0, [], 0
     esdf_s, esdf_ticks = 0.0, []
     esdf_cfg = dict(min_distance_m=a.esdf_min_distance, max_distance_m=a.esdf_max_distance)
+    render_s, renders = 0.0, []
+    if a.render_every:
+        os.makedirs(a.render_out, exist_ok=True)
 
     def acc(fr, T, st):
-        nonlocal upd, refresh_s, n_seen, esdf_s
+        nonlocal upd, refresh_s, n_seen, esdf_s, render_s
         upd += st.n_voxel_updates
         n_seen += 1
         if a.esdf_every and n_seen % a.esdf_every == 0:
@@ -83,6 +94,14 @@ def main():
                 es = dict(integ.esdf_update(**esdf_cfg), tiles_recomputed=None)
             esdf_s += time.perf_counter() - t1
             esdf_ticks.append(es)
+        if a.render_every and n_seen % a.render_every == 0:
+            hh, ww = fr.depth.shape
+            t1 = time.perf_counter()
+            depth, labels, rgba, normals, rs = integ.render(T, fr.K, ww, hh, max_range_m=a.render_max_range)
+            render_s += time.perf_counter() - t1
+            renders.append(rs)
+            np.savez_compressed(os.path.join(a.render_out, "view_%06d.npz" % n_seen), depth=depth, labels=labels, rgba=rgba, normals=normals,
+                                T_G_C=np.asarray(T, np.float32), K=np.asarray(fr.K, np.float32))
         if a.mesh_every and n_seen % a.mesh_every == 0:
             t1 = time.perf_counter()
             m = integ.mesh(only_stale=True)        # (completes the frames in flight, like every query)
@@ -104,6 +123,11 @@ def main():
         last = esdf_ticks[-1]
         print(f"1 ESDF update and {len(esdf_ticks) - 1} refreshes in {esdf_s * 1e3:.1f} ms of the above; last refresh: {last['tiles_recomputed']} of "
               f"{last['tiles_total']} tiles recomputed ({last['tiles_stale']} stale), work space {last['workspace_bytes'] / 2 ** 20:.1f} MiB")
+    if renders:
+        last = renders[-1]
+        print(f"{len(renders)} views rendered (incl. the download of the four images) in {render_s * 1e3:.1f} ms of the above: "
+              f"{render_s / len(renders) * 1e3:.2f} ms each; last: {last['pixels_hit']} of {last['pixels_hit'] + last['pixels_missed']} pixels hit, "
+              f"{last['samples'] / (last['pixels_hit'] + last['pixels_missed']):.1f} samples per pixel -> {a.render_out}")
     if a.mesh:
         from kimera_semantics_amd.mesh import write_ply
         t1 = time.perf_counter()
