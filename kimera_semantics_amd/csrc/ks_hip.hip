@@ -45,9 +45,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <set>
 #include <string>
-#include <tuple>
 #include <unordered_map>
 #include <vector>
 
@@ -2197,31 +2195,77 @@ int integrate_device(ks_ctx* c, const float Tq[7], const float* d_xyz, const uin
   return rc;
 }
 
-int collect_block_indices(ks_ctx* c, bool only_updated, bool reset, std::vector<int32_t>* out) {
+// ---- what the readers of the finished map share (block lists, mesh, ESDF) ----
+void sort_unique(std::vector<uint64_t>& v) {
+  std::sort(v.begin(), v.end());
+  v.erase(std::unique(v.begin(), v.end()), v.end());
+}
+// tile positions (pack_coord3 of tile coordinates) -> the words of their blocks (pack_coord3 of block indices), ascending (x, y, z) and unique
+std::vector<uint64_t> blocks_of_tiles(const std::vector<uint64_t>& tile_pos, int vps_shift) {
+  std::vector<uint64_t> blocks(tile_pos.size());
+  for (size_t i = 0; i < tile_pos.size(); ++i) {
+    int t[3];
+    unpack_coord3(tile_pos[i], t[0], t[1], t[2]);
+    blocks[i] = pack_coord3(t[0] >> vps_shift, t[1] >> vps_shift, t[2] >> vps_shift);
+  }
+  sort_unique(blocks);
+  return blocks;
+}
+// packed words -> int32 triples, in the order given
+void words_to_triples(const std::vector<uint64_t>& words, std::vector<int32_t>* out) {
+  out->resize(3 * words.size());
+  for (size_t i = 0; i < words.size(); ++i) unpack_coord3(words[i], (*out)[3 * i], (*out)[3 * i + 1], (*out)[3 * i + 2]);
+}
+
+// The tile directory of a quiesced context on the host: slot -> tile key, slot -> flag byte (a plane of Pool::updated).  A fetch is one blocking copy.
+struct TileSnapshot {
+  uint32_t nt;
+  std::vector<uint64_t> keys;
+  std::vector<uint8_t> flags;
+  explicit TileSnapshot(const ks_ctx* c) : nt(c->tiles_initialised) {}
+  int fetch_keys(ks_ctx* c) {   // (once: a second call finds them there)
+    if (keys.size() == nt) return KS_OK;
+    keys.resize(nt);
+    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    return KS_OK;
+  }
+  int fetch_flags(ks_ctx* c, const uint8_t* d_plane) {
+    flags.resize(nt);
+    if (nt) HIPCHK(c, hipMemcpy(flags.data(), d_plane, nt, hipMemcpyDeviceToHost));
+    return KS_OK;
+  }
+  void tile(uint32_t s, int t[3]) const { unpack_tile(keys[s], t[0], t[1], t[2]); }
+  // the blocks (blocks_of_tiles) of the tiles from slot `first` on whose flag byte has a bit of `mask`; mask 0: of all of them.
+  // The keys are fetched at the first such tile unless they are there: with no such tile they are not read at all
+  int blocks(ks_ctx* c, int vps_shift, uint32_t first, uint8_t mask, std::vector<uint64_t>* out) {
+    std::vector<uint64_t> tiles;
+    for (uint32_t s = first; s < nt; ++s) {
+      if (mask && !(flags[s] & mask)) continue;
+      if (int rc = fetch_keys(c)) return rc;
+      int t[3];
+      tile(s, t);
+      tiles.push_back(pack_coord3(t[0], t[1], t[2]));
+    }
+    *out = blocks_of_tiles(tiles, vps_shift);
+    return KS_OK;
+  }
+};
+
+// ks_num_blocks, ks_get_block_indices, ks_get_updated_block_indices: the blocks of all tiles, or of those flagged `updated`
+int collect_block_indices(ks_ctx* c, bool only_updated, bool reset, int32_t* out, size_t cap, size_t* n) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
   if (int rc = quiesce(c)) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
-  const uint32_t nt = c->tiles_initialised;
-  std::vector<uint64_t> keys(nt);
-  std::vector<uint8_t> upd(nt);
-  if (nt) {
-    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(upd.data(), c->pool.updated, nt, hipMemcpyDeviceToHost));
-    if (only_updated && reset) HIPCHK(c, hipMemset(c->pool.updated, 0, nt));
-  }
-  std::set<std::tuple<int32_t, int32_t, int32_t>> s;
-  for (uint32_t i = 0; i < nt; ++i) {
-    if (only_updated && !upd[i]) continue;
-    const uint64_t k = keys[i];
-    const int tx = (int)((k >> 36) & 0x3ffffu) - kTileBias, ty = (int)((k >> 18) & 0x3ffffu) - kTileBias,
-              tz = (int)(k & 0x3ffffu) - kTileBias;
-    s.insert({tx >> c->vps_shift, ty >> c->vps_shift, tz >> c->vps_shift});
-  }
-  out->clear();
-  for (const auto& t : s) {
-    out->push_back(std::get<0>(t));
-    out->push_back(std::get<1>(t));
-    out->push_back(std::get<2>(t));
-  }
+  TileSnapshot snap(c);
+  if (int rc = snap.fetch_keys(c)) return rc;
+  if (int rc = snap.fetch_flags(c, c->pool.updated)) return rc;
+  if (snap.nt && only_updated && reset) HIPCHK(c, hipMemset(c->pool.updated, 0, snap.nt));
+  std::vector<uint64_t> blocks;
+  if (int rc = snap.blocks(c, c->vps_shift, 0, only_updated ? 0xff : 0, &blocks)) return rc;
+  std::vector<int32_t> v;
+  words_to_triples(blocks, &v);
+  *n = v.size() / 3;
+  if (out) std::memcpy(out, v.data(), std::min(cap, *n) * 3 * sizeof(int32_t));
   return KS_OK;
 }
 
@@ -2734,34 +2778,9 @@ int ks_integrate_depth_device(ks_ctx* c, const float T[7], const void* d_depth, 
   return integrate_depth_impl(c, T, D, freespace, stats);
 }
 
-int ks_num_blocks(ks_ctx* c, size_t* n) {
-  if (!c || !n) return KS_ERR_INVALID_ARG;
-  std::vector<int32_t> v;
-  int rc = collect_block_indices(c, false, false, &v);
-  if (rc) return rc;
-  *n = v.size() / 3;
-  return KS_OK;
-}
-
-int ks_get_block_indices(ks_ctx* c, int32_t* out, size_t cap, size_t* n) {
-  if (!c || !n) return KS_ERR_INVALID_ARG;
-  std::vector<int32_t> v;
-  int rc = collect_block_indices(c, false, false, &v);
-  if (rc) return rc;
-  *n = v.size() / 3;
-  if (out) std::memcpy(out, v.data(), std::min(cap, *n) * 3 * sizeof(int32_t));
-  return KS_OK;
-}
-
-int ks_get_updated_block_indices(ks_ctx* c, int32_t* out, size_t cap, size_t* n, int reset) {
-  if (!c || !n) return KS_ERR_INVALID_ARG;
-  std::vector<int32_t> v;
-  int rc = collect_block_indices(c, true, reset != 0, &v);
-  if (rc) return rc;
-  *n = v.size() / 3;
-  if (out) std::memcpy(out, v.data(), std::min(cap, *n) * 3 * sizeof(int32_t));
-  return KS_OK;
-}
+int ks_num_blocks(ks_ctx* c, size_t* n) { return collect_block_indices(c, false, false, nullptr, 0, n); }
+int ks_get_block_indices(ks_ctx* c, int32_t* out, size_t cap, size_t* n) { return collect_block_indices(c, false, false, out, cap, n); }
+int ks_get_updated_block_indices(ks_ctx* c, int32_t* out, size_t cap, size_t* n, int reset) { return collect_block_indices(c, true, reset != 0, out, cap, n); }
 
 int ks_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, void* tsdf_out, void* sem_out) {
   if (!c || (n && !idx)) return KS_ERR_INVALID_ARG;
@@ -2863,14 +2882,73 @@ static int mesh_arena_reserve(ks_ctx* c, int a, size_t n_vertices) {
   c->mesh_cap[a] = cap;
   return KS_OK;
 }
-// block index <-> one sortable word (ascending word = ascending (x, y, z))
-static inline uint64_t mesh_block_key(int x, int y, int z) {
-  return ((uint64_t)(uint32_t)(x + kCoordBias) << 42) | ((uint64_t)(uint32_t)(y + kCoordBias) << 21) | (uint64_t)(uint32_t)(z + kCoordBias);
+static int holds_voxels(ks_ctx* c, const char* who) {
+  if (!c->shard_export) return KS_OK;
+  c->err = std::string(who) + ": a marcher context of ks_integrate_round_exact holds no voxel data";
+  return KS_ERR_UNSUPPORTED;
 }
-static inline void mesh_block_of(uint64_t k, int32_t out[3]) {
-  out[0] = (int32_t)((k >> 42) & 0x1fffffu) - kCoordBias;
-  out[1] = (int32_t)((k >> 21) & 0x1fffffu) - kCoordBias;
-  out[2] = (int32_t)(k & 0x1fffffu) - kCoordBias;
+// ks_mesh_changed_blocks, ks_esdf_changed_blocks: the count, and the triples when a buffer is given
+static int copy_block_list(ks_ctx* c, const char* who, const std::vector<int32_t>& blocks, int32_t* out_xyz, size_t cap, size_t* n) {
+  if (!n) return KS_ERR_INVALID_ARG;
+  *n = blocks.size() / 3;
+  if (out_xyz) {
+    if (cap < *n) {
+      c->err = std::string(who) + ": output buffer too small";
+      return KS_ERR_INVALID_ARG;
+    }
+    std::memcpy(out_xyz, blocks.data(), blocks.size() * sizeof(int32_t));
+  }
+  return KS_OK;
+}
+
+// The bookkeeping of a mesh update: pure arithmetic over block words (pack_coord3 of block indices; every vector ascending).
+struct MeshPlan {
+  std::vector<uint64_t> B, R;        // every block of the map; of them, the blocks to mesh
+  std::vector<uint32_t> dir_in;      // per block of B: {its number in R, 0}, or {0xffffffff, the vertices it keeps}
+  std::vector<uint32_t> old_first;   // per block of B: where the vertices it keeps are now
+};
+// blocks, old_dir: the block list so far and the directory of the last update (in the same order); fresh, stale: the blocks of the
+// tiles that joined the map, and of those written, since then; full: mesh everything and keep nothing
+static MeshPlan mesh_plan(const std::vector<uint64_t>& blocks, const std::vector<ks_mesh_block>& old_dir, const std::vector<uint64_t>& fresh,
+                          const std::vector<uint64_t>& stale, bool full) {
+  MeshPlan P;
+  std::vector<uint64_t>&B = P.B, &R = P.R;
+  // 1) the block list grows by the tiles that joined the map
+  std::set_union(blocks.begin(), blocks.end(), fresh.begin(), fresh.end(), std::back_inserter(B));
+  // 2) what to mesh: everything, or the blocks with a stale tile plus the up to seven blocks at -x / -y / -z offsets whose
+  //    border cubes read it
+  if (full) {
+    R = B;
+  } else {
+    std::vector<uint64_t> cand;
+    for (uint64_t w : stale) {
+      int b[3];
+      unpack_coord3(w, b[0], b[1], b[2]);
+      for (int o = 0; o < 8; ++o) cand.push_back(pack_coord3(b[0] - (o & 1), b[1] - ((o >> 1) & 1), b[2] - (o >> 2)));
+    }
+    sort_unique(cand);
+    std::set_intersection(cand.begin(), cand.end(), B.begin(), B.end(), std::back_inserter(R));
+  }
+  // 3) the new directory: re-meshed blocks by their number in R, kept ones with the segment they have
+  const size_t nb = B.size(), nr = R.size();
+  auto old_word = [&](size_t io) { return pack_coord3(old_dir[io].block[0], old_dir[io].block[1], old_dir[io].block[2]); };
+  P.dir_in.assign(2 * nb, 0u);
+  P.old_first.assign(nb, 0u);
+  size_t ir = 0, io = 0;
+  for (size_t i = 0; i < nb; ++i) {
+    while (ir < nr && R[ir] < B[i]) ++ir;
+    if (ir < nr && R[ir] == B[i]) {
+      P.dir_in[2 * i] = (uint32_t)ir;
+      continue;
+    }
+    P.dir_in[2 * i] = 0xffffffffu;
+    while (io < old_dir.size() && old_word(io) < B[i]) ++io;
+    if (!full && io < old_dir.size() && old_word(io) == B[i]) {
+      P.dir_in[2 * i + 1] = old_dir[io].n_vertices;
+      P.old_first[i] = old_dir[io].first_vertex;
+    }
+  }
+  return P;
 }
 
 int ks_mesh_default_config(ks_mesh_config* m) {
@@ -2887,90 +2965,30 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
     c->err = "ks_mesh_update: min_weight must be a finite positive number";
     return KS_ERR_INVALID_ARG;
   }
-  if (c->shard_export) {
-    c->err = "ks_mesh_update: a marcher context of ks_integrate_round_exact holds no voxel data";
-    return KS_ERR_UNSUPPORTED;
-  }
+  if (int rc = holds_voxels(c, "ks_mesh_update")) return rc;
   if (int rc = quiesce(c)) return rc;
   hipStream_t st = c->stream;
-  const uint32_t nt = c->tiles_initialised;
   const int sh = c->vps_shift;
-  // 1) the block list grows by the tiles that joined the map since the last call
-  std::vector<uint64_t> keys(nt > c->mesh_tiles_seen ? nt : 0);   // (slot -> tile key; only read when something is new or stale)
-  std::vector<uint8_t> stale(nt);
-  if (nt) {
-    HIPCHK(c, hipMemcpy(stale.data(), c->pool.mesh_stale(), nt, hipMemcpyDeviceToHost));
-    hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleMesh);   // (the ESDF's bit stays)
-  }
-  auto tile_block = [&](uint64_t k) {
-    const int tx = (int)((k >> 36) & 0x3ffffu) - kTileBias, ty = (int)((k >> 18) & 0x3ffffu) - kTileBias, tz = (int)(k & 0x3ffffu) - kTileBias;
-    return mesh_block_key(tx >> sh, ty >> sh, tz >> sh);
-  };
-  if (nt > c->mesh_tiles_seen) {
-    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    std::vector<uint64_t> fresh;
-    for (uint32_t s = c->mesh_tiles_seen; s < nt; ++s) fresh.push_back(tile_block(keys[s]));
-    std::sort(fresh.begin(), fresh.end());
-    fresh.erase(std::unique(fresh.begin(), fresh.end()), fresh.end());
-    std::vector<uint64_t> all;
-    std::set_union(c->mesh_blocks.begin(), c->mesh_blocks.end(), fresh.begin(), fresh.end(), std::back_inserter(all));
-    c->mesh_blocks.swap(all);
-    c->mesh_tiles_seen = nt;
-  }
-  const std::vector<uint64_t>& B = c->mesh_blocks;
-  const size_t nb = B.size();
-  // 2) what to mesh: everything, or the blocks with a stale tile plus the up to seven blocks at -x / -y / -z offsets whose
-  //    border cubes read it
+  int rc;
+  // the stale flags, the tiles that joined the map since the last call, and what follows from them (mesh_plan)
+  TileSnapshot snap(c);
+  const uint32_t nt = snap.nt;
+  if ((rc = snap.fetch_flags(c, c->pool.mesh_stale()))) return rc;
+  if (nt) hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleMesh);   // (the ESDF's bit stays)
+  std::vector<uint64_t> fresh, stale;   // blocks of the tiles that joined the map since the last call, and of the stale ones
+  if ((rc = snap.blocks(c, sh, c->mesh_tiles_seen, 0, &fresh))) return rc;
   const bool full = !m->only_stale || !c->mesh_valid || m->min_weight != c->mesh_min_weight;
   c->mesh_valid = false;   // (a failure below leaves flags cleared that nothing has meshed: the next call starts over)
-  std::vector<uint64_t> R;
-  if (full) {
-    R = B;
-  } else {
-    bool any = false;
-    for (uint32_t s = 0; s < nt && !any; ++s) any = (stale[s] & kStaleMesh) != 0;
-    if (any && keys.empty()) {
-      keys.resize(nt);
-      HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    }
-    std::vector<uint64_t> cand;
-    for (uint32_t s = 0; s < nt; ++s) {
-      if (!(stale[s] & kStaleMesh)) continue;
-      int32_t b[3];
-      mesh_block_of(tile_block(keys[s]), b);
-      for (int o = 0; o < 8; ++o) cand.push_back(mesh_block_key(b[0] - (o & 1), b[1] - ((o >> 1) & 1), b[2] - (o >> 2)));
-    }
-    std::sort(cand.begin(), cand.end());
-    cand.erase(std::unique(cand.begin(), cand.end()), cand.end());
-    std::set_intersection(cand.begin(), cand.end(), B.begin(), B.end(), std::back_inserter(R));
-  }
-  const size_t nr = R.size();
-  // 3) the new directory: re-meshed blocks by their number in R, kept ones with the segment they have
+  if (!full && (rc = snap.blocks(c, sh, 0, kStaleMesh, &stale))) return rc;
+  MeshPlan P = mesh_plan(c->mesh_blocks, c->mesh_dir, fresh, stale, full);
+  c->mesh_blocks.swap(P.B);
+  c->mesh_tiles_seen = nt;
+  const std::vector<uint64_t>& B = c->mesh_blocks;
+  const std::vector<uint32_t>&dir_in = P.dir_in, &old_first = P.old_first;
+  const size_t nb = B.size(), nr = P.R.size();
   std::vector<ks_mesh_block> dir(nb);
-  std::vector<uint32_t> dir_in(2 * nb);
-  std::vector<uint32_t> old_first(nb, 0u);
-  {
-    size_t ir = 0, io = 0;
-    for (size_t i = 0; i < nb; ++i) {
-      mesh_block_of(B[i], dir[i].block);
-      dir[i].first_vertex = dir[i].n_vertices = 0;
-      while (ir < nr && R[ir] < B[i]) ++ir;
-      if (ir < nr && R[ir] == B[i]) {
-        dir_in[2 * i] = (uint32_t)ir;
-        dir_in[2 * i + 1] = 0;
-        continue;
-      }
-      dir_in[2 * i] = 0xffffffffu;
-      dir_in[2 * i + 1] = 0;
-      while (io < c->mesh_dir.size() && mesh_block_key(c->mesh_dir[io].block[0], c->mesh_dir[io].block[1], c->mesh_dir[io].block[2]) < B[i]) ++io;
-      if (!full && io < c->mesh_dir.size() && mesh_block_key(c->mesh_dir[io].block[0], c->mesh_dir[io].block[1], c->mesh_dir[io].block[2]) == B[i]) {
-        dir_in[2 * i + 1] = c->mesh_dir[io].n_vertices;
-        old_first[i] = c->mesh_dir[io].first_vertex;
-      }
-    }
-  }
-  c->mesh_changed.resize(3 * nr);
-  for (size_t r = 0; r < nr; ++r) mesh_block_of(R[r], &c->mesh_changed[3 * r]);
+  for (size_t i = 0; i < nb; ++i) unpack_coord3(B[i], dir[i].block[0], dir[i].block[1], dir[i].block[2]);
+  words_to_triples(P.R, &c->mesh_changed);
   unsigned long long degenerate = 0;
   uint32_t total = 0;
   const int from = c->mesh_cur, to = c->mesh_cur ^ 1;
@@ -2981,7 +2999,6 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
       c->err = "ks_mesh_update: too many blocks for one call";
       return KS_ERR_INVALID_ARG;
     }
-    int rc;
     if ((rc = mesh_scratch(c, 0, std::max<size_t>(nr, 1) * 12)) || (rc = mesh_scratch(c, 1, std::max<size_t>(nr, 1) * nvb)) ||
         (rc = mesh_scratch(c, 2, std::max<size_t>(nr, 1) * nvb * 4)) || (rc = mesh_scratch(c, 3, std::max<size_t>(nr, 1) * 4)) ||
         (rc = mesh_scratch(c, 4, std::max<size_t>(nr, 1) * 4)) || (rc = mesh_scratch(c, 5, nb * 8)) || (rc = mesh_scratch(c, 6, (nb + 1) * 4)) ||
@@ -3088,16 +3105,7 @@ int ks_mesh_download(ks_ctx* c, ks_mesh_block* blocks, size_t cap_blocks, float*
 }
 
 int ks_mesh_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
-  if (!c || !n) return KS_ERR_INVALID_ARG;
-  *n = c->mesh_changed.size() / 3;
-  if (out_xyz) {
-    if (cap < *n) {
-      c->err = "ks_mesh_changed_blocks: output buffer too small";
-      return KS_ERR_INVALID_ARG;
-    }
-    std::memcpy(out_xyz, c->mesh_changed.data(), c->mesh_changed.size() * sizeof(int32_t));
-  }
-  return KS_OK;
+  return c ? copy_block_list(c, "ks_mesh_changed_blocks", c->mesh_changed, out_xyz, cap, n) : KS_ERR_INVALID_ARG;
 }
 
 // ---- batch ESDF (ks_k_esdf.h) ----------------------------------------------------------------------------
@@ -3109,6 +3117,55 @@ int ks_esdf_default_config(ks_esdf_config* e) {
   e->max_distance_m = 2.0f;
   e->max_workspace_bytes = 8ull << 30;
   return KS_OK;
+}
+
+// The dense box of a batch update: pure arithmetic over the tile directory.
+struct EsdfBoxPlan {
+  int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};   // tiles [lo, hi] of the box
+  int r0[3], r1[3];                              // voxels [r0, r1) that get results, counted from the box's corner
+  uint64_t nbt[3] = {0, 0, 0};                   // tiles of the box along each axis; all 0: nothing to compute
+  uint64_t tiles() const { return nbt[0] * nbt[1] * nbt[2]; }
+  // the dense slot grid of the box: the pool slot of each of its tiles, 0xffffffff where none is resident
+  std::vector<uint32_t> slot_grid(const TileSnapshot& snap) const {
+    std::vector<uint32_t> grid(tiles(), 0xffffffffu);
+    for (uint32_t s = 0; s < snap.nt; ++s) {
+      int t[3];
+      snap.tile(s, t);
+      if (t[0] < lo[0] || t[0] > hi[0] || t[1] < lo[1] || t[1] > hi[1] || t[2] < lo[2] || t[2] > hi[2]) continue;
+      grid[((size_t)(t[2] - lo[2]) * nbt[1] + (size_t)(t[1] - lo[1])) * nbt[0] + (size_t)(t[0] - lo[0])] = s;
+    }
+    return grid;
+  }
+};
+// the bounding box of the resident tiles, in tiles; with a region: its tiles dilated by ceil(R / 8), clipped to that box.
+// tpb: tiles per block side; R: the reach in voxels
+static EsdfBoxPlan esdf_box_plan(const TileSnapshot& snap, const ks_esdf_config& e, int tpb, int R) {
+  EsdfBoxPlan P;
+  const uint32_t nt = snap.nt;
+  for (uint32_t s = 0; s < nt; ++s) {
+    int t[3];
+    snap.tile(s, t);
+    for (int a = 0; a < 3; ++a) {
+      if (s == 0 || t[a] < P.lo[a]) P.lo[a] = t[a];
+      if (s == 0 || t[a] > P.hi[a]) P.hi[a] = t[a];
+    }
+  }
+  bool empty = nt == 0;
+  for (int a = 0; a < 3; ++a) {
+    int64_t r0 = (int64_t)P.lo[a] * 8, r1 = ((int64_t)P.hi[a] + 1) * 8;   // voxels [r0, r1) that get results, in world voxel indices
+    if (e.use_region && nt) {
+      const int64_t t0 = (int64_t)e.region_min[a] * tpb, t1 = ((int64_t)e.region_max[a] + 1) * tpb - 1, grow = (R + 7) / 8;   // tiles [t0, t1]
+      r0 = std::max<int64_t>(r0, t0 * 8);
+      r1 = std::min<int64_t>(r1, (t1 + 1) * 8);
+      P.lo[a] = (int)std::max<int64_t>(P.lo[a], t0 - grow);
+      P.hi[a] = (int)std::min<int64_t>(P.hi[a], t1 + grow);
+    }
+    empty = empty || P.hi[a] < P.lo[a] || r1 <= r0;
+    P.r0[a] = (int)std::max<int64_t>(r0 - (int64_t)P.lo[a] * 8, 0);
+    P.r1[a] = (int)std::min<int64_t>(r1 - (int64_t)P.lo[a] * 8, ((int64_t)P.hi[a] - P.lo[a] + 1) * 8);
+  }
+  for (int a = 0; a < 3 && !empty; ++a) P.nbt[a] = (uint64_t)(P.hi[a] - P.lo[a] + 1);
+  return P;
 }
 
 int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
@@ -3131,52 +3188,17 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
         c->err = "ks_esdf_update: region_min exceeds region_max";
         return KS_ERR_INVALID_ARG;
       }
-  if (c->shard_export) {
-    c->err = "ks_esdf_update: a marcher context of ks_integrate_round_exact holds no voxel data";
-    return KS_ERR_UNSUPPORTED;
-  }
+  if (int rc = holds_voxels(c, "ks_esdf_update")) return rc;
   if (int rc = quiesce(c)) return rc;
   hipStream_t st = c->stream;
-  const uint32_t nt = c->tiles_initialised;
   int rc;
-  // 1) the bounding box of the resident tiles, in tiles; with a region: its tiles dilated by ceil(R / 8), clipped to that box
-  std::vector<uint64_t> keys(nt);
-  if (nt) HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
-  auto tile_of = [](uint64_t k, int t[3]) {
-    t[0] = (int)((k >> 36) & 0x3ffffu) - kTileBias;
-    t[1] = (int)((k >> 18) & 0x3ffffu) - kTileBias;
-    t[2] = (int)(k & 0x3ffffu) - kTileBias;
-  };
-  int lo[3] = {0, 0, 0}, hi[3] = {-1, -1, -1};   // tiles [lo, hi]
-  for (uint32_t s = 0; s < nt; ++s) {
-    int t[3];
-    tile_of(keys[s], t);
-    for (int a = 0; a < 3; ++a) {
-      if (s == 0 || t[a] < lo[a]) lo[a] = t[a];
-      if (s == 0 || t[a] > hi[a]) hi[a] = t[a];
-    }
-  }
-  int64_t r0[3], r1[3];   // voxels [r0, r1) that get results, in world voxel indices
-  for (int a = 0; a < 3; ++a) {
-    r0[a] = (int64_t)lo[a] * 8;
-    r1[a] = ((int64_t)hi[a] + 1) * 8;
-  }
-  if (e->use_region && nt) {
-    const int tpb = c->cfg.voxels_per_side / 8, grow = (R + 7) / 8;
-    for (int a = 0; a < 3; ++a) {
-      const int64_t t0 = (int64_t)e->region_min[a] * tpb, t1 = ((int64_t)e->region_max[a] + 1) * tpb - 1;   // tiles [t0, t1]
-      r0[a] = std::max<int64_t>(r0[a], t0 * 8);
-      r1[a] = std::min<int64_t>(r1[a], (t1 + 1) * 8);
-      lo[a] = (int)std::max<int64_t>(lo[a], t0 - grow);
-      hi[a] = (int)std::min<int64_t>(hi[a], t1 + grow);
-    }
-  }
-  bool empty = nt == 0;
-  for (int a = 0; a < 3; ++a) empty = empty || hi[a] < lo[a] || r1[a] <= r0[a];
-  uint64_t nbt[3] = {0, 0, 0};   // tiles of the box
-  if (!empty)
-    for (int a = 0; a < 3; ++a) nbt[a] = (uint64_t)(hi[a] - lo[a] + 1);
-  const uint64_t box_tiles = nbt[0] * nbt[1] * nbt[2], box_voxels = box_tiles * 512;
+  // 1) the box
+  TileSnapshot snap(c);
+  const uint32_t nt = snap.nt;
+  if ((rc = snap.fetch_keys(c))) return rc;
+  const EsdfBoxPlan P = esdf_box_plan(snap, *e, c->cfg.voxels_per_side / 8, R);
+  const uint64_t* nbt = P.nbt;
+  const uint64_t box_tiles = P.tiles(), box_voxels = box_tiles * 512;
   const uint64_t workspace = box_voxels * 32 + box_tiles * 4;   // two key buffers of two planes of 8 bytes; the slot grid
   if (stats) {
     for (int a = 0; a < 3; ++a) stats->box_voxels[a] = nbt[a] * 8;
@@ -3201,15 +3223,9 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
     hipLaunchKernelGGL(k_esdf_fill, dim3((uint32_t)(((size_t)nt * kTileVoxels + 255) / 256)), dim3(256), 0, st, c->esdf_store.get(),
                        (size_t)nt * kTileVoxels);
   unsigned long long counts[3] = {0, 0, 0};
-  if (!empty) {
+  if (box_tiles) {
     // 3) the dense slot grid of the box
-    std::vector<uint32_t> grid(box_tiles, 0xffffffffu);
-    for (uint32_t s = 0; s < nt; ++s) {
-      int t[3];
-      tile_of(keys[s], t);
-      if (t[0] < lo[0] || t[0] > hi[0] || t[1] < lo[1] || t[1] > hi[1] || t[2] < lo[2] || t[2] > hi[2]) continue;
-      grid[((size_t)(t[2] - lo[2]) * nbt[1] + (size_t)(t[1] - lo[1])) * nbt[0] + (size_t)(t[0] - lo[0])] = s;
-    }
+    const std::vector<uint32_t> grid = P.slot_grid(snap);
     if ((rc = c->esdf_slots.reserve(c, box_tiles, box_tiles + box_tiles / 2))) return rc;
     for (auto& K : c->esdf_keys)
       if ((rc = K.reserve(c, 2 * box_voxels, 2 * box_voxels + box_voxels / 2))) return rc;
@@ -3218,11 +3234,8 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
     B.nx = (int)(nbt[0] * 8);
     B.ny = (int)(nbt[1] * 8);
     B.nz = (int)(nbt[2] * 8);
-    const int org[3] = {lo[0] * 8, lo[1] * 8, lo[2] * 8}, dim[3] = {B.nx, B.ny, B.nz};
-    for (int a = 0; a < 3; ++a) {
-      B.r0[a] = (int)std::max<int64_t>(r0[a] - org[a], 0);
-      B.r1[a] = (int)std::min<int64_t>(r1[a] - org[a], dim[a]);
-    }
+    std::copy(P.r0, P.r0 + 3, B.r0);
+    std::copy(P.r1, P.r1 + 3, B.r1);
     B.R = R;
     B.voxel_size = c->cfg.voxel_size;
     B.min_weight = e->min_weight;
@@ -3263,46 +3276,27 @@ static int esdf_ready(ks_ctx* c, const char* who) {
 }
 
 // ---- incremental refresh of the stored ESDF ("ESDF", incremental refresh) ----
-// The lists of a refresh: pure arithmetic over tile positions (esdf_pos of ks_k_esdf.h; every vector ascending).
+// The lists of a refresh: pure arithmetic over tile positions (pack_coord3 of tile coordinates; every vector ascending).
 struct EsdfLists {
   std::vector<uint64_t> X, Y, Z;   // positions of passes x, y and z; Z = A, the tiles that are recomputed
   std::vector<uint32_t> z_slots;   // pool slot of each tile of Z
   uint64_t n_stale = 0;            // |S|
 };
-static inline void esdf_pos_of(uint64_t p, int t[3]) {
-  t[0] = (int)((p >> 42) & 0x1fffffu) - kEsdfPosBias;
-  t[1] = (int)((p >> 21) & 0x1fffffu) - kEsdfPosBias;
-  t[2] = (int)(p & 0x1fffffu) - kEsdfPosBias;
-}
 // every position within g of a listed one along `axis`
 static std::vector<uint64_t> esdf_dilate(const std::vector<uint64_t>& in, int axis, int g) {
   std::vector<uint64_t> out;
   out.reserve(in.size() * (size_t)(2 * g + 1));
-  for (uint64_t p : in) {
-    int t[3];
-    esdf_pos_of(p, t);
-    for (int d = -g; d <= g; ++d) {
-      int u[3] = {t[0], t[1], t[2]};
-      u[axis] += d;
-      out.push_back(esdf_pos(u[0], u[1], u[2]));
-    }
-  }
-  std::sort(out.begin(), out.end());
-  out.erase(std::unique(out.begin(), out.end()), out.end());
+  for (uint64_t p : in)
+    for (int d = -g; d <= g; ++d) out.push_back(coord3_moved(p, axis, d));
+  sort_unique(out);
   return out;
 }
 // the positions of `in` that have one of `have` (ascending) within g along `axis`
 static std::vector<uint64_t> esdf_keep_near(const std::vector<uint64_t>& in, const std::vector<uint64_t>& have, int axis, int g) {
   std::vector<uint64_t> out;
   for (uint64_t p : in) {
-    int t[3];
-    esdf_pos_of(p, t);
     bool near = false;
-    for (int d = -g; d <= g && !near; ++d) {
-      int u[3] = {t[0], t[1], t[2]};
-      u[axis] += d;
-      near = std::binary_search(have.begin(), have.end(), esdf_pos(u[0], u[1], u[2]));
-    }
+    for (int d = -g; d <= g && !near; ++d) near = std::binary_search(have.begin(), have.end(), coord3_moved(p, axis, d));
     if (near) out.push_back(p);
   }
   return out;
@@ -3318,8 +3312,9 @@ static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vec
   std::vector<std::pair<uint64_t, uint32_t>> resident(nt);
   std::vector<uint64_t> S;
   for (size_t s = 0; s < nt; ++s) {
-    const uint64_t k = keys[s];
-    const uint64_t p = esdf_pos((int)((k >> 36) & 0x3ffffu) - kTileBias, (int)((k >> 18) & 0x3ffffu) - kTileBias, (int)(k & 0x3ffffu) - kTileBias);
+    int t[3];
+    unpack_tile(keys[s], t[0], t[1], t[2]);
+    const uint64_t p = pack_coord3(t[0], t[1], t[2]);
     resident[s] = {p, (uint32_t)s};
     if (stale[s]) S.push_back(p);
   }
@@ -3331,7 +3326,7 @@ static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vec
   for (size_t i = 0; i < nt; ++i) {
     all[i] = resident[i].first;
     int t[3];
-    esdf_pos_of(all[i], t);
+    unpack_coord3(all[i], t[0], t[1], t[2]);
     bool in = std::binary_search(reach.begin(), reach.end(), all[i]);
     for (int a = 0; a < 3 && in && use_region; ++a) in = t[a] >= region_lo[a] && t[a] <= region_hi[a];
     if (!in) continue;
@@ -3346,10 +3341,7 @@ static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vec
 int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_stats* stats) {
   if (!c) return KS_ERR_INVALID_ARG;
   if (stats) std::memset(stats, 0, sizeof(*stats));
-  if (c->shard_export) {
-    c->err = "ks_esdf_refresh: a marcher context of ks_integrate_round_exact holds no voxel data";
-    return KS_ERR_UNSUPPORTED;
-  }
+  if (int rc = holds_voxels(c, "ks_esdf_refresh")) return rc;
   if (int rc = esdf_ready(c, "ks_esdf_refresh")) return rc;
   if (int rc = quiesce(c)) return rc;
   hipStream_t st = c->stream;
@@ -3359,13 +3351,9 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
   const int R = (int)ceilf(e.max_distance_m / c->cfg.voxel_size), g = (R + 7) / 8;
   int rc;
   // 1) the stale tiles (a tile that joined the map since has no records yet: stale whatever its mark says) and the lists
-  std::vector<uint64_t> keys(nt);
-  std::vector<uint8_t> stale(nt);
-  if (nt) {
-    HIPCHK(c, hipMemcpy(keys.data(), c->table.slot_keys, (size_t)nt * sizeof(uint64_t), hipMemcpyDeviceToHost));
-    HIPCHK(c, hipMemcpy(stale.data(), c->pool.mesh_stale(), nt, hipMemcpyDeviceToHost));
-  }
-  for (uint32_t s = 0; s < nt; ++s) stale[s] = (stale[s] & kStaleEsdf) || s >= nt_old;
+  TileSnapshot snap(c);
+  if ((rc = snap.fetch_keys(c)) || (rc = snap.fetch_flags(c, c->pool.mesh_stale()))) return rc;
+  for (uint32_t s = 0; s < nt; ++s) snap.flags[s] = (snap.flags[s] & kStaleEsdf) || s >= nt_old;
   int64_t region_lo[3] = {0, 0, 0}, region_hi[3] = {0, 0, 0};
   const int tpb = c->cfg.voxels_per_side / 8;
   for (int a = 0; a < 3; ++a) {
@@ -3373,7 +3361,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     region_hi[a] = ((int64_t)e.region_max[a] + 1) * tpb - 1;
   }
   EsdfLists L;
-  esdf_refresh_lists(keys, stale, g, e.use_region != 0, region_lo, region_hi, &L);
+  esdf_refresh_lists(snap.keys, snap.flags, g, e.use_region != 0, region_lo, region_hi, &L);
   const size_t nx = L.X.size(), ny = L.Y.size(), nz = L.Z.size();
   const uint64_t workspace = (uint64_t)(nx + ny) * kEsdfBrickKeys * 8 + (uint64_t)(nx + ny + nz) * 8 + (uint64_t)nz * 4;
   if (stats) {
@@ -3450,17 +3438,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
   c->esdf_tiles = nt;
   for (int k = 0; k < 3; ++k) c->esdf_totals[k] = counts[k];
   // 4) the blocks of the recomputed tiles
-  const int sh = c->vps_shift;
-  std::vector<uint64_t> blocks(nz);
-  for (size_t i = 0; i < nz; ++i) {
-    int t[3];
-    esdf_pos_of(L.Z[i], t);
-    blocks[i] = mesh_block_key(t[0] >> sh, t[1] >> sh, t[2] >> sh);
-  }
-  std::sort(blocks.begin(), blocks.end());
-  blocks.erase(std::unique(blocks.begin(), blocks.end()), blocks.end());
-  c->esdf_changed.resize(3 * blocks.size());
-  for (size_t i = 0; i < blocks.size(); ++i) mesh_block_of(blocks[i], &c->esdf_changed[3 * i]);
+  words_to_triples(blocks_of_tiles(L.Z, c->vps_shift), &c->esdf_changed);
   if (stats) {
     stats->voxels_observed = counts[0];
     stats->voxels_fixed = counts[1];
@@ -3470,16 +3448,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
 }
 
 int ks_esdf_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
-  if (!c || !n) return KS_ERR_INVALID_ARG;
-  *n = c->esdf_changed.size() / 3;
-  if (out_xyz) {
-    if (cap < *n) {
-      c->err = "ks_esdf_changed_blocks: output buffer too small";
-      return KS_ERR_INVALID_ARG;
-    }
-    std::memcpy(out_xyz, c->esdf_changed.data(), c->esdf_changed.size() * sizeof(int32_t));
-  }
-  return KS_OK;
+  return c ? copy_block_list(c, "ks_esdf_changed_blocks", c->esdf_changed, out_xyz, cap, n) : KS_ERR_INVALID_ARG;
 }
 
 int ks_esdf_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, void* out) {
@@ -3560,10 +3529,7 @@ static int render_enqueue(ks_ctx* c, const char* who, const float T[7], const fl
   if (r->min_range_m >= r->max_range_m) return refuse("min_range_m must be below max_range_m");
   if (r->max_range_m / c->cfg.voxel_size > 4096.0f) return refuse("max_range_m is more than 4096 voxels");
   if (!d_depth && !d_labels && !d_rgba && !d_normals) return refuse("all four outputs are NULL");
-  if (c->shard_export) {
-    c->err = std::string(who) + ": a marcher context of ks_integrate_round_exact holds no voxel data";
-    return KS_ERR_UNSUPPORTED;
-  }
+  if (int rc = holds_voxels(c, who)) return rc;
   if (int rc = quiesce(c)) return rc;
   if (int rc = c->render_counters.reserve(c, 3, 3)) return rc;
   RenderView V{};

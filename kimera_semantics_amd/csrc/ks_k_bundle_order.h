@@ -142,8 +142,8 @@ __global__ void __launch_bounds__(kBoBlock) k_bo_init(uint32_t n, const uint64_t
   const uint32_t clearing = (uint32_t)(key >> 63);
   const uint32_t si = svals[i] + clearing * n;
   const uint32_t t = s_tot[si / kBoBlock] + X.flag_lp[si] - clearing * n_normal;
-  const int vx = (int)((key >> 42) & 0x1fffffu) - kCoordBias, vy = (int)((key >> 21) & 0x1fffffu) - kCoordBias,
-            vz = (int)(key & 0x1fffffu) - kCoordBias;
+  int vx, vy, vz;
+  unpack_coord3(key, vx, vy, vz);
   X.m[clearing].H[t] = index_hash(vx, vy, vz);  // vxb::LongIndexHash
   X.t_of_head[i] = t;
 }

@@ -289,13 +289,8 @@ __global__ void __launch_bounds__(256) k_esdf_query(TileTable T, const EsdfRecor
 // passes read it with lanes on consecutive 8-byte words.  Staging a brick writes it transposed; an 8-byte LDS write goes 16
 // lanes at a time over 32 banks, and the rows are padded so that those 16 lanes fall on 16 different words: pass x stages
 // 8 indices along the axis times 2 rows across (row stride = 2 words mod 16: 66), pass y 2 along times 8 across (8 mod 16: 72).
-constexpr int kEsdfPosBias = 1 << 20;   // list positions are tile coordinates dilated by up to 2 * 32 tiles: 21-bit fields
+// A list position is pack_coord3 of a tile's coordinates: they are dilated by up to 2 * 32 tiles, beyond the 18-bit fields of a tile key.
 constexpr int kEsdfBrickKeys = 2 * kTileVoxels;
-
-__host__ __device__ __forceinline__ uint64_t esdf_pos(int tx, int ty, int tz) {
-  return ((uint64_t)(uint32_t)(tx + kEsdfPosBias) << 42) | ((uint64_t)(uint32_t)(ty + kEsdfPosBias) << 21) |
-         (uint64_t)(uint32_t)(tz + kEsdfPosBias);
-}
 
 struct EsdfRefresh {
   int R;
@@ -331,9 +326,8 @@ __global__ void __launch_bounds__(256) k_esdf_brick(EsdfRefresh E, TileTable T, 
   constexpr int kRow = AXIS == 0 ? 66 : 72;
   __shared__ uint64_t s_key[2][8][kRow];
   const uint32_t b = blockIdx.x, across = lane_id(), wave = threadIdx.x >> 6;
-  const uint64_t p = pos[b];
-  const int tx = (int)((p >> 42) & 0x1fffffu) - kEsdfPosBias, ty = (int)((p >> 21) & 0x1fffffu) - kEsdfPosBias,
-            tz = (int)(p & 0x1fffffu) - kEsdfPosBias;
+  int tx, ty, tz;
+  unpack_coord3(pos[b], tx, ty, tz);
   const int R = E.R, g = (R + 7) >> 3;
   // pass z: the voxel's own record decides the plane it reads
   uint32_t slot = 0;
@@ -365,7 +359,7 @@ __global__ void __launch_bounds__(256) k_esdf_brick(EsdfRefresh E, TileTable T, 
         src = tile_lookup(T, pack_tile(nx, ny, nz));
       if (src >= n_tiles) continue;
     } else {
-      src = esdf_find(in_pos, n_in, esdf_pos(nx, ny, nz));
+      src = esdf_find(in_pos, n_in, pack_coord3(nx, ny, nz));
       if (src == 0xffffffffu) continue;
     }
     __syncthreads();   // (the brick staged before this one has been read)

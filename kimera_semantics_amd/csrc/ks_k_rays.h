@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(1024) k_dedup_commit(FrameParams F, const uint
 // K4 (merged): per point — validity, point_G, end-voxel key.  vxb::MergedTsdfIntegrator::bundleRays,
 // called at [K:src/semantic_tsdf_integrator_merged.cpp:119-124].
 // ------------------------------------------------------------------------------------------
-// validity + end-voxel key of point idx: kEmpty64 = not integrated, else clearing << 63 | x << 42 | y << 21 | z (biased by kCoordBias)
+// validity + end-voxel key of point idx: kEmpty64 = not integrated, else clearing << 63 | pack_coord3(x, y, z)
 __device__ __forceinline__ uint64_t merged_point_key(const FrameParams& F, const float* __restrict__ xyz, const uint8_t* __restrict__ rgba,
                                                      const uint8_t* __restrict__ labels, const uint8_t* __restrict__ color_lut,
                                                      uint32_t idx, Counters* C, bool report) {
@@ -147,8 +147,7 @@ __device__ __forceinline__ uint64_t merged_point_key(const FrameParams& F, const
     if (report) atomicOr(&C->err, kErrIndex);
     return kEmpty64;
   }
-  return ((uint64_t)(valid == 2 ? 1u : 0u) << 63) | ((uint64_t)(uint32_t)((int)gx + kCoordBias) << 42) |
-         ((uint64_t)(uint32_t)((int)gy + kCoordBias) << 21) | (uint64_t)(uint32_t)((int)gz + kCoordBias);
+  return ((uint64_t)(valid == 2 ? 1u : 0u) << 63) | coord3_field((int)gx, 0) | coord3_field((int)gy, 1) | coord3_field((int)gz, 2);
 }
 
 // The voxels outside the key window (FrameParams::key_base / key_bits): a slot per distinct end-voxel key in an open-addressing
@@ -191,9 +190,9 @@ __global__ void __launch_bounds__(1024) k_points_merged(FrameParams F, const flo
       uint32_t kw = kEmpty32;
       if (counted) {
         const uint32_t w = F.key_bits;
-        const uint32_t rx = (uint32_t)((int)((key >> 42) & 0x1fffffu) - kCoordBias - F.key_base[0]);
-        const uint32_t ry = (uint32_t)((int)((key >> 21) & 0x1fffffu) - kCoordBias - F.key_base[1]);
-        const uint32_t rz = (uint32_t)((int)(key & 0x1fffffu) - kCoordBias - F.key_base[2]);
+        const uint32_t rx = (uint32_t)(coord3_of(key, 0) - F.key_base[0]);
+        const uint32_t ry = (uint32_t)(coord3_of(key, 1) - F.key_base[1]);
+        const uint32_t rz = (uint32_t)(coord3_of(key, 2) - F.key_base[2]);
         if (((rx | ry | rz) >> w) == 0u) kw = ((uint32_t)(key >> 63) << (3u * w)) | (rx << (2u * w)) | (ry << w) | rz;
         else kw = 0x80000000u | key_overflow_slot(overflow_tab, overflow_mask, key);
       }

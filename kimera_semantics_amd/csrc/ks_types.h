@@ -20,6 +20,54 @@ constexpr float kPriorInit = -0.60205999132f;                  // [K:include/kim
 constexpr int kCoordBias = 1 << 20;                            // voxel coordinates packed as 21-bit fields
 constexpr int kTileBias = 1 << 17;                             // tile coordinates packed as 18-bit fields
 
+// ---- packed coordinates: the ONLY place that knows the two layouts (both cross the ABI: ks_get_tile_keys, ks_tile_owner) ----
+// Tile key: three 18-bit fields x << 36 | y << 18 | z, each biased by kTileBias.
+// Triple:   three 21-bit fields x << 42 | y << 21 | z, each biased by kCoordBias: the end-voxel keys of the merged integrator
+//           (bit 63, clearing, is the caller's), the block words of the mesh and the ESDF, the tile positions of the refresh lists.
+//           The bias makes an ascending word an ascending signed (x, y, z): the host sorts and bisects the words as they are.
+constexpr __host__ __device__ __forceinline__ uint64_t pack_tile(int tx, int ty, int tz) {
+  return ((uint64_t)(uint32_t)(tx + kTileBias) << 36) | ((uint64_t)(uint32_t)(ty + kTileBias) << 18) |
+         (uint64_t)(uint32_t)(tz + kTileBias);
+}
+constexpr __host__ __device__ __forceinline__ void unpack_tile(uint64_t k, int& tx, int& ty, int& tz) {
+  tx = (int)((k >> 36) & 0x3ffffu) - kTileBias;
+  ty = (int)((k >> 18) & 0x3ffffu) - kTileBias;
+  tz = (int)(k & 0x3ffffu) - kTileBias;
+}
+constexpr __host__ __device__ __forceinline__ uint64_t coord3_field(int v, int axis) {   // one field in its place (axis 0 = x)
+  return (uint64_t)(uint32_t)(v + kCoordBias) << (21 * (2 - axis));
+}
+constexpr __host__ __device__ __forceinline__ int coord3_of(uint64_t k, int axis) {
+  return (int)((k >> (21 * (2 - axis))) & 0x1fffffu) - kCoordBias;
+}
+constexpr __host__ __device__ __forceinline__ uint64_t coord3_moved(uint64_t k, int axis, int d) {   // one field + d, while it stays in its 21 bits
+  return k + ((uint64_t)(int64_t)d << (21 * (2 - axis)));
+}
+constexpr __host__ __device__ __forceinline__ uint64_t pack_coord3(int x, int y, int z) {
+  return coord3_field(x, 0) | coord3_field(y, 1) | coord3_field(z, 2);
+}
+constexpr __host__ __device__ __forceinline__ void unpack_coord3(uint64_t k, int& x, int& y, int& z) {
+  x = coord3_of(k, 0), y = coord3_of(k, 1), z = coord3_of(k, 2);
+}
+// checked where they are defined: round trips at 0 and both ends of every field, the order the host relies on, one literal each
+template <uint64_t (*Pack)(int, int, int), void (*Unpack)(uint64_t, int&, int&, int&)>
+constexpr bool coords_ok(int lo, int hi) {
+  const int v[3] = {lo, 0, hi};
+  for (int x : v)
+    for (int y : v)
+      for (int z : v) {
+        int a = 1, b = 1, c = 1;
+        Unpack(Pack(x, y, z), a, b, c);
+        if (a != x || b != y || c != z) return false;
+      }
+  return Pack(-1, hi, hi) < Pack(0, lo, lo) && Pack(0, -1, hi) < Pack(0, 0, lo) && Pack(0, 0, -1) < Pack(0, 0, 0) && Pack(lo, 0, 0) < Pack(hi, 0, 0);
+}
+static_assert(coords_ok<pack_tile, unpack_tile>(-kTileBias, kTileBias - 1), "tile key: round trip; ascending word = ascending signed (x, y, z)");
+static_assert(coords_ok<pack_coord3, unpack_coord3>(-kCoordBias, kCoordBias - 1), "triple: round trip; ascending word = ascending signed (x, y, z)");
+static_assert(pack_tile(1, -2, 3) == 0x00200017fffa0003ull && pack_coord3(1, -2, 3) == 0x400005ffffd00003ull, "the layouts are ABI");
+static_assert(coord3_moved(pack_coord3(1, -2, 3), 1, -5) == pack_coord3(1, -7, 3) && coord3_moved(pack_coord3(-1, 0, 0), 0, 2) == pack_coord3(1, 0, 0), "a move is an add");
+static_assert(pack_coord3(kCoordBias - 1, 0, 0) >> 63 == 0, "bit 63 of a triple is free (the clearing bit of an end-voxel key)");
+
 // error bits raised by kernels
 enum : uint32_t { kErrLabel = 1u, kErrPool = 2u, kErrIndex = 4u, kErrTable = 8u, kErrPairs = 16u /* pair buffer too small: the host grows it and repeats the emission */,
                  kErrExact = 32u /* exact early-out: the device-driven fix point gave up, the host-driven loop repeats the frame's stage B */ };
@@ -203,8 +251,7 @@ __device__ __forceinline__ bool grazing_skip(const FrameParams& F, int cx, int c
   if (!F.grazing_keys) return false;
   const int lim = kCoordBias - 1;
   if (abs(cx) >= lim || abs(cy) >= lim || abs(cz) >= lim) return false;
-  const uint64_t k = ((uint64_t)(uint32_t)(cx + kCoordBias) << 42) | ((uint64_t)(uint32_t)(cy + kCoordBias) << 21) |
-                     (uint64_t)(uint32_t)(cz + kCoordBias);
+  const uint64_t k = pack_coord3(cx, cy, cz);
   if (!clearing && k == own_key) return false;
   uint32_t lo = 0, hi = F.n;
   while (lo < hi) {
@@ -228,15 +275,6 @@ __device__ __forceinline__ uint32_t point_position(const FrameParams& F, const u
   return (idx % F.order_per) * F.order_groups + idx / F.order_per;
 }
 
-__host__ __device__ __forceinline__ uint64_t pack_tile(int tx, int ty, int tz) {
-  return ((uint64_t)(uint32_t)(tx + kTileBias) << 36) | ((uint64_t)(uint32_t)(ty + kTileBias) << 18) |
-         (uint64_t)(uint32_t)(tz + kTileBias);
-}
-__device__ __forceinline__ void unpack_tile(uint64_t k, int& tx, int& ty, int& tz) {
-  tx = (int)((k >> 36) & 0x3ffffu) - kTileBias;
-  ty = (int)((k >> 18) & 0x3ffffu) - kTileBias;
-  tz = (int)(k & 0x3ffffu) - kTileBias;
-}
 __host__ __device__ __forceinline__ uint32_t mix64(uint64_t k) {
   k ^= k >> 33;
   k *= 0xff51afd7ed558ccdull;

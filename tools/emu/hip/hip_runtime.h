@@ -585,7 +585,13 @@ template <typename T> inline hipError_t hipMalloc(T** p, size_t bytes) { *p = (T
 template <typename T> inline hipError_t hipHostMalloc(T** p, size_t bytes, unsigned = 0) { *p = (T*)emu_alloc(bytes); return *p ? hipSuccess : hipErrorOutOfMemory; }
 inline hipError_t hipFree(void* p) { emu_free(p); return hipSuccess; }
 inline hipError_t hipHostFree(void* p) { emu_free(p); return hipSuccess; }
-inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { emu::touch((ihipStream_t*)nullptr); memmove(d, s, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
+inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind kind) {   // blocking: traced on the null stream
+  if (emu::tracing()) fprintf(stderr, "emu: memcpy_sync kind %d bytes %zu stream 0\n", (int)kind, n);
+  emu::touch((ihipStream_t*)nullptr);
+  memmove(d, s, n);
+  emu::touch((ihipStream_t*)nullptr);
+  return hipSuccess;
+}
 inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind kind, hipStream_t st = nullptr) {
   if (emu::tracing()) fprintf(stderr, "emu: memcpy kind %d bytes %zu stream %ld\n", (int)kind, n, emu::ordinal(st));
   emu::touch(st);
@@ -593,7 +599,13 @@ inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind
   emu::touch(st);
   return hipSuccess;
 }
-inline hipError_t hipMemset(void* d, int v, size_t n) { emu::touch((ihipStream_t*)nullptr); memset(d, v, n); emu::touch((ihipStream_t*)nullptr); return hipSuccess; }
+inline hipError_t hipMemset(void* d, int v, size_t n) {
+  if (emu::tracing()) fprintf(stderr, "emu: memset_sync bytes %zu stream 0\n", n);
+  emu::touch((ihipStream_t*)nullptr);
+  memset(d, v, n);
+  emu::touch((ihipStream_t*)nullptr);
+  return hipSuccess;
+}
 inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) {
   if (emu::tracing()) fprintf(stderr, "emu: memset bytes %zu stream %ld\n", n, emu::ordinal(st));
   emu::touch(st);
