@@ -404,6 +404,49 @@ int ks_render_view(ks_ctx* ctx, const float T_G_C[7], const float K[4] /* fx, fy
 int ks_render_view_device(ks_ctx* ctx, const float T_G_C[7], const float K[4], int width, int height, const ks_render_config* cfg,
                           float* d_depth, uint8_t* d_labels, uint8_t* d_rgba, float* d_normals, ks_render_stats* stats);
 
+/* ---- scan alignment: refine the pose of a point cloud against the resident TSDF (new: the reference's launch files select
+ * Voxblox's ICP, which reads the host layer; this reads the device-resident map and needs no layer sync) ----
+ * The contract is DESIGN.md, section "Scan alignment".  A Gauss-Newton alignment of the cloud to the zero level set of the
+ * TSDF: point i is used iff i % point_stride == 0 and it is finite; p = T * p_C, s and its gradient from the eight corners of the
+ * renderer's trilinear sample S(p) (the same validity rule); an inlier has a valid sample, |s| < max_residual_m and a non-zero
+ * gradient; residual s, Jacobian row (a x grad, grad) with a = p - t: rotation about the sensor origin in the world frame, then
+ * translation.  29 sums in f64 in a fixed order (no floating-point atomics), a damped 6 x 6 LDL^T solve, dq = (1, omega / 2)
+ * applied from the left and renormalised, t + v; the whole loop runs on the device with one read-back at its end.
+ * T_G_C_out is the last accepted pose (T_G_C_in bit for bit when no step was taken).  A status other than CONVERGED is no error.
+ * stats.iterations = pose updates applied; rmse = sqrt(sum r^2 / inliers), 0 without inliers.  Two calls give the same bytes.
+ * Aligning only READS the map: the `updated` and `dirty` flags, both stale bits, the stored mesh and the stored ESDF stay as
+ * they were.
+ * ks_align_points          xyz on the host (camera frame); completes the frames in flight first.
+ * ks_align_points_device   the same with xyz a DEVICE pointer, read on the stream ks_stream returns.
+ * Errors: KS_ERR_INVALID_ARG (a NULL pose or config; a non-finite pose or a zero quaternion; min_weight not a finite positive
+ * number; max_residual_m, damping or an eps negative or not finite; max_iterations outside 1..64; point_stride or min_inliers
+ * below 1; dof_mask 0 or above 0x3f; n >= 2^31), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact), KS_ERR_HIP.
+ * n = 0 and an empty map are no errors: TOO_FEW_INLIERS with T_G_C_out = T_G_C_in.  Multi-GPU: each context aligns against the
+ * tiles it holds. */
+typedef struct ks_align_config {
+  float min_weight;        /* 1e-4 */
+  float max_residual_m;    /* 0: the context's truncation_distance */
+  float damping;           /* 1e-6: times the inlier count, added to the diagonal */
+  float eps_rotation_rad;  /* 1e-4 */
+  float eps_translation_m; /* 1e-4 */
+  int32_t max_iterations;  /* 10, 1..64 */
+  int32_t point_stride;    /* 1, >= 1 */
+  int32_t min_inliers;     /* 64, >= 1 */
+  uint32_t dof_mask;       /* 0x3f; bits 0-2 rotation about world x, y, z, bits 3-5 translation; 0x3c = yaw + translation
+                              (Voxblox's default) */
+} ks_align_config;
+typedef struct ks_align_stats {
+  uint32_t status, iterations;
+  uint64_t points_used, inliers_first, inliers_last;
+  double rmse_first, rmse_last;
+} ks_align_stats; /* 48 bytes */
+enum { KS_ALIGN_CONVERGED = 0, KS_ALIGN_ITERATION_LIMIT = 1, KS_ALIGN_TOO_FEW_INLIERS = 2, KS_ALIGN_DEGENERATE = 3 };
+int ks_align_default_config(ks_align_config* cfg);
+int ks_align_points(ks_ctx* ctx, const float T_G_C_in[7], const float* xyz /* host, camera frame */, size_t n,
+                    const ks_align_config* cfg, float T_G_C_out[7], ks_align_stats* stats /* may be NULL */);
+int ks_align_points_device(ks_ctx* ctx, const float T_G_C_in[7], const float* d_xyz, size_t n, const ks_align_config* cfg,
+                           float T_G_C_out[7], ks_align_stats* stats);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
     "ks_esdf_refresh", "ks_esdf_changed_blocks",
     "ks_render_default_config", "ks_render_view", "ks_render_view_device",
+    "ks_align_default_config", "ks_align_points", "ks_align_points_device",
 ]
 
 
@@ -119,6 +120,20 @@ class KsRenderStats(C.Structure):
     _fields_ = [("pixels_hit", C.c_uint64), ("pixels_missed", C.c_uint64), ("samples", C.c_uint64)]
 
 
+class KsAlignConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("max_residual_m", C.c_float), ("damping", C.c_float), ("eps_rotation_rad", C.c_float),
+                ("eps_translation_m", C.c_float), ("max_iterations", C.c_int32), ("point_stride", C.c_int32), ("min_inliers", C.c_int32),
+                ("dof_mask", C.c_uint32)]
+
+
+class KsAlignStats(C.Structure):
+    _fields_ = [("status", C.c_uint32), ("iterations", C.c_uint32), ("points_used", C.c_uint64), ("inliers_first", C.c_uint64),
+                ("inliers_last", C.c_uint64), ("rmse_first", C.c_double), ("rmse_last", C.c_double)]
+
+
+KS_ALIGN_CONVERGED, KS_ALIGN_ITERATION_LIMIT, KS_ALIGN_TOO_FEW_INLIERS, KS_ALIGN_DEGENERATE = 0, 1, 2, 3
+
+
 class KsProfile(C.Structure):
     _fields_ = [("ms", C.c_double * 8), ("launches", C.c_uint64 * 8), ("frames", C.c_uint64),
                 ("updates", C.c_uint64), ("points", C.c_uint64), ("apply_kernel_ms", C.c_double),
@@ -130,7 +145,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -209,6 +224,9 @@ def lib():
         L.ks_render_default_config.argtypes = [C.POINTER(KsRenderConfig)]
         L.ks_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
         L.ks_render_view_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
+        L.ks_align_default_config.argtypes = [C.POINTER(KsAlignConfig)]
+        L.ks_align_points.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(KsAlignConfig), vp, C.POINTER(KsAlignStats)]
+        L.ks_align_points_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(KsAlignConfig), vp, C.POINTER(KsAlignStats)]
         _lib = L
     return _lib
 
@@ -483,6 +501,37 @@ class HipIntegrator:
         self._chk(lib().ks_render_view_device(self._h, _ptr(T), _ptr(Kc), int(width), int(height), C.byref(rc), d_depth or None, d_labels or None,
                                               d_rgba or None, d_normals or None, C.byref(st) if stats else None))
         return {k: int(getattr(st, k)) for k, _ in KsRenderStats._fields_} if stats else None
+
+    def align_config(self, **cfg) -> KsAlignConfig:
+        ac = KsAlignConfig()
+        lib().ks_align_default_config(C.byref(ac))
+        for k, v in cfg.items():
+            if k not in [f for f, _ in KsAlignConfig._fields_]:
+                raise AttributeError(k)
+            if v is not None:
+                setattr(ac, k, v)
+        return ac
+
+    @staticmethod
+    def _align_stats(st) -> dict:
+        return {k: (float if k.startswith("rmse") else int)(getattr(st, k)) for k, _ in KsAlignStats._fields_}
+
+    def align(self, T_G_C, xyz, **cfg):
+        """ks_align_points: refines the pose T_G_C of the cloud xyz (n, 3; camera frame) against the TSDF of the map.  Returns
+        (T_out (7,) f32, stats dict); a status other than KS_ALIGN_CONVERGED is no error.  The contract is DESIGN.md, section
+        "Scan alignment"; cfg are the fields of KsAlignConfig."""
+        T = np.ascontiguousarray(T_G_C, dtype=np.float32)
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        ac, st, out = self.align_config(**cfg), KsAlignStats(), np.zeros(7, np.float32)
+        self._chk(lib().ks_align_points(self._h, _ptr(T), _ptr(xyz), len(xyz), C.byref(ac), _ptr(out), C.byref(st)))
+        return out, self._align_stats(st)
+
+    def align_device(self, T_G_C, d_xyz: int, n: int, **cfg):
+        """ks_align_points_device: the cloud at the raw device address d_xyz (e.g. torch.Tensor.data_ptr()), read on self.stream."""
+        T = np.ascontiguousarray(T_G_C, dtype=np.float32)
+        ac, st, out = self.align_config(**cfg), KsAlignStats(), np.zeros(7, np.float32)
+        self._chk(lib().ks_align_points_device(self._h, _ptr(T), d_xyz or None, int(n), C.byref(ac), _ptr(out), C.byref(st)))
+        return out, self._align_stats(st)
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----
     TILE_BYTES = 65536

@@ -69,6 +69,7 @@ using namespace ksd;
 #include "ks_k_mesh.h"
 #include "ks_k_esdf.h"
 #include "ks_k_render.h"
+#include "ks_k_align.h"
 
 using namespace ksk;
 
@@ -505,6 +506,10 @@ struct ks_ctx {
   DevBuf<uint32_t> render_rgba;
   DevBuf<uint8_t> render_labels;
   DevBuf<unsigned long long> render_counters;
+  // ks_align_points (ks_k_align.h): the wavefronts' partial sums, the state block, and the cloud of the host-pointer call
+  DevBuf<double> align_partials;
+  DevBuf<AlignState> align_state;
+  DevBuf<float> align_xyz;
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -3600,6 +3605,112 @@ int ks_render_view(ks_ctx* c, const float T[7], const float K[4], int width, int
   if (stats) return render_stats(c, stats);
   HIPCHK(c, hipStreamSynchronize(st));
   return KS_OK;
+}
+
+// ---- scan alignment ("Scan alignment"; ks_k_align.h) --------------------------------------------
+int ks_align_default_config(ks_align_config* a) {
+  if (!a) return KS_ERR_INVALID_ARG;
+  a->min_weight = 1e-4f;
+  a->max_residual_m = 0.0f;
+  a->damping = 1e-6f;
+  a->eps_rotation_rad = 1e-4f;
+  a->eps_translation_m = 1e-4f;
+  a->max_iterations = 10;
+  a->point_stride = 1;
+  a->min_inliers = 64;
+  a->dof_mask = 0x3fu;
+  return KS_OK;
+}
+
+// the checks of both calls, then the whole loop on the context's stream: max_iterations pairs (evaluate, finish) and the
+// last pair, one read-back of the state block, one host wait
+static int align_run(ks_ctx* c, const char* who, const float T[7], const float* d_xyz, size_t n, const ks_align_config* a, float T_out[7],
+                     ks_align_stats* stats) {
+  AlignParams A{};
+  A.xyz = d_xyz;
+  A.n = (uint32_t)n;
+  A.stride = (uint32_t)a->point_stride;
+  A.n_used = (uint32_t)((n + (size_t)a->point_stride - 1) / (size_t)a->point_stride);
+  A.n_waves = (A.n_used + 63u) / 64u;
+  A.voxel_size_inv = c->voxel_size_inv;
+  A.min_weight = a->min_weight;
+  A.max_residual = a->max_residual_m > 0.0f ? a->max_residual_m : c->cfg.truncation_distance;
+  A.n_tiles = c->tiles_initialised;
+  A.damping = a->damping;
+  A.eps_rotation = a->eps_rotation_rad;
+  A.eps_translation = a->eps_translation_m;
+  A.max_iterations = a->max_iterations;
+  A.min_inliers = a->min_inliers;
+  A.dof_mask = a->dof_mask;
+  const size_t n_partials = (size_t)kAlignSums * std::max<size_t>(A.n_waves, 1);
+  if (int rc = c->align_partials.reserve(c, n_partials, n_partials)) return rc;
+  if (int rc = c->align_state.reserve(c, 1, 1)) return rc;
+  A.partials = c->align_partials;
+  A.state = c->align_state;
+  AlignState S{};
+  for (int k = 0; k < 4; ++k) S.q[k] = T[k];
+  for (int k = 0; k < 3; ++k) S.t[k] = T[4 + k];
+  S.status = KS_ALIGN_ITERATION_LIMIT;
+  hipStream_t st = c->stream;
+  HIPCHK(c, hipMemcpyAsync(c->align_state, &S, sizeof(S), hipMemcpyHostToDevice, st));
+  const dim3 grid(std::max<uint32_t>((A.n_used + 255u) / 256u, 1u));
+  for (int it = 0; it <= a->max_iterations; ++it) {
+    const int iteration = it < a->max_iterations ? it : kAlignLast;
+    hipLaunchKernelGGL(k_align_eval, grid, dim3(256), 0, st, c->table, c->pool, A, iteration);
+    hipLaunchKernelGGL(k_align_finish, dim3(1), dim3(256), 0, st, A, iteration);
+  }
+  HIPCHK(c, hipGetLastError());
+  HIPCHK(c, hipMemcpyAsync(&S, c->align_state, sizeof(S), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  for (int k = 0; k < 4; ++k) T_out[k] = S.q[k];
+  for (int k = 0; k < 3; ++k) T_out[4 + k] = S.t[k];
+  if (stats) {
+    stats->status = S.status;
+    stats->iterations = S.iterations;
+    stats->points_used = (uint64_t)S.used;
+    stats->inliers_first = (uint64_t)S.inliers_first;
+    stats->inliers_last = (uint64_t)S.inliers_last;
+    stats->rmse_first = S.inliers_first > 0.0 ? std::sqrt(S.rr_first / S.inliers_first) : 0.0;
+    stats->rmse_last = S.inliers_last > 0.0 ? std::sqrt(S.rr_last / S.inliers_last) : 0.0;
+  }
+  return KS_OK;
+}
+
+static int align_check(ks_ctx* c, const char* who, const float T[7], size_t n, const ks_align_config* a) {
+  auto refuse = [&](const char* why) {
+    c->err = std::string(who) + ": " + why;
+    return KS_ERR_INVALID_ARG;
+  };
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(T[k])) return refuse("the pose must be finite");
+  if (T[0] == 0.0f && T[1] == 0.0f && T[2] == 0.0f && T[3] == 0.0f) return refuse("the quaternion is zero");
+  if (!std::isfinite(a->min_weight) || !(a->min_weight > 0.0f)) return refuse("min_weight must be a finite positive number");
+  const float par[4] = {a->max_residual_m, a->damping, a->eps_rotation_rad, a->eps_translation_m};
+  for (float v : par)
+    if (!std::isfinite(v) || v < 0.0f) return refuse("max_residual_m, damping, eps_rotation_rad and eps_translation_m must be finite and not negative");
+  if (a->max_iterations < 1 || a->max_iterations > 64) return refuse("max_iterations must lie in 1..64");
+  if (a->point_stride < 1) return refuse("point_stride must be at least 1");
+  if (a->min_inliers < 1) return refuse("min_inliers must be at least 1");
+  if (a->dof_mask == 0u || a->dof_mask > 0x3fu) return refuse("dof_mask must lie in 1..0x3f");
+  if (n >= ((size_t)1 << 31)) return refuse("more than 2^31 - 1 points");
+  if (int rc = holds_voxels(c, who)) return rc;
+  return quiesce(c);
+}
+
+int ks_align_points_device(ks_ctx* c, const float T[7], const float* d_xyz, size_t n, const ks_align_config* a, float T_out[7], ks_align_stats* stats) {
+  if (!c || !T || !a || !T_out || (n && !d_xyz)) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (int rc = align_check(c, "ks_align_points_device", T, n, a)) return rc;
+  return align_run(c, "ks_align_points_device", T, d_xyz, n, a, T_out, stats);
+}
+
+int ks_align_points(ks_ctx* c, const float T[7], const float* xyz, size_t n, const ks_align_config* a, float T_out[7], ks_align_stats* stats) {
+  if (!c || !T || !a || !T_out || (n && !xyz)) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (int rc = align_check(c, "ks_align_points", T, n, a)) return rc;
+  if (int rc = c->align_xyz.reserve(c, 3 * n, 3 * n)) return rc;
+  if (n) HIPCHK(c, hipMemcpyAsync(c->align_xyz, xyz, 3 * n * sizeof(float), hipMemcpyHostToDevice, c->stream));
+  return align_run(c, "ks_align_points", T, c->align_xyz, n, a, T_out, stats);
 }
 
 // ---- voxel-level host sync -------------------------------------------------------------------------------

@@ -187,9 +187,10 @@ def synthetic_sequence(n_frames: int, width=640, height=480, hfov_deg=90.0, scen
     return seq
 
 
-def replay(seq: Sequence, integrator, use_label_img=True, on_frame=None) -> dict:
+def replay(seq: Sequence, integrator, use_label_img=True, on_frame=None, refine=None) -> dict:
     """kimera_semantics_rosbag.cpp:83-141 over a Sequence: per depth image the stamp CHECK, the tf lookup, the
-    composition T_G_C = T_G_B * T_B_C and one ks_integrate_depth call.  Returns counters (frames integrated / skipped)."""
+    composition T_G_C = T_G_B * T_B_C and one ks_integrate_depth call.  refine(frame, T_G_C) -> T_G_C, when given, has the
+    last word on the pose a frame is integrated with.  Returns counters (frames integrated / skipped)."""
     done = skipped = 0
     for fr in seq.frames:
         if fr.semantic_stamp_ns is not None and fr.semantic_stamp_ns != fr.stamp_ns:
@@ -199,6 +200,8 @@ def replay(seq: Sequence, integrator, use_label_img=True, on_frame=None) -> dict
             skipped += 1      # "Couldn't find tf for given pointcloud..."
             continue
         T_G_C = compose(T_G_B, seq.T_B_C)
+        if refine:
+            T_G_C = refine(fr, T_G_C)
         if use_label_img and fr.label_img is not None:
             st = integrator.integrate_depth(T_G_C, fr.depth, fr.K, label_img=fr.label_img)
         else:

@@ -11,6 +11,7 @@
 #include <algorithm>
 #include <array>
 #include <chrono>
+#include <cmath>
 #include <voxblox/utils/timing.h>
 #include <cstdio>
 #include <cstdlib>
@@ -104,7 +105,8 @@ int main(int argc, char** argv) {
   const char* esdf_refresh_path = std::getenv("KS_DEMO_ESDF_REFRESH");
   using EsdfBlock = kimera::HipSemanticTsdfIntegrator::EsdfBlock;
   std::map<std::array<int32_t, 3>, EsdfBlock> esdf_kept;   // (ascending by x, y, z)
-  float last_T[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // pose of the last frame read (KS_DEMO_RENDER)
+  float last_T[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};   // pose of the last frame read (KS_DEMO_RENDER, KS_DEMO_ALIGN)
+  vxb::Pointcloud last_points;                                     // ... and its cloud (KS_DEMO_ALIGN)
   for (uint32_t f = 0; f < n_frames; ++f) {
     if (esdf_refresh_path && f == n_frames / 2) {
       auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
@@ -149,6 +151,7 @@ int main(int argc, char** argv) {
       pts[i] = vxb::Point(xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
       cols[i] = vxb::Color(rgba[4 * i], rgba[4 * i + 1], rgba[4 * i + 2], rgba[4 * i + 3]);
     }
+    if (f + 1 == n_frames && std::getenv("KS_DEMO_ALIGN")) last_points = pts;
     const auto t0 = std::chrono::steady_clock::now();
     integrator->integratePointCloud(vxb::Transformation(T[0], T[1], T[2], T[3], vxb::Point(T[4], T[5], T[6])), pts, cols, false);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -228,6 +231,37 @@ int main(int argc, char** argv) {
     const ks_esdf_stats& es = hip->lastEsdfStats();
     std::printf("adapter_demo: updateEsdf %.3f ms, %u blocks, %llu observed voxels, %llu in the band\n", ms, n_esdf_blocks,
                 (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
+  }
+
+  // KS_DEMO_ALIGN=<file>: the LAST frame's pose, moved by (0.03, -0.02, 0.025) m and turned by 1.5 degrees about
+  // (1, 2, -1) / sqrt(6) in the world frame, refined against the map with that frame's cloud on the device without any layer
+  // sync (alignPointCloud, default options), written as { f32 T_in[7]; f32 T_out[7]; ks_align_stats (48 bytes) }
+  if (const char* align_path = std::getenv("KS_DEMO_ALIGN")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip || n_frames == 0) return 8;
+    const double half = 0.5 * 1.5 * 3.14159265358979323846 / 180.0, s6 = std::sin(half) / std::sqrt(6.0);
+    const double dq[4] = {std::cos(half), s6, 2.0 * s6, -s6}, q[4] = {last_T[0], last_T[1], last_T[2], last_T[3]};
+    const float T_in[7] = {(float)(dq[0] * q[0] - dq[1] * q[1] - dq[2] * q[2] - dq[3] * q[3]),
+                           (float)(dq[0] * q[1] + dq[1] * q[0] + dq[2] * q[3] - dq[3] * q[2]),
+                           (float)(dq[0] * q[2] - dq[1] * q[3] + dq[2] * q[0] + dq[3] * q[1]),
+                           (float)(dq[0] * q[3] + dq[1] * q[2] - dq[2] * q[1] + dq[3] * q[0]),
+                           last_T[4] + 0.03f, last_T[5] - 0.02f, last_T[6] + 0.025f};
+    vxb::Transformation refined;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->alignPointCloud(vxb::Transformation(T_in[0], T_in[1], T_in[2], T_in[3], vxb::Point(T_in[4], T_in[5], T_in[6])), last_points,
+                         kimera::HipSemanticTsdfIntegrator::AlignOptions(), &refined);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const float T_out[7] = {refined.qw(), refined.qvec().x(), refined.qvec().y(), refined.qvec().z(), refined.getPosition().x(),
+                            refined.getPosition().y(), refined.getPosition().z()};
+    const ks_align_stats& as = hip->lastAlignStats();
+    FILE* af = std::fopen(align_path, "wb");
+    if (!af) return 9;
+    std::fwrite(T_in, 4, 7, af);
+    std::fwrite(T_out, 4, 7, af);
+    std::fwrite(&as, sizeof(as), 1, af);
+    std::fclose(af);
+    std::printf("adapter_demo: alignPointCloud %.3f ms, status %u after %u iterations, %llu of %llu points inliers, rmse %.4f -> %.4f m\n", ms, as.status,
+                as.iterations, (unsigned long long)as.inliers_first, (unsigned long long)as.points_used, as.rmse_first, as.rmse_last);
   }
 
   // KS_DEMO_RENDER=<file>: the map seen from the LAST frame's pose, made on the device without any layer sync (renderView;

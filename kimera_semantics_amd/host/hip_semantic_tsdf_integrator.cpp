@@ -335,6 +335,31 @@ bool HipSemanticTsdfIntegrator::renderView(const vxb::Transformation& T_G_C, flo
   return last_render_stats_.pixels_hit != 0;
 }
 
+bool HipSemanticTsdfIntegrator::alignPointCloud(const vxb::Transformation& T_G_C, const vxb::Pointcloud& points_C, const AlignOptions& options,
+                                                vxb::Transformation* T_refined) {
+  CHECK_NOTNULL(T_refined);
+  static_assert(sizeof(vxb::Point) == 12, "point layout");
+  const float T[7] = {T_G_C.qw(),          T_G_C.qvec().x(),        T_G_C.qvec().y(),       T_G_C.qvec().z(),
+                      T_G_C.getPosition().x(), T_G_C.getPosition().y(), T_G_C.getPosition().z()};
+  ks_align_config ac;
+  ks_align_default_config(&ac);
+  ac.min_weight = options.min_weight;
+  ac.max_residual_m = options.max_residual_m;
+  ac.damping = options.damping;
+  ac.eps_rotation_rad = options.eps_rotation_rad;
+  ac.eps_translation_m = options.eps_translation_m;
+  ac.max_iterations = options.max_iterations;
+  ac.point_stride = options.point_stride;
+  ac.min_inliers = options.min_inliers;
+  ac.dof_mask = options.dof_mask;
+  float out[7];
+  check(ks_align_points(ctx_, T, points_C.empty() ? nullptr : reinterpret_cast<const float*>(points_C.data()), points_C.size(), &ac, out,
+                        &last_align_stats_),
+        "ks_align_points");
+  *T_refined = vxb::Transformation(out[0], out[1], out[2], out[3], vxb::Point(out[4], out[5], out[6]));
+  return last_align_stats_.iterations != 0;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

@@ -161,6 +161,20 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   bool renderView(const vxb::Transformation& T_G_C, float fx, float fy, float cx, float cy, int width, int height,
                   const RenderOptions& options, RenderedView* out);
   const ks_render_stats& lastRenderStats() const { return last_render_stats_; }
+  /// Refines the pose of a cloud against the TSDF of the map ON THE DEVICE (ks_align_points; the contract is DESIGN.md, "Scan
+  /// alignment"): what Voxblox's ICP (`enable_icp`) does against the host layer, as the map is after the frames in flight.
+  /// Needs NO syncLayers(): the voxels stay in HBM, only the cloud and the pose travel.  dof_mask: bits 0-2 rotation about
+  /// world x, y, z, bits 3-5 translation; 0x3c = yaw and translation, Voxblox's default.  max_residual_m = 0: the truncation
+  /// distance.  *T_refined is the last accepted pose (T_G_C itself when no step was taken); lastAlignStats().status says how
+  /// the loop ended.  Returns true when at least one step was taken.
+  struct AlignOptions {
+    float min_weight = 1e-4f, max_residual_m = 0.0f, damping = 1e-6f, eps_rotation_rad = 1e-4f, eps_translation_m = 1e-4f;
+    int max_iterations = 10, point_stride = 1, min_inliers = 64;
+    uint32_t dof_mask = 0x3fu;
+  };
+  bool alignPointCloud(const vxb::Transformation& T_G_C, const vxb::Pointcloud& points_C, const AlignOptions& options,
+                       vxb::Transformation* T_refined);
+  const ks_align_stats& lastAlignStats() const { return last_align_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -176,6 +190,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_esdf_stats last_esdf_stats_{};
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
   ks_render_stats last_render_stats_{};
+  ks_align_stats last_align_stats_{};
   void downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out);
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand

@@ -6,9 +6,11 @@ the GPU (ks_integrate_depth), report frames/s and voxel updates/s.  The semantic
 generates at the end of a bag (:147-167) — is extracted on the device (ks_mesh_update) with --mesh / --mesh-every, and the
 batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf, and kept up to date while frames stream in
 (ks_esdf_refresh) with --esdf-every; --render-every writes what the map looks like from the frame's own pose and intrinsics
-(ks_render_view: depth, labels, colours, normals) every N frames; map saving stays on the host side of the drop-in boundary (out of scope).
+(ks_render_view: depth, labels, colours, normals) every N frames; --align refines every frame's pose against the map on the
+device before the frame is integrated (ks_align_points: what `enable_icp` selects in the reference's launch files, without a layer
+sync) and prints the correction; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--render-every 10 --render-out views/]
+      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -50,6 +52,12 @@ def main():
                     "every N frames (ks_render_view; completes the frames in flight)")
     ap.add_argument("--render-out", metavar="DIR", help="where --render-every writes view_<frame>.npz (depth, labels, rgba, normals, T_G_C, K)")
     ap.add_argument("--render-max-range", type=float, default=10.0, metavar="M")
+    ap.add_argument("--align", action="store_true", help="refine every frame's pose against the map on the device before integrating it "
+                    "(ks_align_points; skipped while the map is empty; completes the frames in flight)")
+    ap.add_argument("--align-iterations", type=int, default=10, metavar="N", help="the reference's icp_iterations")
+    ap.add_argument("--align-dof", type=lambda v: int(v, 0), default=0x3f, metavar="MASK", help="bits 0-2 rotation about world x, y, z, bits 3-5 "
+                    "translation; 0x3c = yaw and translation")
+    ap.add_argument("--align-stride", type=int, default=1, metavar="N", help="use every N-th pixel")
     a = ap.parse_args()
     if a.render_every and not a.render_out:
         ap.error("--render-every needs --render-out")
@@ -107,8 +115,25 @@ def main():
             m = integ.mesh(only_stale=True)        # (completes the frames in flight, like every query)
             refresh_s += time.perf_counter() - t1
             refreshes.append((m.stats["blocks_meshed"], m.stats["blocks_total"], m.n_triangles))
+    align_s, aligned = 0.0, []
+
+    def refine(fr, T):
+        nonlocal align_s
+        if len(integ.block_indices()) == 0:     # nothing to align against yet
+            return T
+        xyz = synth.backproject(np.asarray(fr.depth, np.float32), fr.K).reshape(-1, 3)
+        t1 = time.perf_counter()
+        T_out, st = integ.align(T, xyz, max_iterations=a.align_iterations, dof_mask=a.align_dof, point_stride=a.align_stride)
+        align_s += time.perf_counter() - t1
+        aligned.append(st)
+        dt_m = float(np.linalg.norm(T_out[4:].astype(np.float64) - np.asarray(T, np.float64)[4:]))
+        dot = abs(float(np.dot(T_out[:4].astype(np.float64), np.asarray(T, np.float64)[:4]))) / float(np.linalg.norm(np.asarray(T, np.float64)[:4]))
+        print(f"frame {len(aligned)}: pose corrected by {dt_m * 1e3:.2f} mm, {np.degrees(2 * np.arccos(min(dot, 1.0))):.4f} deg; status {st['status']} after "
+              f"{st['iterations']} iterations, {st['inliers_first']} of {st['points_used']} points inliers, rmse {st['rmse_first']:.4f} -> {st['rmse_last']:.4f} m")
+        return T_out
+
     t0 = time.perf_counter()
-    out = FS.replay(seq, integ, use_label_img=not a.bag, on_frame=acc)
+    out = FS.replay(seq, integ, use_label_img=not a.bag, on_frame=acc, refine=refine if a.align else None)
     upd += integ.flush().n_voxel_updates
     integ.synchronize()
     dt = time.perf_counter() - t0
@@ -123,6 +148,9 @@ def main():
         last = esdf_ticks[-1]
         print(f"1 ESDF update and {len(esdf_ticks) - 1} refreshes in {esdf_s * 1e3:.1f} ms of the above; last refresh: {last['tiles_recomputed']} of "
               f"{last['tiles_total']} tiles recomputed ({last['tiles_stale']} stale), work space {last['workspace_bytes'] / 2 ** 20:.1f} MiB")
+    if aligned:
+        print(f"{len(aligned)} poses refined (incl. the upload of the cloud) in {align_s * 1e3:.1f} ms of the above: {align_s / len(aligned) * 1e3:.2f} ms each; "
+              f"{sum(s['status'] == B.KS_ALIGN_CONVERGED for s in aligned)} converged")
     if renders:
         last = renders[-1]
         print(f"{len(renders)} views rendered (incl. the download of the four images) in {render_s * 1e3:.1f} ms of the above: "
