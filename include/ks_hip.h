@@ -447,6 +447,59 @@ int ks_align_points(ks_ctx* ctx, const float T_G_C_in[7], const float* xyz /* ho
 int ks_align_points_device(ks_ctx* ctx, const float T_G_C_in[7], const float* d_xyz, size_t n, const ks_align_config* cfg,
                            float T_G_C_out[7], ks_align_stats* stats);
 
+/* ---- semantic object instances: the surface of every label clustered into connected components (new: the scene-graph work
+ * downstream of this map builds its objects from exactly this, on the host, from a downloaded layer) ----
+ * The contract is DESIGN.md, section "Object instances".  The global index of a voxel is 8 * tile + local per axis.  A voxel of
+ * a resident tile is a SURFACE voxel iff weight >= min_weight and |distance| <= surface_distance_m (a NaN distance is none); its
+ * label is dword 3 of its record (255 reads as 0, as in ks_download_blocks); it TAKES PART iff it is a surface voxel, its label
+ * is < 21 and bit `label` of label_mask is set.  Two voxels that take part are adjacent iff they have the same label and their
+ * global indices differ by at most 1 on every axis (26-connectivity, across tile seams; a neighbour in a tile that is not
+ * resident does not exist); a COMPONENT is an equivalence class of the closure, an OBJECT a component of at least min_voxels
+ * voxels.  Everything in a record is an integer (no floating-point sums, no floating-point atomics):
+ * centroid_k = ((double)sum_k / n_voxels + 0.5) * voxel_size is the host's one division.
+ * Order (part of the ABI): objects ascend by pack_coord3(first_voxel), i.e. by (x, y, z) of their smallest voxel.  Two calls on
+ * the same map give the same bytes, and so do the same voxels uploaded in another block order (nothing depends on slots).
+ * ks_objects_update   clusters the map as it is after the frames in flight have completed, and stores the records and, beside
+ *                     the tiles, one uint32 per voxel: the index of its object in that list, or KS_OBJECT_NONE (the voxel takes
+ *                     no part; its component is below min_voxels; its tile joined the map after the call).  Later integrate
+ *                     calls do not change what is stored; ks_clear and ks_clear_voxels drop it.  stats: voxels_surface = voxels
+ *                     taking part, components = before the min_voxels filter, objects, voxels_in_objects,
+ *                     largest_object_voxels, workspace_bytes.  The call only READS the map: the `updated` and `dirty` flags, both
+ *                     stale bits, the stored mesh and the stored ESDF stay as they were.
+ * ks_objects_size / ks_objects_download   the number of records / the records (cap >= that number).
+ * ks_objects_download_blocks   vps^3 ids per host-layout block in x + vps * (y + vps * z) order; absent blocks read as none.
+ * ks_objects_query    the id of the voxel that contains each point (the point-to-voxel rule of ks_esdf_query); out-of-range
+ *                     points and non-resident tiles read as none.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; min_weight not a finite positive number; surface_distance_m negative or not
+ * finite; label_mask 0 or with a bit >= 21 set; min_voxels < 1; size, download or query before any update; capacity too small),
+ * KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact; a map of 2^23 tiles or more, beyond what a pool can hold: a
+ * voxel's id is slot * 512 + local in 32 bits), KS_ERR_HIP (nothing stays stored afterwards).  An empty map is no error: zero
+ * objects.  ks_objects_download_blocks and ks_objects_query complete the frames in flight too (as ks_esdf_query does), although
+ * what they read is the store of the last update.  Multi-GPU: each context clusters the tiles it holds; seams between owners are not joined. */
+typedef struct ks_objects_config {
+  float min_weight;         /* 1e-4 */
+  float surface_distance_m; /* 0: the context's voxel_size */
+  uint32_t label_mask;      /* 0x1fffff */
+  uint32_t min_voxels;      /* 8 */
+} ks_objects_config;
+typedef struct ks_objects_stats {
+  uint64_t voxels_surface, components, objects, voxels_in_objects, largest_object_voxels, workspace_bytes;
+} ks_objects_stats; /* 48 bytes */
+typedef struct ks_object {
+  int32_t first_voxel[3]; /* the component's smallest global voxel index in (x, y, z) order: its identity */
+  uint32_t n_voxels;
+  int32_t bb_min[3], bb_max[3]; /* inclusive, global voxel indices */
+  int64_t sum[3];               /* sums of the voxels' global indices */
+  uint32_t label, pad;          /* pad = 0 */
+} ks_object; /* 72 bytes */
+#define KS_OBJECT_NONE 0xffffffffu
+int ks_objects_default_config(ks_objects_config* cfg);
+int ks_objects_update(ks_ctx* ctx, const ks_objects_config* cfg, ks_objects_stats* stats /* may be NULL */);
+int ks_objects_size(ks_ctx* ctx, size_t* n);
+int ks_objects_download(ks_ctx* ctx, ks_object* out, size_t cap, size_t* n);
+int ks_objects_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, uint32_t* out /* n * vps^3 ids, host block layout */);
+int ks_objects_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* id);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

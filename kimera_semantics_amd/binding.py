@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "ks_esdf_refresh", "ks_esdf_changed_blocks",
     "ks_render_default_config", "ks_render_view", "ks_render_view_device",
     "ks_align_default_config", "ks_align_points", "ks_align_points_device",
+    "ks_objects_default_config", "ks_objects_update", "ks_objects_size", "ks_objects_download", "ks_objects_download_blocks", "ks_objects_query",
 ]
 
 
@@ -131,6 +132,27 @@ class KsAlignStats(C.Structure):
                 ("inliers_last", C.c_uint64), ("rmse_first", C.c_double), ("rmse_last", C.c_double)]
 
 
+class KsObjectsConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("surface_distance_m", C.c_float), ("label_mask", C.c_uint32), ("min_voxels", C.c_uint32)]
+
+
+class KsObjectsStats(C.Structure):
+    _fields_ = [("voxels_surface", C.c_uint64), ("components", C.c_uint64), ("objects", C.c_uint64), ("voxels_in_objects", C.c_uint64),
+                ("largest_object_voxels", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
+# ks_object: 72 bytes; centroid_k = (sum_k / n_voxels + 0.5) * voxel_size (object_centroids)
+OBJECT_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
+                         ("sum", "<i8", (3,)), ("label", "<u4"), ("pad", "<u4")])
+KS_OBJECT_NONE = 0xffffffff
+
+
+def object_centroids(records, voxel_size) -> np.ndarray:
+    """Centroids in metres, (n, 3) f64, of ks_object records: the host's one division."""
+    r = np.asarray(records)
+    return (r["sum"].astype(np.float64) / np.maximum(r["n_voxels"], 1)[:, None].astype(np.float64) + 0.5) * float(voxel_size)
+
+
 KS_ALIGN_CONVERGED, KS_ALIGN_ITERATION_LIMIT, KS_ALIGN_TOO_FEW_INLIERS, KS_ALIGN_DEGENERATE = 0, 1, 2, 3
 
 
@@ -145,7 +167,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -227,6 +249,12 @@ def lib():
         L.ks_align_default_config.argtypes = [C.POINTER(KsAlignConfig)]
         L.ks_align_points.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(KsAlignConfig), vp, C.POINTER(KsAlignStats)]
         L.ks_align_points_device.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(KsAlignConfig), vp, C.POINTER(KsAlignStats)]
+        L.ks_objects_default_config.argtypes = [C.POINTER(KsObjectsConfig)]
+        L.ks_objects_update.argtypes = [vp, C.POINTER(KsObjectsConfig), C.POINTER(KsObjectsStats)]
+        L.ks_objects_size.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.ks_objects_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_objects_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_objects_query.argtypes = [vp, vp, C.c_size_t, vp]
         _lib = L
     return _lib
 
@@ -532,6 +560,47 @@ class HipIntegrator:
         ac, st, out = self.align_config(**cfg), KsAlignStats(), np.zeros(7, np.float32)
         self._chk(lib().ks_align_points_device(self._h, _ptr(T), d_xyz or None, int(n), C.byref(ac), _ptr(out), C.byref(st)))
         return out, self._align_stats(st)
+
+    def objects_config(self, **cfg) -> KsObjectsConfig:
+        oc = KsObjectsConfig()
+        lib().ks_objects_default_config(C.byref(oc))
+        for k, v in cfg.items():
+            if k not in [f for f, _ in KsObjectsConfig._fields_]:
+                raise AttributeError(k)
+            if v is not None:
+                setattr(oc, k, v)
+        return oc
+
+    def objects(self, **cfg):
+        """ks_objects_update + ks_objects_download: clusters the surface voxels of every label into 26-connected components and
+        returns (records (n,) OBJECT_DTYPE ascending by first_voxel, stats dict).  cfg are the fields of KsObjectsConfig.  The
+        contract is DESIGN.md, section "Object instances"; object_ids() / object_query() read the per-voxel ids it stores."""
+        oc, st = self.objects_config(**cfg), KsObjectsStats()
+        self._chk(lib().ks_objects_update(self._h, C.byref(oc), C.byref(st)))
+        return self.object_records(), {k: int(getattr(st, k)) for k, _ in KsObjectsStats._fields_}
+
+    def object_records(self) -> np.ndarray:
+        """The records of the last objects() call."""
+        n = C.c_size_t()
+        self._chk(lib().ks_objects_size(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=OBJECT_DTYPE)
+        self._chk(lib().ks_objects_download(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def object_ids(self, block_idx) -> np.ndarray:
+        """(N, vps^3) u32 in host block layout: the index of each voxel's object in the records of the last objects() call, or
+        KS_OBJECT_NONE."""
+        indices = np.ascontiguousarray(block_idx, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((len(indices), self.vps ** 3), dtype=np.uint32)
+        self._chk(lib().ks_objects_download_blocks(self._h, _ptr(indices), len(indices), _ptr(out)))
+        return out
+
+    def object_query(self, xyz) -> np.ndarray:
+        """(n,) u32: the object id of the voxel that contains each world point, or KS_OBJECT_NONE."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(xyz), dtype=np.uint32)
+        self._chk(lib().ks_objects_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
+        return out
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----
     TILE_BYTES = 65536

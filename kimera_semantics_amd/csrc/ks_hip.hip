@@ -70,6 +70,7 @@ using namespace ksd;
 #include "ks_k_esdf.h"
 #include "ks_k_render.h"
 #include "ks_k_align.h"
+#include "ks_k_objects.h"
 
 using namespace ksk;
 
@@ -510,6 +511,23 @@ struct ks_ctx {
   DevBuf<double> align_partials;
   DevBuf<AlignState> align_state;
   DevBuf<float> align_xyz;
+  // ks_objects_update (ks_k_objects.h).  The id store holds 512 words per tile slot: the objects of the map as it was at the last
+  // update; everything grows only.
+  DevBuf<uint32_t> obj_ids;                // [obj_tiles][512] (during an update: the provisional numbers of the roots)
+  DevBuf<uint32_t> obj_parent;             // the union-find forest of an update, then the voxels' provisional numbers
+  DevBuf<uint8_t> obj_cls;                 // the class byte of every voxel
+  DevBuf<ObjCounters> obj_counters;
+  DevBuf<ObjAcc> obj_acc;                  // per provisional component
+  DevBuf<uint64_t> obj_keys[2];            // the sort's key and payload buffers
+  DevBuf<uint32_t> obj_vals[2];
+  DevBuf<uint32_t> obj_final;              // provisional number -> object index
+  DevBuf<ks_object> obj_records;
+  DevBuf<uint32_t> obj_out;                // staging of download and query
+  DevBuf<int32_t> obj_idx;
+  DevBuf<float> obj_xyz;
+  bool obj_valid = false;                  // an update has run since the map was last cleared
+  uint32_t obj_tiles = 0;                  // tiles that were resident at that update
+  size_t obj_count = 0;                    // records stored
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -3713,6 +3731,168 @@ int ks_align_points(ks_ctx* c, const float T[7], const float* xyz, size_t n, con
   return align_run(c, "ks_align_points", T, c->align_xyz, n, a, T_out, stats);
 }
 
+// ---- object instances ("Object instances"; ks_k_objects.h) --------------------------------------
+int ks_objects_default_config(ks_objects_config* o) {
+  if (!o) return KS_ERR_INVALID_ARG;
+  o->min_weight = 1e-4f;
+  o->surface_distance_m = 0.0f;
+  o->label_mask = 0x1fffffu;
+  o->min_voxels = 8;
+  return KS_OK;
+}
+
+int ks_objects_update(ks_ctx* c, const ks_objects_config* o, ks_objects_stats* stats) {
+  if (!c || !o) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  auto refuse = [&](const char* why) {
+    c->err = std::string("ks_objects_update: ") + why;
+    return KS_ERR_INVALID_ARG;
+  };
+  if (!(o->min_weight > 0.0f) || !std::isfinite(o->min_weight)) return refuse("min_weight must be a finite positive number");
+  if (!(o->surface_distance_m >= 0.0f) || !std::isfinite(o->surface_distance_m)) return refuse("surface_distance_m must be finite and not negative");
+  if (o->label_mask == 0 || (o->label_mask >> kObjLabels) != 0) return refuse("label_mask must name at least one of the labels 0..20 and nothing else");
+  if (o->min_voxels < 1) return refuse("min_voxels must be at least 1");
+  if (int rc = holds_voxels(c, "ks_objects_update")) return rc;
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->tiles_initialised;
+  if (nt >= (1u << 23)) {   // (a voxel's id is slot * 512 + local in 32 bits, all-ones = none)
+    c->err = "ks_objects_update: too many tiles for one call";
+    return KS_ERR_UNSUPPORTED;
+  }
+  const size_t nvox = (size_t)nt * kTileVoxels;
+  int rc;
+  c->obj_valid = false;   // (a failure below leaves nothing half-written readable)
+  c->obj_count = 0;
+  if ((rc = c->obj_ids.reserve(c, nvox, ((size_t)nt + nt / 2 + 64) * kTileVoxels)) || (rc = c->obj_parent.reserve(c, nvox, nvox + nvox / 2)) ||
+      (rc = c->obj_cls.reserve(c, nvox, nvox + nvox / 2)) || (rc = c->obj_counters.reserve(c, 1, 1)))
+    return rc;
+  HIPCHK(c, hipMemsetAsync(c->obj_counters, 0, sizeof(ObjCounters), st));
+  ObjParams O{};
+  O.min_weight = o->min_weight;
+  O.surface_distance = o->surface_distance_m == 0.0f ? c->cfg.voxel_size : o->surface_distance_m;
+  O.label_mask = o->label_mask;
+  O.min_voxels = o->min_voxels;
+  O.nt = nt;
+  ObjCounters counts{};
+  uint64_t workspace = (uint64_t)nvox * 9 + sizeof(ObjCounters);   // the forest, the id store, the class bytes
+  if (nt) {
+    // 1) - 3) in-tile labelling, seams, flat forest and provisional numbers
+    hipLaunchKernelGGL(k_obj_label, dim3(nt), dim3(512), 0, st, c->pool, O, c->obj_cls.get(), c->obj_parent.get(), c->obj_counters.get());
+    hipLaunchKernelGGL(k_obj_seams, dim3(nt), dim3(512), 0, st, c->table, O, (const uint8_t*)c->obj_cls.get(), c->obj_parent.get());
+    hipLaunchKernelGGL(k_obj_number, dim3(nt * 2), dim3(256), 0, st, c->obj_parent.get(), c->obj_ids.get(), c->obj_counters.get());
+    HIPCHK(c, hipMemcpyAsync(&counts, c->obj_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the one read that sizes what follows
+    const uint32_t nc = counts.n_components;
+    if (nc) {
+      // 4) + 5) reduce, filter, order, assign
+      const size_t cap = (size_t)nc + nc / 2;
+      if ((rc = c->obj_acc.reserve(c, nc, cap)) || (rc = c->obj_final.reserve(c, nc, cap)) || (rc = c->obj_records.reserve(c, nc, cap))) return rc;
+      for (int k = 0; k < 2; ++k)
+        if ((rc = c->obj_keys[k].reserve(c, nc, cap)) || (rc = c->obj_vals[k].reserve(c, nc, cap))) return rc;
+      const dim3 per_comp((nc + 255) / 256);
+      hipLaunchKernelGGL(k_obj_acc_init, per_comp, dim3(256), 0, st, c->obj_acc.get(), nc);
+      hipLaunchKernelGGL(k_obj_reduce, dim3(nt * 2), dim3(256), 0, st, c->table, (const uint8_t*)c->obj_cls.get(), c->obj_parent.get(),
+                         (const uint32_t*)c->obj_ids.get(), c->obj_acc.get());
+      hipLaunchKernelGGL(k_obj_keys, per_comp, dim3(256), 0, st, (const ObjAcc*)c->obj_acc.get(), nc, O.min_voxels, c->obj_keys[0].get(),
+                         c->obj_vals[0].get(), c->obj_counters.get());
+      uint64_t* keys = nullptr;
+      uint32_t* vals = nullptr;
+      if ((rc = sort_pairs(c, c->obj_keys[0].get(), c->obj_keys[1].get(), c->obj_vals[0].get(), c->obj_vals[1].get(), nc, 64, &keys, &vals))) return rc;
+      hipLaunchKernelGGL(k_obj_records, per_comp, dim3(256), 0, st, (const ObjAcc*)c->obj_acc.get(), nc, (const uint64_t*)keys, (const uint32_t*)vals,
+                         c->obj_records.get(), c->obj_final.get());
+      workspace += (uint64_t)nc * (sizeof(ObjAcc) + sizeof(ks_object) + 2 * 8 + 3 * 4);
+    }
+    hipLaunchKernelGGL(k_obj_ids, dim3((uint32_t)((nvox + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->obj_parent.get(),
+                       (const uint32_t*)c->obj_final.get(), c->obj_ids.get(), nvox);
+    HIPCHK(c, hipMemcpyAsync(&counts, c->obj_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->obj_valid = true;
+  c->obj_tiles = nt;
+  c->obj_count = counts.n_objects;
+  if (stats) {
+    stats->voxels_surface = counts.voxels_surface;
+    stats->components = counts.n_components;
+    stats->objects = counts.n_objects;
+    stats->voxels_in_objects = counts.voxels_in_objects;
+    stats->largest_object_voxels = counts.largest;
+    stats->workspace_bytes = workspace;
+  }
+  return KS_OK;
+}
+
+static int objects_ready(ks_ctx* c, const char* who) {
+  if (c->obj_valid) return KS_OK;
+  c->err = std::string(who) + ": no objects are stored (ks_objects_update has not run since the map was created or cleared)";
+  return KS_ERR_INVALID_ARG;
+}
+
+int ks_objects_size(ks_ctx* c, size_t* n) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
+  if (int rc = objects_ready(c, "ks_objects_size")) return rc;
+  *n = c->obj_count;
+  return KS_OK;
+}
+
+int ks_objects_download(ks_ctx* c, ks_object* out, size_t cap, size_t* n) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = objects_ready(c, "ks_objects_download")) return rc;
+  if (n) *n = c->obj_count;
+  if (cap < c->obj_count || (c->obj_count && !out)) {
+    c->err = "ks_objects_download: output buffer too small";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (c->obj_count) HIPCHK(c, hipMemcpy(out, c->obj_records.get(), c->obj_count * sizeof(ks_object), hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+
+int ks_objects_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, uint32_t* out) {
+  if (!c || (n && (!idx || !out))) return KS_ERR_INVALID_ARG;
+  if (int rc = objects_ready(c, "ks_objects_download_blocks")) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const int vps = c->cfg.voxels_per_side;
+  const size_t nv = (size_t)vps * vps * vps;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(64) << 20) / (nv * sizeof(uint32_t))), 65535);   // <= 64 MiB staged at a time
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->obj_out.reserve(c, m_max * nv, m_max * nv))) return rc;
+  if ((rc = c->obj_idx.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->obj_idx, idx + 3 * off, m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_download, dim3((uint32_t)((nv + 255) / 256), (uint32_t)m), dim3(256), 0, c->stream, c->table,
+                       (const uint32_t*)c->obj_ids.get(), c->obj_tiles, (const int32_t*)c->obj_idx.get(), vps, c->obj_out.get());
+    HIPCHK(c, hipMemcpyAsync(out + off * nv, c->obj_out, m * nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_objects_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* id) {
+  if (!c || (n && (!xyz || !id))) return KS_ERR_INVALID_ARG;
+  if (int rc = objects_ready(c, "ks_objects_query")) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const size_t m_max = std::min(size_t(1) << 22, n);
+  int rc;
+  if ((rc = c->obj_out.reserve(c, m_max, m_max))) return rc;
+  if ((rc = c->obj_xyz.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->obj_xyz, xyz + 3 * off, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_query, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, (const uint32_t*)c->obj_ids.get(),
+                       c->obj_tiles, (const float*)c->obj_xyz.get(), m, c->voxel_size_inv, c->obj_out.get());
+    HIPCHK(c, hipMemcpyAsync(id + off, c->obj_out, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
 // ---- voxel-level host sync -------------------------------------------------------------------------------
 // Device-side address of a host allocation the GPU can write (hipHostMalloc'ed: ks_host_alloc), else nullptr.
 static void* device_view_of_pinned(void* p) {
@@ -4408,6 +4588,9 @@ static void mesh_reset(ks_ctx* c) {
   c->esdf_valid = false;   // the stored ESDF goes with the map
   c->esdf_tiles = 0;
   c->esdf_changed.clear();
+  c->obj_valid = false;    // ... and the stored objects
+  c->obj_tiles = 0;
+  c->obj_count = 0;
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {

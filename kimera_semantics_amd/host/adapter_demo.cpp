@@ -233,6 +233,35 @@ int main(int argc, char** argv) {
                 (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
   }
 
+  // KS_DEMO_OBJECTS=<file>: the object instances of the map, made on the device without any layer sync (extractObjects,
+  // default options), written as { u32 objects; per object: u32 label, u32 n_voxels, i64 first_voxel[3], i64 bb_min[3],
+  // i64 bb_max[3], f32 centroid[3] }
+  if (const char* objects_path = std::getenv("KS_DEMO_OBJECTS")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    std::vector<kimera::HipSemanticTsdfIntegrator::ObjectInstance> objects;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->extractObjects(kimera::HipSemanticTsdfIntegrator::ObjectOptions(), &objects);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* of = std::fopen(objects_path, "wb");
+    if (!of) return 9;
+    const uint32_t n_objects = objects.size();
+    std::fwrite(&n_objects, 4, 1, of);
+    for (const auto& o : objects) {
+      const uint32_t head[2] = {o.label, o.n_voxels};
+      const int64_t box[9] = {o.first_voxel.x(), o.first_voxel.y(), o.first_voxel.z(), o.bb_min.x(), o.bb_min.y(), o.bb_min.z(),
+                              o.bb_max.x(), o.bb_max.y(), o.bb_max.z()};
+      const float c[3] = {o.centroid.x(), o.centroid.y(), o.centroid.z()};
+      std::fwrite(head, 4, 2, of);
+      std::fwrite(box, 8, 9, of);
+      std::fwrite(c, 4, 3, of);
+    }
+    std::fclose(of);
+    const ks_objects_stats& os = hip->lastObjectsStats();
+    std::printf("adapter_demo: extractObjects %.3f ms, %u objects of %llu components, %llu of %llu surface voxels in objects\n", ms, n_objects,
+                (unsigned long long)os.components, (unsigned long long)os.voxels_in_objects, (unsigned long long)os.voxels_surface);
+  }
+
   // KS_DEMO_ALIGN=<file>: the LAST frame's pose, moved by (0.03, -0.02, 0.025) m and turned by 1.5 degrees about
   // (1, 2, -1) / sqrt(6) in the world frame, refined against the map with that frame's cloud on the device without any layer
   // sync (alignPointCloud, default options), written as { f32 T_in[7]; f32 T_out[7]; ks_align_stats (48 bytes) }

@@ -360,6 +360,37 @@ bool HipSemanticTsdfIntegrator::alignPointCloud(const vxb::Transformation& T_G_C
   return last_align_stats_.iterations != 0;
 }
 
+bool HipSemanticTsdfIntegrator::extractObjects(const ObjectOptions& options, std::vector<ObjectInstance>* out) {
+  CHECK_NOTNULL(out);
+  out->clear();
+  ks_objects_config oc;
+  ks_objects_default_config(&oc);
+  oc.min_weight = options.min_weight;
+  oc.surface_distance_m = options.surface_distance_m;
+  oc.label_mask = options.label_mask;
+  oc.min_voxels = options.min_voxels;
+  check(ks_objects_update(ctx_, &oc, &last_objects_stats_), "ks_objects_update");
+  size_t n = 0;
+  check(ks_objects_size(ctx_, &n), "ks_objects_size");
+  if (n == 0) return false;
+  std::vector<ks_object> rec(n);
+  check(ks_objects_download(ctx_, rec.data(), n, &n), "ks_objects_download");
+  const double voxel_size = semantic_layer_ptr_->voxel_size();
+  out->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    ObjectInstance& o = (*out)[i];
+    const ks_object& r = rec[i];
+    o.label = static_cast<uint8_t>(r.label);
+    o.n_voxels = r.n_voxels;
+    o.first_voxel = vxb::GlobalIndex(r.first_voxel[0], r.first_voxel[1], r.first_voxel[2]);
+    o.bb_min = vxb::GlobalIndex(r.bb_min[0], r.bb_min[1], r.bb_min[2]);
+    o.bb_max = vxb::GlobalIndex(r.bb_max[0], r.bb_max[1], r.bb_max[2]);
+    for (int k = 0; k < 3; ++k)   // the one division of the contract
+      o.centroid[k] = static_cast<float>((static_cast<double>(r.sum[k]) / static_cast<double>(r.n_voxels) + 0.5) * voxel_size);
+  }
+  return true;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

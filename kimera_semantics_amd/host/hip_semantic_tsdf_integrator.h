@@ -175,6 +175,23 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   bool alignPointCloud(const vxb::Transformation& T_G_C, const vxb::Pointcloud& points_C, const AlignOptions& options,
                        vxb::Transformation* T_refined);
   const ks_align_stats& lastAlignStats() const { return last_align_stats_; }
+  /// The object instances of the map (ks_objects_update; the contract is DESIGN.md, "Object instances"): the surface voxels of
+  /// every label clustered into 26-connected components ON THE DEVICE, as the map is after the frames in flight.  Needs NO
+  /// syncLayers(): the voxels stay in HBM, only the records travel.  What a scene-graph builder downstream of the reference does
+  /// on the host from a synced layer.  surface_distance_m = 0: the voxel size.  Objects ascend by their smallest voxel (x, y, z).
+  struct ObjectOptions {
+    float min_weight = 1e-4f, surface_distance_m = 0.0f;
+    uint32_t label_mask = 0x1fffffu, min_voxels = 8;
+  };
+  struct ObjectInstance {
+    uint8_t label;
+    uint32_t n_voxels;
+    vxb::GlobalIndex first_voxel, bb_min, bb_max;   ///< global voxel indices, the box inclusive; first_voxel is the identity
+    vxb::Point centroid;                            ///< metres, world frame
+  };
+  /// Returns true when `out` is not empty.
+  bool extractObjects(const ObjectOptions& options, std::vector<ObjectInstance>* out);
+  const ks_objects_stats& lastObjectsStats() const { return last_objects_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -191,6 +208,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};
+  ks_objects_stats last_objects_stats_{};
   void downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out);
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand

@@ -8,9 +8,10 @@ batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf, 
 (ks_esdf_refresh) with --esdf-every; --render-every writes what the map looks like from the frame's own pose and intrinsics
 (ks_render_view: depth, labels, colours, normals) every N frames; --align refines every frame's pose against the map on the
 device before the frame is integrated (ks_align_points: what `enable_icp` selects in the reference's launch files, without a layer
-sync) and prints the correction; map saving stays on the host side of the drop-in boundary (out of scope).
+sync) and prints the correction; --objects clusters the surface of every label into object instances on the device at the end
+of the replay (ks_objects_update) and writes their records, centroids in metres and label names; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c]
+      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -58,6 +59,9 @@ def main():
     ap.add_argument("--align-dof", type=lambda v: int(v, 0), default=0x3f, metavar="MASK", help="bits 0-2 rotation about world x, y, z, bits 3-5 "
                     "translation; 0x3c = yaw and translation")
     ap.add_argument("--align-stride", type=int, default=1, metavar="N", help="use every N-th pixel")
+    ap.add_argument("--objects", metavar="OUT.npz", help="cluster the surface voxels of every label into object instances at the end of the replay and "
+                    "write them (records (n,) of 72 bytes ascending by first_voxel, centroids_m (n, 3), label_names (n,), voxel_size)")
+    ap.add_argument("--objects-min-voxels", type=int, default=8, metavar="N")
     a = ap.parse_args()
     if a.render_every and not a.render_out:
         ap.error("--render-every needs --render-out")
@@ -66,12 +70,14 @@ def main():
     else:
         seq = FS.synthetic_sequence(a.synthetic or 20)
     lut = synth.default_label_colors()
+    names = {}
     if a.label_csv:
         import csv
         lut = np.zeros((256, 4), np.uint8)
         for row in csv.reader(open(a.label_csv)):
             try:
                 lut[int(row[5])] = [int(row[1]), int(row[2]), int(row[3]), int(row[4])]
+                names.setdefault(int(row[5]), row[0])
             except (ValueError, IndexError):
                 continue
         lut[0] = [255, 255, 255, 255]
@@ -178,6 +184,16 @@ def main():
         how = f"{st['tiles_recomputed']} of {st['tiles_total']} tiles recomputed" if esdf_ticks else f"box {st['box_voxels']}"
         print(f"esdf: {st['voxels_observed']} observed voxels ({st['voxels_fixed']} in the band, {st['voxels_clamped']} at +-{a.esdf_max_distance} m), "
               f"{how}, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_esdf * 1e3:.2f} ms ({'refresh' if esdf_ticks else 'update'} + download) -> {a.esdf}")
+    if a.objects:
+        t1 = time.perf_counter()
+        rec, st = integ.objects(min_voxels=a.objects_min_voxels)
+        t_obj = time.perf_counter() - t1
+        label_names = np.array([names.get(int(l), "label_%d" % int(l)) for l in rec["label"]])
+        np.savez_compressed(a.objects, records=rec, centroids_m=B.object_centroids(rec, integ.cfg.voxel_size), label_names=label_names,
+                            voxel_size=np.float32(a.voxel_size))
+        print(f"objects: {st['objects']} objects of {st['components']} components over {st['voxels_surface']} surface voxels "
+              f"({st['voxels_in_objects']} in objects, the largest {st['largest_object_voxels']}), labels {sorted(set(rec['label'].tolist()))}, "
+              f"work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_obj * 1e3:.2f} ms (update + download) -> {a.objects}")
 
 
 if __name__ == "__main__":
