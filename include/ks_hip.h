@@ -519,6 +519,51 @@ int ks_clear(ks_ctx* ctx);
  * This is what voxblox::TsdfServer::clear() does to the reference's integrator (nothing); integration/server.patch calls
  * it, then uploads the semantic layer that survives clear() in the reference. */
 int ks_clear_voxels(ks_ctx* ctx);
+/* ---- removal of blocks from the resident map (new on this side of the boundary: voxblox::TsdfServer prunes its TSDF layer after
+ * every integrated cloud with Layer::removeDistantBlocks, parameter max_block_distance_from_body; without these calls that
+ * empties the host layer only, the tiles stay in HBM and host and device disagree as soon as a pruned block is touched again) ----
+ * The contract is DESIGN.md §16.
+ * ks_remove_blocks           takes the given host-layout blocks (edge voxels_per_side) out of the map, all (vps / 8)^3 device
+ *                            tiles of a block together.  A block that is not resident is ignored, and so is a repeated index;
+ *                            n = 0 removes nothing.
+ * ks_remove_distant_blocks   the rule of Voxblox's Layer::removeDistantBlocks as published (Voxblox is not part of the reference
+ *                            tree), evaluated on the device for every resident block, in f32, in this order, no contraction:
+ *                              block_size = voxel_size * (float)vps;  o_k = (float)b_k * block_size  (the block's ORIGIN, not
+ *                              its centre);  d_k = o_k - center_k;  d2 = (dx * dx + dy * dy) + dz * dz;
+ *                            the block is removed iff d2 > max_distance_m * max_distance_m.  A block goes iff the rule holds for
+ *                            that block; tiles are never judged one by one.
+ * ks_removed_blocks          the blocks the LAST removal call took out, ascending by (x, y, z) like ks_get_block_indices (out_xyz
+ *                            may be NULL to ask for the count).
+ * Both removal calls complete the frames in flight first; the statistics of those frames stay owed to the next integrate call
+ * or ks_flush, and the integrator's own state (the two approximate sets of `fast`, their offsets, the clear-check counter, the
+ * exact early-out's table) stays as the frames left it, as with ks_clear_voxels.  Afterwards a removed block is not resident for
+ * any entry point: it is absent from ks_get_block_indices, ks_get_updated_block_indices and ks_get_tile_keys, reads as default
+ * voxels in ks_download_blocks, reports no voxels to ks_count_updated_voxels / ks_download_updated_voxels, and the renderer and
+ * the aligner see nothing there; a later integrate, upload or merge that touches it allocates fresh tiles (counted in
+ * n_blocks_allocated).  The tiles that stay keep their `updated` and `dirty` flags and both stale bits.  Slot numbers change:
+ * survivors move into the freed slots (what ks_get_tile_keys lists by slot is renumbered).  Freed slots are reused and
+ * pool_capacity_tiles never grows because of a removal; the pool ALLOCATION itself is not shrunk — returning memory is not part of
+ * these calls.
+ * The stored products: ks_mesh_update(only_stale = 1) after a removal leaves the stored mesh byte for byte what a from-scratch
+ * extraction gives — the removed blocks leave it, appear in ks_mesh_changed_blocks of that update, and the resident blocks whose
+ * border cubes read a removed tile are re-meshed, nothing else; until that update the stored mesh is the one of the last update.
+ * ks_esdf_refresh after a removal leaves the store byte for byte what ks_esdf_update would store now (the positions of the
+ * removed tiles count as stale tiles: every resident tile within g tiles of one is recomputed); with no stored ESDF nothing is
+ * done.  The object records stay the snapshot of the last ks_objects_update; ids travel with their tiles, and removed blocks
+ * read KS_OBJECT_NONE.
+ * stats: blocks_removed, tiles_removed, tiles_moved (survivors that changed slot, at most tiles_removed), tiles_resident after
+ * the call, pool_capacity_tiles.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx; NULL idx_xyz with n > 0; a NULL or non-finite centre; max_distance_m negative or not
+ * finite; ks_removed_blocks with a capacity that is too small; a context in a failed state), KS_ERR_INDEX_RANGE (a block index
+ * outside the packed range, as ks_upload_blocks reports it), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact),
+ * KS_ERR_HIP.  A call that fails before the first tile moves leaves the map as it was.
+ * Multi-GPU: each context removes among the tiles it holds. */
+typedef struct ks_remove_stats {
+  uint64_t blocks_removed, tiles_removed, tiles_moved, tiles_resident /* after */, pool_capacity_tiles;
+} ks_remove_stats; /* 40 bytes */
+int ks_remove_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, ks_remove_stats* stats /* may be NULL */);
+int ks_remove_distant_blocks(ks_ctx* ctx, const float center[3], float max_distance_m, ks_remove_stats* stats /* may be NULL */);
+int ks_removed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n); /* of the LAST removal call, ascending (x,y,z) */
 /* Resets the tiles at the given slots to the empty state (a rank that has handed tiles to their owner keeps
  * them as empty deltas). */
 int ks_reset_tiles(ks_ctx* ctx, const uint32_t* slots, size_t n);

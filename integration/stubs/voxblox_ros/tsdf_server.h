@@ -2,6 +2,7 @@
 // kimera::SemanticTsdfServer (kimera_semantics_ros/src/semantic_tsdf_server.cpp) and integration/server.patch touch.
 // Signatures as in ethz-asl/voxblox voxblox_ros/include/voxblox_ros/tsdf_server.h (not vendored under /root/reference).
 #pragma once
+#include <limits>
 #include <memory>
 #include <string>
 #include <ros/ros.h>
@@ -35,5 +36,7 @@ class TsdfServer {
  protected:
   std::shared_ptr<TsdfMap> tsdf_map_;
   std::unique_ptr<TsdfIntegratorBase> tsdf_integrator_;
+  /// processPointCloudMessageAndInsert: after integratePointcloud the TSDF layer's removeDistantBlocks(T_G_C.getPosition(), this)
+  FloatingPoint max_block_distance_from_body_ = std::numeric_limits<FloatingPoint>::max();
 };
 }  // namespace voxblox

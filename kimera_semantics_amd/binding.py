@@ -23,6 +23,7 @@ KS_BUNDLE_ORDER_REFERENCE, KS_BUNDLE_ORDER_CANONICAL = 0, 1
 KS_EARLY_OUT_EXACT = 1   # value of KsConfig.early_out_phase_growth: the reference's serial early-out result
 KS_ERR_LABEL_RANGE, KS_ERR_PROBABILITY, KS_ERR_POOL_FULL, KS_ERR_NO_DEVICE, KS_ERR_UNSUPPORTED = -2, -3, -5, -7, -8
 KS_ERR_INVALID_ARG, KS_ERR_PEER_FAILED = -1, -9
+KS_ERR_HIP, KS_ERR_INDEX_RANGE = -4, -6
 
 STAGES = ["points", "sort_points", "rays", "march", "emit", "sort_pairs", "apply", "apply_long"]
 
@@ -43,6 +44,7 @@ ABI_SYMBOLS = [
     "ks_render_default_config", "ks_render_view", "ks_render_view_device",
     "ks_align_default_config", "ks_align_points", "ks_align_points_device",
     "ks_objects_default_config", "ks_objects_update", "ks_objects_size", "ks_objects_download", "ks_objects_download_blocks", "ks_objects_query",
+    "ks_remove_blocks", "ks_remove_distant_blocks", "ks_removed_blocks",
 ]
 
 
@@ -141,6 +143,11 @@ class KsObjectsStats(C.Structure):
                 ("largest_object_voxels", C.c_uint64), ("workspace_bytes", C.c_uint64)]
 
 
+class KsRemoveStats(C.Structure):
+    _fields_ = [("blocks_removed", C.c_uint64), ("tiles_removed", C.c_uint64), ("tiles_moved", C.c_uint64), ("tiles_resident", C.c_uint64),
+                ("pool_capacity_tiles", C.c_uint64)]
+
+
 # ks_object: 72 bytes; centroid_k = (sum_k / n_voxels + 0.5) * voxel_size (object_centroids)
 OBJECT_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
                          ("sum", "<i8", (3,)), ("label", "<u4"), ("pad", "<u4")])
@@ -167,7 +174,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -255,6 +262,9 @@ def lib():
         L.ks_objects_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ks_objects_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_objects_query.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_remove_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsRemoveStats)]
+        L.ks_remove_distant_blocks.argtypes = [vp, vp, C.c_float, C.POINTER(KsRemoveStats)]
+        L.ks_removed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         _lib = L
     return _lib
 
@@ -648,6 +658,31 @@ class HipIntegrator:
     def clear_voxels(self):
         """The map goes, the integrator's sets and counters stay (ks_clear_voxels)."""
         self._chk(lib().ks_clear_voxels(self._h))
+
+    def remove_blocks(self, indices) -> dict:
+        """ks_remove_blocks: takes the host-layout blocks `indices` (n, 3) out of the map (absent and repeated ones are ignored).
+        Returns the stats; removed_blocks() lists what left.  The contract is DESIGN.md, section 16."""
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+        st = KsRemoveStats()
+        self._chk(lib().ks_remove_blocks(self._h, _ptr(indices) if len(indices) else None, len(indices), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in KsRemoveStats._fields_}
+
+    def remove_distant(self, center, max_distance_m) -> dict:
+        """ks_remove_distant_blocks: removes every block whose ORIGIN is further than max_distance_m from `center` (the rule of
+        Voxblox's Layer::removeDistantBlocks, evaluated on the device in f32).  Returns the stats."""
+        ctr = np.ascontiguousarray(center, dtype=np.float32).reshape(3)
+        st = KsRemoveStats()
+        self._chk(lib().ks_remove_distant_blocks(self._h, _ptr(ctr), float(max_distance_m), C.byref(st)))
+        return {k: int(getattr(st, k)) for k, _ in KsRemoveStats._fields_}
+
+    def removed_blocks(self) -> np.ndarray:
+        """The blocks the last remove_blocks() / remove_distant() took out, (n, 3) i32 ascending by (x, y, z)."""
+        n = C.c_size_t()
+        self._chk(lib().ks_removed_blocks(self._h, None, 0, C.byref(n)))
+        out = np.zeros((n.value, 3), dtype=np.int32)
+        if n.value:
+            self._chk(lib().ks_removed_blocks(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
 
     def reset_tiles(self, slots: np.ndarray):
         s = np.ascontiguousarray(slots, dtype=np.uint32)

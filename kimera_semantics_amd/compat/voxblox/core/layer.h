@@ -53,6 +53,7 @@ class Layer {
     (void)insert_status;
   }
   bool hasBlock(const BlockIndex& index) const { return block_map_.count(index) > 0; }
+  void removeBlock(const BlockIndex& index) { block_map_.erase(index); }
   void removeAllBlocks() { block_map_.clear(); }
   void getAllAllocatedBlocks(BlockIndexList* blocks) const {
     blocks->clear();

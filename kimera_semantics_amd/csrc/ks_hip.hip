@@ -71,6 +71,7 @@ using namespace ksd;
 #include "ks_k_render.h"
 #include "ks_k_align.h"
 #include "ks_k_objects.h"
+#include "ks_k_remove.h"
 
 using namespace ksk;
 
@@ -471,7 +472,8 @@ struct ks_ctx {
   uint32_t cap_xl_chunks = 1u << 17;   // 8 M updates in such runs per frame (more: the serial kernel takes the rest)
   // ks_mesh_update (ks_k_mesh.h).  The mesh lives in one of two arenas as per-block segments back to back; a call writes the
   // other arena (re-meshed blocks from the kernels, kept ones copied) and swaps.  The host keeps the directory and the
-  // sorted block list (tiles only ever join a map, so the list is extended by the tiles that are new since the last call).
+  // sorted block list: between two removals tiles only join a map, so the list is extended by the tiles that are new since the
+  // last call; a removal (remove_tiles) brings the list up to date itself, takes its blocks out and restarts the count.
   MeshArena mesh_arena[2] = {};            // views of the four owners below
   DevBuf<float> mesh_xyz[2], mesh_nrm[2];
   DevBuf<uint32_t> mesh_rgba[2];
@@ -486,7 +488,8 @@ struct ks_ctx {
   std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
   DevBuf<uint8_t> d_mesh_buf[10];          // grow-only scratch of the passes (mesh_scratch)
   // ks_esdf_update / ks_esdf_refresh (ks_k_esdf.h).  The store holds 512 records per tile slot: the ESDF of the map as it
-  // was at the last update or refresh; everything grows only.
+  // was at the last update or refresh; the buffers grow only.  A removal moves the records with their tiles and lowers
+  // esdf_tiles to the new tile count (remove_tiles).
   DevBuf<EsdfRecord> esdf_store;           // [esdf_tiles][512]
   DevBuf<uint64_t> esdf_keys[2];           // the two key buffers of the passes: [sign][box voxel] each
   DevBuf<uint32_t> esdf_slots;             // dense slot grid of the box
@@ -512,7 +515,7 @@ struct ks_ctx {
   DevBuf<AlignState> align_state;
   DevBuf<float> align_xyz;
   // ks_objects_update (ks_k_objects.h).  The id store holds 512 words per tile slot: the objects of the map as it was at the last
-  // update; everything grows only.
+  // update; the buffers grow only.  A removal moves the ids with their tiles and lowers obj_tiles to the new tile count.
   DevBuf<uint32_t> obj_ids;                // [obj_tiles][512] (during an update: the provisional numbers of the roots)
   DevBuf<uint32_t> obj_parent;             // the union-find forest of an update, then the voxels' provisional numbers
   DevBuf<uint8_t> obj_cls;                 // the class byte of every voxel
@@ -528,6 +531,15 @@ struct ks_ctx {
   bool obj_valid = false;                  // an update has run since the map was last cleared
   uint32_t obj_tiles = 0;                  // tiles that were resident at that update
   size_t obj_count = 0;                    // records stored
+  // ks_remove_blocks / ks_remove_distant_blocks (ks_k_remove.h).  What the stored products still have to hear of a removal:
+  std::vector<int32_t> removed_blocks;     // the blocks the LAST removal call took out, ascending (ks_removed_blocks)
+  std::vector<uint64_t> mesh_removed;      // block words removed since the last ks_mesh_update, ascending: it reports them as
+                                           // changed and re-meshes the resident blocks whose border cubes read them
+  std::vector<uint64_t> esdf_removed;      // tile positions (pack_coord3) removed since the stored ESDF was last brought up to date:
+                                           // stale positions without a tile for ks_esdf_refresh
+  DevBuf<uint8_t> rm_mark;                 // one byte per slot: the tile leaves
+  DevBuf<uint64_t> rm_keys;                // the tile keys of the listed blocks
+  DevBuf<uint2> rm_moves;                  // {source slot, destination slot} per moved tile
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -3003,6 +3015,15 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
   const bool full = !m->only_stale || !c->mesh_valid || m->min_weight != c->mesh_min_weight;
   c->mesh_valid = false;   // (a failure below leaves flags cleared that nothing has meshed: the next call starts over)
   if (!full && (rc = snap.blocks(c, sh, 0, kStaleMesh, &stale))) return rc;
+  // a block that left the map since the last update carries no flag: it counts as written, so that the resident blocks whose
+  // border cubes read it are re-meshed (it is no block of the map itself: mesh_plan keeps the blocks of the list only)
+  const std::vector<uint64_t> removed = std::move(c->mesh_removed);
+  c->mesh_removed.clear();
+  if (!full && !removed.empty()) {
+    std::vector<uint64_t> both;
+    std::set_union(stale.begin(), stale.end(), removed.begin(), removed.end(), std::back_inserter(both));
+    stale.swap(both);
+  }
   MeshPlan P = mesh_plan(c->mesh_blocks, c->mesh_dir, fresh, stale, full);
   c->mesh_blocks.swap(P.B);
   c->mesh_tiles_seen = nt;
@@ -3011,7 +3032,14 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
   const size_t nb = B.size(), nr = P.R.size();
   std::vector<ks_mesh_block> dir(nb);
   for (size_t i = 0; i < nb; ++i) unpack_coord3(B[i], dir[i].block[0], dir[i].block[1], dir[i].block[2]);
-  words_to_triples(P.R, &c->mesh_changed);
+  std::vector<int32_t> r_triples;   // the blocks to mesh, as the kernels take them
+  words_to_triples(P.R, &r_triples);
+  {
+    // what this update replaces: the segments of the re-meshed blocks, and those of the blocks that left the map
+    std::vector<uint64_t> changed;
+    std::set_union(P.R.begin(), P.R.end(), removed.begin(), removed.end(), std::back_inserter(changed));
+    words_to_triples(changed, &c->mesh_changed);
+  }
   unsigned long long degenerate = 0;
   uint32_t total = 0;
   const int from = c->mesh_cur, to = c->mesh_cur ^ 1;
@@ -3041,7 +3069,7 @@ int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
     HIPCHK(c, hipMemsetAsync(W.degenerate, 0, 8, st));
     HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[5], dir_in.data(), nb * 8, hipMemcpyHostToDevice, st));
     if (nr) {
-      HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[0], c->mesh_changed.data(), nr * 12, hipMemcpyHostToDevice, st));
+      HIPCHK(c, hipMemcpyAsync(c->d_mesh_buf[0], r_triples.data(), nr * 12, hipMemcpyHostToDevice, st));
       HIPCHK(c, hipMemsetAsync(W.cube_cnt, 0, nr * nvb, st));
       hipLaunchKernelGGL(k_mesh_tiles<false>, dim3((uint32_t)(nr * tiles_per_block)), dim3(512), 0, st, c->table, c->pool, W, MeshArena{});
       hipLaunchKernelGGL(k_mesh_scan, dim3((uint32_t)nr), dim3(1024), 0, st, W);
@@ -3281,6 +3309,7 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
   HIPCHK(c, hipGetLastError());
   c->esdf_valid = true;
   c->esdf_tiles = nt;
+  c->esdf_removed.clear();
   c->esdf_cfg = *e;
   for (int k = 0; k < 3; ++k) c->esdf_totals[k] = counts[k];
   c->esdf_changed.clear();
@@ -3329,8 +3358,11 @@ static std::vector<uint64_t> esdf_keep_near(const std::vector<uint64_t>& in, con
 //   Y = A dilated by g along z, X = Y dilated by g along y — less the positions whose brick can hold no real key: a brick of X
 //   has one only with a resident tile within g along x, a brick of Y only with a kept position of X within g along y.  A dropped
 //   brick would hold kEsdfNone throughout, which is what a miss reads as.
-static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& stale, int g, bool use_region,
-                               const int64_t region_lo[3], const int64_t region_hi[3], EsdfLists* L) {
+// removed: the positions of the tiles that left the map since the store was last current (ascending) — stale positions that hold
+//   no tile: their sites are gone, so they enter S for the reach (and a position that holds a tile again is in S anyway); n_stale
+//   counts resident tiles only.
+static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vector<uint8_t>& stale, const std::vector<uint64_t>& removed, int g,
+                               bool use_region, const int64_t region_lo[3], const int64_t region_hi[3], EsdfLists* L) {
   const size_t nt = keys.size();
   std::vector<std::pair<uint64_t, uint32_t>> resident(nt);
   std::vector<uint64_t> S;
@@ -3342,8 +3374,9 @@ static void esdf_refresh_lists(const std::vector<uint64_t>& keys, const std::vec
     if (stale[s]) S.push_back(p);
   }
   std::sort(resident.begin(), resident.end());
-  std::sort(S.begin(), S.end());
   L->n_stale = S.size();
+  S.insert(S.end(), removed.begin(), removed.end());
+  sort_unique(S);
   const std::vector<uint64_t> reach = esdf_dilate(esdf_dilate(esdf_dilate(S, 0, g), 1, g), 2, g);
   std::vector<uint64_t> all(nt);
   for (size_t i = 0; i < nt; ++i) {
@@ -3384,7 +3417,8 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     region_hi[a] = ((int64_t)e.region_max[a] + 1) * tpb - 1;
   }
   EsdfLists L;
-  esdf_refresh_lists(snap.keys, snap.flags, g, e.use_region != 0, region_lo, region_hi, &L);
+  const bool tiles_left = !c->esdf_removed.empty();   // a removal since the store was last current
+  esdf_refresh_lists(snap.keys, snap.flags, c->esdf_removed, g, e.use_region != 0, region_lo, region_hi, &L);
   const size_t nx = L.X.size(), ny = L.Y.size(), nz = L.Z.size();
   const uint64_t workspace = (uint64_t)(nx + ny) * kEsdfBrickKeys * 8 + (uint64_t)(nx + ny + nz) * 8 + (uint64_t)nz * 4;
   if (stats) {
@@ -3394,9 +3428,9 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     stats->voxels_observed = c->esdf_totals[0];
     stats->voxels_fixed = c->esdf_totals[1];
     stats->voxels_clamped = c->esdf_totals[2];
-    stats->workspace_bytes = L.n_stale ? workspace : 0;
+    stats->workspace_bytes = (L.n_stale || tiles_left) ? workspace : 0;
   }
-  if (L.n_stale == 0) {   // nothing to do: the totals of the store as it is
+  if (L.n_stale == 0 && !tiles_left) {   // nothing to do: the totals of the store as it is
     c->esdf_changed.clear();
     return KS_OK;
   }
@@ -3436,7 +3470,6 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     if (ny) HIPCHK(c, hipMemcpyAsync(d_y, L.Y.data(), ny * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_z, L.Z.data(), nz * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(c->esdf_zslots, L.z_slots.data(), nz * 4, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
     EsdfRefresh E{R, c->cfg.voxel_size, e.min_weight, e.min_distance_m, e.max_distance_m};
     if (nx)
       hipLaunchKernelGGL(k_esdf_brick<0>, dim3((uint32_t)nx), dim3(256), 0, st, E, c->table, c->pool, nt, (const uint64_t*)d_x,
@@ -3449,16 +3482,22 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     hipLaunchKernelGGL(k_esdf_brick<2>, dim3((uint32_t)nz), dim3(256), 0, st, E, c->table, c->pool, nt, (const uint64_t*)d_z,
                        (const uint64_t*)d_y, (uint32_t)ny, (const uint64_t*)c->esdf_bricks[1].get(), (uint64_t*)nullptr,
                        (const uint32_t*)c->esdf_zslots.get(), c->esdf_store.get());
+  }
+  if (nt) {   // (after a removal also with nothing to recompute: the records of the tiles that left no longer count)
     const size_t nrec = (size_t)nt * kTileVoxels;
+    HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
     hipLaunchKernelGGL(k_esdf_count, dim3((uint32_t)((nrec + 1023) / 1024)), dim3(256), 0, st, (const EsdfRecord*)c->esdf_store.get(), nrec,
                        e.max_distance_m, c->esdf_counters.get());
     HIPCHK(c, hipMemcpyAsync(counts, c->esdf_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleEsdf);
+  } else {
+    counts[0] = counts[1] = counts[2] = 0;   // (every tile has left)
   }
-  hipLaunchKernelGGL(k_stale_clear, dim3((nt + 255) / 256), dim3(256), 0, st, c->pool.mesh_stale(), nt, kStaleEsdf);
   HIPCHK(c, hipStreamSynchronize(st));
   HIPCHK(c, hipGetLastError());
   c->esdf_valid = true;
   c->esdf_tiles = nt;
+  c->esdf_removed.clear();
   for (int k = 0; k < 3; ++k) c->esdf_totals[k] = counts[k];
   // 4) the blocks of the recomputed tiles
   words_to_triples(blocks_of_tiles(L.Z, c->vps_shift), &c->esdf_changed);
@@ -4588,6 +4627,8 @@ static void mesh_reset(ks_ctx* c) {
   c->esdf_valid = false;   // the stored ESDF goes with the map
   c->esdf_tiles = 0;
   c->esdf_changed.clear();
+  c->esdf_removed.clear();
+  c->mesh_removed.clear();
   c->obj_valid = false;    // ... and the stored objects
   c->obj_tiles = 0;
   c->obj_count = 0;
@@ -4642,6 +4683,177 @@ static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
 int ks_clear(ks_ctx* c) {
   if (!c) return KS_ERR_INVALID_ARG;
   return clear_impl(c, false);
+}
+
+// ---- removal of blocks from the resident map (ks_k_remove.h) -------------------------------------------------
+// What both entry points do first: refuse a context that holds no voxel data or has failed, complete the frames in flight —
+// their statistics stay owed (c->owed is not touched: the trap of clear_impl) and the integrator's own state stays as they left
+// it — and clear the byte plane the selection writes.
+static int remove_begin(ks_ctx* c, const char* who, ks_remove_stats* stats) {
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (int rc = holds_voxels(c, who)) return rc;
+  if (c->fatal) {
+    c->err = std::string(who) + ": context is in a failed state (earlier pool/index error)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (int rc = quiesce(c)) return rc;
+  const size_t nt = c->tiles_initialised;
+  if (int rc = c->rm_mark.reserve(c, nt, nt + nt / 2 + 64)) return rc;
+  if (nt) HIPCHK(c, hipMemsetAsync(c->rm_mark, 0, nt, c->stream));
+  return KS_OK;
+}
+
+// The tiles marked in c->rm_mark leave the map: the survivors above the new tile count move into the holes below it, the
+// directory is rebuilt over the slots that remain, and the bookkeeping of the stored products follows the slots.
+static int remove_tiles(ks_ctx* c, ks_remove_stats* stats) {
+  hipStream_t st = c->stream;
+  TileSnapshot snap(c);
+  const uint32_t nt = snap.nt;
+  const int sh = c->vps_shift;
+  int rc;
+  c->removed_blocks.clear();
+  std::vector<uint8_t> mark(nt);
+  if (nt) HIPCHK(c, hipMemcpyAsync(mark.data(), c->rm_mark, nt, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  uint32_t n_removed = 0;
+  for (uint32_t s = 0; s < nt; ++s) n_removed += mark[s] != 0;
+  const uint32_t nt_new = nt - n_removed;
+  if (stats) {
+    stats->tiles_resident = nt_new;
+    stats->pool_capacity_tiles = c->cfg.max_tiles;
+  }
+  if (n_removed == 0) return KS_OK;
+  if ((rc = snap.fetch_keys(c))) return rc;
+  // 1) what leaves: tile positions and blocks, ascending
+  std::vector<uint64_t> gone_tiles;
+  gone_tiles.reserve(n_removed);
+  for (uint32_t s = 0; s < nt; ++s) {
+    if (!mark[s]) continue;
+    int t[3];
+    snap.tile(s, t);
+    gone_tiles.push_back(pack_coord3(t[0], t[1], t[2]));
+  }
+  std::sort(gone_tiles.begin(), gone_tiles.end());
+  const std::vector<uint64_t> gone_blocks = blocks_of_tiles(gone_tiles, sh);
+  // 2) every survivor at a slot >= nt_new moves into a hole < nt_new: there are as many of the one as of the other, and
+  //    sources and destinations are disjoint
+  std::vector<uint2> moves;
+  for (uint32_t s = nt_new, hole = 0; s < nt; ++s) {
+    if (mark[s]) continue;
+    while (!mark[hole]) ++hole;
+    moves.push_back(make_uint2(s, hole++));
+  }
+  if ((rc = c->rm_moves.reserve(c, moves.size(), moves.size() + moves.size() / 2 + 64))) return rc;
+  // the blocks of the tiles that joined since the last mesh update enter the mesher's list now: their slots are renumbered below
+  std::vector<uint64_t> fresh;
+  if ((rc = snap.blocks(c, sh, c->mesh_tiles_seen, 0, &fresh))) return rc;
+  // 3) move, rebuild the directory over [0, nt_new) (the sequence of grow_pool; table and pool stay where they are, so captured
+  //    graphs stay valid), clear the flags of the vacated slots, set the persistent tile count
+  const bool esdf = c->esdf_valid && c->esdf_tiles, obj = c->obj_valid && c->obj_tiles;
+  if (!moves.empty()) {
+    HIPCHK(c, hipMemcpyAsync(c->rm_moves, moves.data(), moves.size() * sizeof(uint2), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_remove_move, dim3((uint32_t)moves.size()), dim3(512), 0, st, c->pool, c->table.slot_keys, (const uint2*)c->rm_moves.get(),
+                       esdf ? c->esdf_store.get() : (EsdfRecord*)nullptr, c->esdf_tiles, obj ? c->obj_ids.get() : (uint32_t*)nullptr, c->obj_tiles);
+  }
+  HIPCHK(c, hipMemsetAsync(c->table.ent, 0xff, ((size_t)c->table.mask + 1) * sizeof(TileEntry), st));
+  if (nt_new) hipLaunchKernelGGL(k_rehash_tiles, dim3((nt_new + 255) / 256), dim3(256), 0, st, c->table, (const uint64_t*)c->table.slot_keys, nt_new);
+  HIPCHK(c, hipMemsetAsync(c->pool.updated + nt_new, 0, n_removed, st));
+  HIPCHK(c, hipMemsetAsync(c->pool.dirty + nt_new, 0, n_removed, st));
+  HIPCHK(c, hipMemsetAsync(c->pool.mesh_stale() + nt_new, 0, n_removed, st));
+  HIPCHK(c, hipMemcpyAsync(c->table.n_tiles, &nt_new, sizeof(uint32_t), hipMemcpyHostToDevice, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->tiles_initialised = nt_new;
+  for (auto& S : c->slot)
+    if (S.h_snap) S.h_snap->n_tiles = nt_new;   // (the pool-growth trigger reads the snapshots' tile counts)
+  // 4) the stored products.  Mesh: the block list loses the blocks; the next update reports them and re-meshes what read them.
+  {
+    std::vector<uint64_t> all, kept;
+    std::set_union(c->mesh_blocks.begin(), c->mesh_blocks.end(), fresh.begin(), fresh.end(), std::back_inserter(all));
+    std::set_difference(all.begin(), all.end(), gone_blocks.begin(), gone_blocks.end(), std::back_inserter(kept));
+    c->mesh_blocks.swap(kept);
+    c->mesh_tiles_seen = nt_new;
+    if (c->mesh_valid) {
+      std::vector<uint64_t> both;
+      std::set_union(c->mesh_removed.begin(), c->mesh_removed.end(), gone_blocks.begin(), gone_blocks.end(), std::back_inserter(both));
+      c->mesh_removed.swap(both);
+    }
+  }
+  // ESDF: records have moved with their tiles; the positions that lost their tile are stale positions of the next refresh
+  if (c->esdf_valid) {
+    std::vector<uint64_t> both;
+    std::set_union(c->esdf_removed.begin(), c->esdf_removed.end(), gone_tiles.begin(), gone_tiles.end(), std::back_inserter(both));
+    c->esdf_removed.swap(both);
+    c->esdf_tiles = std::min(c->esdf_tiles, nt_new);
+  }
+  // objects: the records are the snapshot of the last update; the ids have moved with their tiles
+  if (c->obj_valid) c->obj_tiles = std::min(c->obj_tiles, nt_new);
+  words_to_triples(gone_blocks, &c->removed_blocks);
+  if (stats) {
+    stats->blocks_removed = gone_blocks.size();
+    stats->tiles_removed = n_removed;
+    stats->tiles_moved = moves.size();
+  }
+  return KS_OK;
+}
+
+int ks_remove_blocks(ks_ctx* c, const int32_t* idx, size_t n, ks_remove_stats* stats) {
+  if (!c || (n && !idx)) return KS_ERR_INVALID_ARG;
+  const int tpb = c->cfg.voxels_per_side / 8;
+  const int lim = kTileBias / tpb;
+  std::vector<uint64_t> keys;
+  keys.reserve(n * tpb * tpb * tpb);
+  for (size_t b = 0; b < n; ++b) {
+    const int bx = idx[3 * b], by = idx[3 * b + 1], bz = idx[3 * b + 2];
+    if (bx < -lim || bx >= lim || by < -lim || by >= lim || bz < -lim || bz >= lim) {
+      c->err = "ks_remove_blocks: block index outside the packed tile-key range";
+      return KS_ERR_INDEX_RANGE;
+    }
+    for (int z = 0; z < tpb; ++z)
+      for (int y = 0; y < tpb; ++y)
+        for (int x = 0; x < tpb; ++x) keys.push_back(pack_tile(bx * tpb + x, by * tpb + y, bz * tpb + z));
+  }
+  if (keys.size() >= (1ull << 31)) {
+    c->err = "ks_remove_blocks: too many blocks for one call";
+    return KS_ERR_INVALID_ARG;
+  }
+  int rc;
+  if ((rc = remove_begin(c, "ks_remove_blocks", stats))) return rc;
+  const uint32_t nt = c->tiles_initialised;
+  if (!keys.empty() && nt) {
+    if ((rc = c->rm_keys.reserve(c, keys.size(), keys.size() + keys.size() / 2))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->rm_keys, keys.data(), keys.size() * sizeof(uint64_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_remove_select_list, dim3((uint32_t)((keys.size() + 255) / 256)), dim3(256), 0, c->stream, c->table,
+                       (const uint64_t*)c->rm_keys.get(), (uint32_t)keys.size(), nt, c->rm_mark.get());
+  }
+  return remove_tiles(c, stats);
+}
+
+int ks_remove_distant_blocks(ks_ctx* c, const float center[3], float max_distance_m, ks_remove_stats* stats) {
+  if (!c || !center) return KS_ERR_INVALID_ARG;
+  if (!std::isfinite(center[0]) || !std::isfinite(center[1]) || !std::isfinite(center[2]) || !(max_distance_m >= 0.0f) ||
+      !std::isfinite(max_distance_m)) {
+    c->err = "ks_remove_distant_blocks: the centre must be finite and max_distance_m finite and not negative";
+    return KS_ERR_INVALID_ARG;
+  }
+  int rc;
+  if ((rc = remove_begin(c, "ks_remove_distant_blocks", stats))) return rc;
+  const uint32_t nt = c->tiles_initialised;
+  if (nt) {
+    RemoveRule R{};
+    R.block_size = c->cfg.voxel_size * (float)c->cfg.voxels_per_side;
+    R.cx = center[0], R.cy = center[1], R.cz = center[2];
+    R.max_distance = max_distance_m;
+    R.vps_shift = c->vps_shift;
+    hipLaunchKernelGGL(k_remove_select_distance, dim3((nt + 255) / 256), dim3(256), 0, c->stream, (const uint64_t*)c->table.slot_keys, nt, R,
+                       c->rm_mark.get());
+  }
+  return remove_tiles(c, stats);
+}
+
+int ks_removed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
+  return c ? copy_block_list(c, "ks_removed_blocks", c->removed_blocks, out_xyz, cap, n) : KS_ERR_INVALID_ARG;
 }
 
 int ks_clear_voxels(ks_ctx* c) {

@@ -87,6 +87,17 @@ int main(int argc, char** argv) {
       hip->setSyncPolicy(kimera::HipSemanticTsdfIntegrator::SyncPolicy::kOnDemand);
   };
   on_demand();
+  // KS_DEMO_PRUNE=<metres>: vxb::TsdfServer with max_block_distance_from_body, as integration/server.patch wires it — the server
+  // hands its radius to the integrator once, and every integrated cloud ends with removeDistantBlocks around the sensor: the
+  // far blocks leave the device map and the host TSDF layer.  KS_DEMO_PRUNE_DROP_SEMANTIC=1: and the host semantic layer
+  auto pruning = [&]() {
+    const char* prune = std::getenv("KS_DEMO_PRUNE");
+    if (!prune) return;
+    const char* drop = std::getenv("KS_DEMO_PRUNE_DROP_SEMANTIC");
+    if (auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get()))
+      hip->setMaxBlockDistanceFromBody((float)std::atof(prune), /*keep_semantic_layer=*/!(drop && std::atoi(drop) != 0));
+  };
+  pruning();
   if (auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get())) {
     int32_t shape[4] = {0, 0, 0, 0};
     ks_pipeline_shape(hip->context(), shape);
@@ -125,6 +136,7 @@ int main(int argc, char** argv) {
       integrator.reset();
       integrator = make();
       on_demand();
+      pruning();
     }
     if (const char* ca = std::getenv("KS_DEMO_CLEAR_AFTER")) {
       if ((int)f == std::atoi(ca)) {
@@ -156,6 +168,14 @@ int main(int argc, char** argv) {
     integrator->integratePointCloud(vxb::Transformation(T[0], T[1], T[2], T[3], vxb::Point(T[4], T[5], T[6])), pts, cols, false);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     integrate_ms += ms;
+    if (std::getenv("KS_DEMO_PRUNE")) {
+      auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+      if (!hip) return 7;
+      const ks_remove_stats& rs = hip->lastRemoveStats();
+      std::printf("adapter_demo: pruned after frame %u: %llu blocks removed, %llu tiles resident of a pool of %llu, host layers %zu tsdf / %zu semantic blocks\n",
+                  f, (unsigned long long)rs.blocks_removed, (unsigned long long)rs.tiles_resident, (unsigned long long)rs.pool_capacity_tiles,
+                  tsdf_layer.getNumberOfAllocatedBlocks(), semantic_layer.getNumberOfAllocatedBlocks());
+    }
     if (std::getenv("KS_DEMO_TRACE")) std::fprintf(stderr, "frame %u done (%.3f ms, %zu blocks)\n", f, ms, tsdf_layer.getNumberOfAllocatedBlocks());
     if (3 * f >= 2 * n_frames) {  // steady state: the last third (staging buffers and most blocks exist)
       tail_ms += ms;

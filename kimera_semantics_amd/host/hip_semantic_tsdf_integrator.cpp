@@ -188,6 +188,7 @@ void HipSemanticTsdfIntegrator::integratePointCloud(const vxb::Transformation& T
     check(ks_flush(ctx_, &last_stats_), "ks_flush");
     syncLayers();
   }
+  pruneAfterFrame(T_G_C);
 }
 
 void HipSemanticTsdfIntegrator::integratePointCloud(const vxb::Transformation& T_G_C,
@@ -212,11 +213,63 @@ void HipSemanticTsdfIntegrator::integratePointCloud(const vxb::Transformation& T
     check(ks_flush(ctx_, &last_stats_), "ks_flush");
     syncLayers();
   }
+  pruneAfterFrame(T_G_C);
 }
 
 void HipSemanticTsdfIntegrator::clearDeviceMap(bool keep_integrator_state) {
   if (keep_integrator_state) check(ks_clear_voxels(ctx_), "ks_clear_voxels");
   else check(ks_clear(ctx_), "ks_clear");
+}
+
+size_t HipSemanticTsdfIntegrator::removeDistantBlocks(const vxb::Point& center, vxb::FloatingPoint max_distance, bool keep_semantic_layer) {
+  if (keep_semantic_layer) {
+    // the semantic blocks survive on the host (the reference prunes the TSDF layer alone): they must hold what the device holds
+    // (the sync completes the frames in flight; their statistics stay owed)
+    syncLayers();
+  }
+  const float c[3] = {center.x(), center.y(), center.z()};
+  check(ks_remove_distant_blocks(ctx_, c, max_distance, &last_remove_stats_), "ks_remove_distant_blocks");
+  size_t n = 0;
+  check(ks_removed_blocks(ctx_, nullptr, 0, &n), "ks_removed_blocks");
+  if (n == 0) return 0;
+  idx_buf_.resize(3 * n);
+  check(ks_removed_blocks(ctx_, idx_buf_.data(), n, &n), "ks_removed_blocks");
+  // the same blocks leave the host TSDF layer; the semantic halves that survive go back up
+  const size_t vps = layer_->voxels_per_side();
+  const size_t nv = vps * vps * vps;
+  std::vector<int32_t> back;
+  for (size_t b = 0; b < n; ++b) {
+    const vxb::BlockIndex idx(idx_buf_[3 * b], idx_buf_[3 * b + 1], idx_buf_[3 * b + 2]);
+    layer_->removeBlock(idx);
+    if (!keep_semantic_layer) semantic_layer_ptr_->removeBlock(idx);
+    else if (semantic_layer_ptr_->hasBlock(idx)) back.insert(back.end(), {idx.x(), idx.y(), idx.z()});
+  }
+  if (!back.empty()) {
+    const size_t m = back.size() / 3;
+    uint8_t* sem_stage = sem_buf_.reserve(m * nv * 92);
+    std::memset(sem_stage, 0, m * nv * 92);
+    for (size_t b = 0; b < m; ++b) {
+      const auto sb = semantic_layer_ptr_->getBlockPtrByIndex(vxb::BlockIndex(back[3 * b], back[3 * b + 1], back[3 * b + 2]));
+      for (size_t i = 0; i < nv; ++i) {
+        const SemanticVoxel& sv = sb->getVoxelByLinearIndex(i);
+        uint8_t* r = sem_stage + (b * nv + i) * 92;
+        r[0] = sv.semantic_label;
+        for (size_t l = 0; l < kTotalNumberOfLabels; ++l) {
+          const float p = sv.semantic_priors[l];
+          std::memcpy(r + 4 + 4 * l, &p, 4);
+        }
+        r[88] = sv.color.r;
+        r[89] = sv.color.g;
+        r[90] = sv.color.b;
+        r[91] = sv.color.a;
+      }
+    }
+    check(ks_upload_blocks(ctx_, back.data(), m, nullptr, sem_stage), "ks_upload_blocks");
+    // what was just uploaded is not "updated by integration" (the sync above has consumed every other mark)
+    size_t u = 0;
+    check(ks_get_updated_block_indices(ctx_, nullptr, 0, &u, 1), "ks_get_updated_block_indices");
+  }
+  return n;
 }
 
 bool HipSemanticTsdfIntegrator::updateMesh(bool only_mesh_updated_blocks, std::vector<MeshBlock>* changed) {

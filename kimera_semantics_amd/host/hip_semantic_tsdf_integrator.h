@@ -9,6 +9,7 @@
 #pragma once
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <memory>
 #include <mutex>
 #include <string>
@@ -94,6 +95,24 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// (ks_clear_voxels) — vxb::TsdfServer::clear() removes the TSDF blocks and leaves the integrator and the semantic layer
   /// alone: integration/server.patch syncs, lets the base class clear, empties the GPU map this way and uploads what survived.
   void clearDeviceMap(bool keep_integrator_state = false);
+  /// vxb::Layer::removeDistantBlocks for a map that lives on the GPU (ks_remove_distant_blocks; the contract is DESIGN.md,
+  /// section 16): every block whose ORIGIN is further than max_distance from center leaves the device map, and the same blocks
+  /// (ks_removed_blocks) leave the host TSDF layer, so host and device keep agreeing when a pruned block is touched again.
+  /// keep_semantic_layer = true is what the reference does: vxb::TsdfServer prunes the TSDF layer it knows and the semantic
+  /// blocks survive — the host layers are brought up to date first, and the surviving semantic halves go back up afterwards
+  /// (ks_upload_blocks with no TSDF half: the blocks are resident again, with default TSDF voxels — the device holds a block's two
+  /// halves together, so this mode frees no device memory).  false removes the host semantic blocks too: the map really shrinks.
+  /// Returns the number of blocks removed.  integration/server.patch calls it where vxb::TsdfServer prunes.
+  size_t removeDistantBlocks(const vxb::Point& center, vxb::FloatingPoint max_distance, bool keep_semantic_layer = true);
+  const ks_remove_stats& lastRemoveStats() const { return last_remove_stats_; }
+  /// A server that prunes (vxb::TsdfServer, parameter max_block_distance_from_body) hands its radius over once: from then on
+  /// every integratePointCloud ends with removeDistantBlocks(T_G_C.getPosition(), max_distance, keep_semantic_layer) — right
+  /// before the base class prunes its host TSDF layer, which then finds nothing left to do.  The largest FloatingPoint (the
+  /// server's default) switches it off.  keep_semantic_layer = true brings the host layers up to date after every frame.
+  void setMaxBlockDistanceFromBody(vxb::FloatingPoint max_distance, bool keep_semantic_layer = true) {
+    prune_distance_ = max_distance;
+    prune_keep_semantic_ = keep_semantic_layer;
+  }
 
   /// One block of the semantic mesh: the fields of vxb::Mesh (three vertices per triangle, no indices) plus the arg-max
   /// label of the voxel that contains each vertex, in types this adapter already uses.
@@ -209,6 +228,12 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};
   ks_objects_stats last_objects_stats_{};
+  ks_remove_stats last_remove_stats_{};
+  vxb::FloatingPoint prune_distance_ = std::numeric_limits<vxb::FloatingPoint>::max();
+  bool prune_keep_semantic_ = true;
+  void pruneAfterFrame(const vxb::Transformation& T_G_C) {
+    if (prune_distance_ < std::numeric_limits<vxb::FloatingPoint>::max()) removeDistantBlocks(T_G_C.getPosition(), prune_distance_, prune_keep_semantic_);
+  }
   void downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out);
   vxb::Layer<SemanticVoxel>* semantic_layer_ptr_;
   // page-locked staging for layer transfers (ks_host_alloc); grows on demand

@@ -9,9 +9,12 @@ batch ESDF it ends with is computed on the device (ks_esdf_update) with --esdf, 
 (ks_render_view: depth, labels, colours, normals) every N frames; --align refines every frame's pose against the map on the
 device before the frame is integrated (ks_align_points: what `enable_icp` selects in the reference's launch files, without a layer
 sync) and prints the correction; --objects clusters the surface of every label into object instances on the device at the end
-of the replay (ks_objects_update) and writes their records, centroids in metres and label names; map saving stays on the host side of the drop-in boundary (out of scope).
+of the replay (ks_objects_update) and writes their records, centroids in metres and label names; --max-block-distance M prunes the
+map around the sensor position after every frame (ks_remove_distant_blocks: what voxblox::TsdfServer does with
+max_block_distance_from_body; completes the frames in flight), so that a long replay runs in a bounded pool; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz]
+      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
+      [--max-block-distance 3.0]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -62,6 +65,8 @@ def main():
     ap.add_argument("--objects", metavar="OUT.npz", help="cluster the surface voxels of every label into object instances at the end of the replay and "
                     "write them (records (n,) of 72 bytes ascending by first_voxel, centroids_m (n, 3), label_names (n,), voxel_size)")
     ap.add_argument("--objects-min-voxels", type=int, default=8, metavar="N")
+    ap.add_argument("--max-block-distance", type=float, default=None, metavar="M", help="after every frame remove the blocks whose origin is further "
+                    "than M metres from the sensor position (ks_remove_distant_blocks; completes the frames in flight)")
     a = ap.parse_args()
     if a.render_every and not a.render_out:
         ap.error("--render-every needs --render-out")
@@ -96,10 +101,16 @@ def main():
     if a.render_every:
         os.makedirs(a.render_out, exist_ok=True)
 
+    prune_s, prunes = 0.0, []
+
     def acc(fr, T, st):
-        nonlocal upd, refresh_s, n_seen, esdf_s, render_s
+        nonlocal upd, refresh_s, n_seen, esdf_s, render_s, prune_s
         upd += st.n_voxel_updates
         n_seen += 1
+        if a.max_block_distance is not None:   # first: what the later ticks of this frame see is the pruned map
+            t1 = time.perf_counter()
+            prunes.append(integ.remove_distant(np.asarray(T, np.float32)[4:7], a.max_block_distance))
+            prune_s += time.perf_counter() - t1
         if a.esdf_every and n_seen % a.esdf_every == 0:
             t1 = time.perf_counter()
             if esdf_ticks:
@@ -146,6 +157,10 @@ def main():
     print(f"{out['integrated']} frames integrated ({out['skipped_no_tf']} skipped: no tf) in {dt:.3f} s: "
           f"{out['integrated'] / dt:.1f} frames/s incl. H2D of the images, {upd / dt / 1e6:.1f} M voxel updates/s, "
           f"{len(integ.block_indices())} blocks")
+    if prunes:
+        print(f"pruned after every frame beyond {a.max_block_distance} m in {prune_s * 1e3:.1f} ms of the above: {prune_s / len(prunes) * 1e3:.3f} ms each; "
+              f"{sum(p['blocks_removed'] for p in prunes)} blocks removed, {sum(p['tiles_moved'] for p in prunes)} tiles moved, at most "
+              f"{max(p['tiles_resident'] for p in prunes)} tiles resident afterwards, pool of {prunes[-1]['pool_capacity_tiles']} tiles")
     if refreshes:
         print(f"{len(refreshes)} mesh refreshes (only_stale, incl. the download) in {refresh_s * 1e3:.1f} ms of the above: "
               f"{refresh_s / len(refreshes) * 1e3:.2f} ms each; last: {refreshes[-1][0]} of {refreshes[-1][1]} blocks re-meshed, "
