@@ -564,6 +564,43 @@ typedef struct ks_remove_stats {
 int ks_remove_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, ks_remove_stats* stats /* may be NULL */);
 int ks_remove_distant_blocks(ks_ctx* ctx, const float center[3], float max_distance_m, ks_remove_stats* stats /* may be NULL */);
 int ks_removed_blocks(ks_ctx* ctx, int32_t* out_xyz, size_t cap, size_t* n); /* of the LAST removal call, ascending (x,y,z) */
+/* ---- fusing a submap into the resident map at a rigid pose (new on this side of the boundary: a loop closure or a ks_align_points
+ * result that corrects a submap's pose, a server that receives a layer on Voxblox's tsdf_map_in and calls
+ * mergeLayerAintoLayerB(layer, T, ...), any submap-based mapper) ----
+ * The contract is DESIGN.md §17; no parity with Voxblox's resampleLayer is claimed (Voxblox is not part of the reference tree).
+ * ks_fuse_map resamples the map of `src` under T_D_S (qw qx qy qz tx ty tz: source frame -> destination frame) into the grid of
+ * `dst` and folds the result into `dst` by the rule of ks_merge_tiles_device.  Both contexts live on the same device and have
+ * bit-equal voxel_size; voxels_per_side may differ.  For every destination voxel of a candidate tile: its centre
+ * c_k = ((float)v_k + 0.5f) * voxel_size goes through the inverse pose (formed on the host in f64, rounded to f32) into the source
+ * frame, the source is sampled there as the renderer samples it (trilinear over the eight corners; VALID iff every corner lies
+ * inside the packed range, in a resident source tile, has weight >= min_weight and a distance that is not NaN); a valid voxel's
+ * incoming record is {interpolated distance, interpolated weight, the colour, label (255 as 0) and 21 priors of the NEAREST corner},
+ * an invalid voxel is untouched.  A destination tile exists afterwards iff it existed before or holds a touched voxel.
+ * The result depends on the voxels of the two maps, T_D_S and min_weight alone — not on slot numbers, on the enumeration of
+ * candidate tiles or on the chunking by max_workspace_bytes.
+ * Both contexts complete their frames in flight first; the statistics of those frames stay owed, the integrators' own state stays.
+ * `src` is only read.  In `dst` every tile that holds a touched voxel is flagged for both host syncs and marked stale for the mesher
+ * and the ESDF: ks_mesh_update(only_stale = 1) and ks_esdf_refresh afterwards leave the bytes of a from-scratch call; object records
+ * stay the snapshot they were.
+ * cfg:   min_weight (1e-4), max_workspace_bytes (1 GiB): bounds the work space of exchange-format tiles; the candidate tiles are
+ *        processed in `chunks` of it.
+ * stats: tiles_source (resident tiles of src), tiles_candidate (destination tiles examined), tiles_touched (those that hold a
+ *        touched voxel), tiles_allocated (the touched tiles that are new in dst), voxels_fused, chunks, workspace_bytes.
+ * Errors: KS_ERR_INVALID_ARG (a NULL argument; dst == src; different devices; different voxel_size; a non-finite pose or a zero
+ * quaternion; min_weight not a finite positive number; a context in a failed state), KS_ERR_INDEX_RANGE (a candidate tile leaves the
+ * packed tile range: reported before anything is written), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact;
+ * max_workspace_bytes below what one tile needs: stats->workspace_bytes says what that is and dst is unchanged), KS_ERR_POOL_FULL,
+ * KS_ERR_HIP.  An empty src is no error: all counts are 0.  Multi-GPU: each context fuses the tiles it holds. */
+typedef struct ks_fuse_config {
+  float min_weight;
+  uint32_t pad;
+  uint64_t max_workspace_bytes;
+} ks_fuse_config; /* 16 bytes */
+typedef struct ks_fuse_stats {
+  uint64_t tiles_source, tiles_candidate, tiles_touched, tiles_allocated, voxels_fused, chunks, workspace_bytes;
+} ks_fuse_stats; /* 56 bytes */
+int ks_fuse_default_config(ks_fuse_config* cfg);
+int ks_fuse_map(ks_ctx* dst, ks_ctx* src, const float T_D_S[7], const ks_fuse_config* cfg, ks_fuse_stats* stats /* may be NULL */);
 /* Resets the tiles at the given slots to the empty state (a rank that has handed tiles to their owner keeps
  * them as empty deltas). */
 int ks_reset_tiles(ks_ctx* ctx, const uint32_t* slots, size_t n);

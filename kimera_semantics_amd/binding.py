@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "ks_align_default_config", "ks_align_points", "ks_align_points_device",
     "ks_objects_default_config", "ks_objects_update", "ks_objects_size", "ks_objects_download", "ks_objects_download_blocks", "ks_objects_query",
     "ks_remove_blocks", "ks_remove_distant_blocks", "ks_removed_blocks",
+    "ks_fuse_default_config", "ks_fuse_map",
 ]
 
 
@@ -148,6 +149,15 @@ class KsRemoveStats(C.Structure):
                 ("pool_capacity_tiles", C.c_uint64)]
 
 
+class KsFuseConfig(C.Structure):
+    _fields_ = [("min_weight", C.c_float), ("pad", C.c_uint32), ("max_workspace_bytes", C.c_uint64)]
+
+
+class KsFuseStats(C.Structure):
+    _fields_ = [("tiles_source", C.c_uint64), ("tiles_candidate", C.c_uint64), ("tiles_touched", C.c_uint64), ("tiles_allocated", C.c_uint64),
+                ("voxels_fused", C.c_uint64), ("chunks", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
 # ks_object: 72 bytes; centroid_k = (sum_k / n_voxels + 0.5) * voxel_size (object_centroids)
 OBJECT_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
                          ("sum", "<i8", (3,)), ("label", "<u4"), ("pad", "<u4")])
@@ -174,7 +184,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -265,6 +275,8 @@ def lib():
         L.ks_remove_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsRemoveStats)]
         L.ks_remove_distant_blocks.argtypes = [vp, vp, C.c_float, C.POINTER(KsRemoveStats)]
         L.ks_removed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_fuse_default_config.argtypes = [C.POINTER(KsFuseConfig)]
+        L.ks_fuse_map.argtypes = [vp, vp, vp, C.POINTER(KsFuseConfig), C.POINTER(KsFuseStats)]
         _lib = L
     return _lib
 
@@ -683,6 +695,27 @@ class HipIntegrator:
         if n.value:
             self._chk(lib().ks_removed_blocks(self._h, _ptr(out), n.value, C.byref(n)))
         return out
+
+    def fuse(self, src: "HipIntegrator", T_D_S, min_weight=None, max_workspace_bytes=None) -> dict:
+        """ks_fuse_map: resamples the map of `src` under T_D_S (qw qx qy qz tx ty tz: source frame -> this map's frame) into this
+        map's grid and folds it in by the merge rule.  `src` is only read.  Returns the stats — also when the call is refused for
+        its work space (KsError.stats).  The contract is DESIGN.md, section 17."""
+        cfg = KsFuseConfig()
+        self._chk(lib().ks_fuse_default_config(C.byref(cfg)))
+        if min_weight is not None:
+            cfg.min_weight = min_weight
+        if max_workspace_bytes is not None:
+            cfg.max_workspace_bytes = int(max_workspace_bytes)
+        T = np.ascontiguousarray(T_D_S, dtype=np.float32).reshape(7)
+        st = KsFuseStats()
+        rc = lib().ks_fuse_map(self._h, src._h, _ptr(T), C.byref(cfg), C.byref(st))
+        stats = {k: int(getattr(st, k)) for k, _ in KsFuseStats._fields_}
+        try:
+            self._chk(rc)
+        except KsError as e:
+            e.stats = stats
+            raise
+        return stats
 
     def reset_tiles(self, slots: np.ndarray):
         s = np.ascontiguousarray(slots, dtype=np.uint32)

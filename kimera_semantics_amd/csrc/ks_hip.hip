@@ -72,6 +72,7 @@ using namespace ksd;
 #include "ks_k_align.h"
 #include "ks_k_objects.h"
 #include "ks_k_remove.h"
+#include "ks_k_fuse.h"
 
 using namespace ksk;
 
@@ -540,6 +541,10 @@ struct ks_ctx {
   DevBuf<uint8_t> rm_mark;                 // one byte per slot: the tile leaves
   DevBuf<uint64_t> rm_keys;                // the tile keys of the listed blocks
   DevBuf<uint2> rm_moves;                  // {source slot, destination slot} per moved tile
+  // ks_fuse_map (ks_k_fuse.h), held by the DESTINATION context; grow-only
+  DevBuf<uint4> fuse_ws;                   // the work space: one exchange-format tile (64 KiB) per candidate tile of a chunk
+  DevBuf<uint64_t> fuse_keys;              // the chunk's candidate keys, then the keys of its touched tiles
+  DevBuf<uint32_t> fuse_u32;               // per candidate its count of touched voxels, then offs and idx of k_merge_tiles
   ks_profile prof{};
   ProfSet pset[kProfSets];
   bool fatal = false;
@@ -4854,6 +4859,203 @@ int ks_remove_distant_blocks(ks_ctx* c, const float center[3], float max_distanc
 
 int ks_removed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
   return c ? copy_block_list(c, "ks_removed_blocks", c->removed_blocks, out_xyz, cap, n) : KS_ERR_INVALID_ARG;
+}
+
+// ---- fusing a submap at a rigid pose (ks_k_fuse.h) ---------------------------------------------------------------
+int ks_fuse_default_config(ks_fuse_config* f) {
+  if (!f) return KS_ERR_INVALID_ARG;
+  f->min_weight = 1e-4f;
+  f->pad = 0;
+  f->max_workspace_bytes = 1ull << 30;
+  return KS_OK;
+}
+
+namespace {
+constexpr uint64_t kFuseTileBytes = (uint64_t)kTileVoxels * 128 + 16;   // the tile, its key, its count, its idx entry
+struct Pose64 {
+  double w, v[3], t[3];
+};
+void cross64(const double a[3], const double b[3], double out[3]) {
+  out[0] = a[1] * b[2] - a[2] * b[1];
+  out[1] = a[2] * b[0] - a[0] * b[2];
+  out[2] = a[0] * b[1] - a[1] * b[0];
+}
+// r = (p + (2 w) (v x p)) + 2 (v x (v x p)), in this form
+void rotate64(const Pose64& T, const double p[3], double r[3]) {
+  double uv[3], c2[3];
+  cross64(T.v, p, uv);
+  cross64(T.v, uv, c2);
+  for (int k = 0; k < 3; ++k) r[k] = (p[k] + (2.0 * T.w) * uv[k]) + 2.0 * c2[k];
+}
+// The destination tiles the source tiles can reach: a destination voxel is touched only if the lowest corner of its sample lies in
+// a resident source tile s, i.e. its point lies in the cube vs * [8 s + 0.5, 8 s + 8.5)^3; the cube's corners through T_D_S (f64)
+// bound the voxel's centre, and one voxel on every side covers what f32 rounds differently.  Ascending, unique.
+int fuse_candidates(ks_ctx* d, const std::vector<uint64_t>& src_keys, const Pose64& T_D_S, std::vector<uint64_t>* out) {
+  const double vs = (double)d->cfg.voxel_size;
+  out->clear();
+  out->reserve(src_keys.size() * 8);
+  for (uint64_t key : src_keys) {
+    int s[3];
+    unpack_tile(key, s[0], s[1], s[2]);
+    double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300};
+    for (int k = 0; k < 8; ++k) {
+      const double p[3] = {vs * (8.0 * s[0] + 0.5 + 8.0 * (k & 1)), vs * (8.0 * s[1] + 0.5 + 8.0 * ((k >> 1) & 1)), vs * (8.0 * s[2] + 0.5 + 8.0 * (k >> 2))};
+      double r[3];
+      rotate64(T_D_S, p, r);
+      for (int a = 0; a < 3; ++a) {
+        const double c = r[a] + T_D_S.t[a];
+        lo[a] = std::min(lo[a], c);
+        hi[a] = std::max(hi[a], c);
+      }
+    }
+    int t0[3], t1[3];
+    for (int a = 0; a < 3; ++a) {
+      const double v0 = std::floor(lo[a] / vs - 0.5) - 1.0, v1 = std::ceil(hi[a] / vs - 0.5) + 1.0;
+      const double a0 = std::floor(v0 / 8.0), a1 = std::floor(v1 / 8.0);
+      if (!(a0 >= -(double)kTileBias) || !(a1 < (double)kTileBias)) {
+        d->err = "ks_fuse_map: a candidate tile leaves the packed tile-key range";
+        return KS_ERR_INDEX_RANGE;
+      }
+      t0[a] = (int)a0;
+      t1[a] = (int)a1;
+    }
+    for (int x = t0[0]; x <= t1[0]; ++x)
+      for (int y = t0[1]; y <= t1[1]; ++y)
+        for (int z = t0[2]; z <= t1[2]; ++z) out->push_back(pack_tile(x, y, z));
+  }
+  sort_unique(*out);
+  return KS_OK;
+}
+}  // namespace
+
+int ks_fuse_map(ks_ctx* d, ks_ctx* s, const float T[7], const ks_fuse_config* f, ks_fuse_stats* stats) {
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!d || !s || !T || !f) return KS_ERR_INVALID_ARG;
+  auto refuse = [&](const char* why) {
+    d->err = std::string("ks_fuse_map: ") + why;
+    return KS_ERR_INVALID_ARG;
+  };
+  if (d == s) return refuse("dst and src are the same context (use a second context)");
+  if (d->cfg.device_id != s->cfg.device_id) return refuse("the two contexts live on different devices");
+  if (std::memcmp(&d->cfg.voxel_size, &s->cfg.voxel_size, sizeof(float)) != 0) return refuse("the two contexts differ in voxel_size");
+  for (int k = 0; k < 7; ++k)
+    if (!std::isfinite(T[k])) return refuse("the pose must be finite");
+  const double qn = std::sqrt((double)T[0] * T[0] + (double)T[1] * T[1] + (double)T[2] * T[2] + (double)T[3] * T[3]);
+  if (!(qn > 0.0)) return refuse("the quaternion is zero");
+  if (!std::isfinite(f->min_weight) || !(f->min_weight > 0.0f)) return refuse("min_weight must be a finite positive number");
+  int rc;
+  if ((rc = holds_voxels(d, "ks_fuse_map"))) return rc;
+  if (s->shard_export) {
+    d->err = "ks_fuse_map: src is a marcher context of ks_integrate_round_exact and holds no voxel data";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (d->fatal || s->fatal) return refuse("a context is in a failed state (earlier pool/index error)");
+  // the frames in flight of both contexts; their statistics stay owed (c->owed is not touched)
+  if ((rc = quiesce(d))) return rc;
+  if ((rc = quiesce(s))) {
+    d->err = "ks_fuse_map: src: " + s->err;
+    return rc;
+  }
+  // 1. the inverse pose, f64, rounded to f32 at the end
+  Pose64 T_D_S{(double)T[0] / qn, {(double)T[1] / qn, (double)T[2] / qn, (double)T[3] / qn}, {(double)T[4], (double)T[5], (double)T[6]}};
+  Pose64 inv{T_D_S.w, {-T_D_S.v[0], -T_D_S.v[1], -T_D_S.v[2]}, {0, 0, 0}};
+  {
+    double r[3];
+    rotate64(inv, T_D_S.t, r);
+    for (int k = 0; k < 3; ++k) inv.t[k] = -r[k];
+  }
+  FuseView V{};
+  V.T.w = (float)inv.w;
+  V.T.v = {(float)inv.v[0], (float)inv.v[1], (float)inv.v[2]};
+  V.T.t = {(float)inv.t[0], (float)inv.t[1], (float)inv.t[2]};
+  V.voxel_size = d->cfg.voxel_size;
+  V.voxel_size_inv = d->voxel_size_inv;
+  V.min_weight = f->min_weight;
+  V.n_src_tiles = s->tiles_initialised;
+  TileSnapshot snap(s);
+  if (stats) stats->tiles_source = snap.nt;
+  if (snap.nt == 0) return KS_OK;
+  if ((rc = snap.fetch_keys(s))) {
+    d->err = "ks_fuse_map: src: " + s->err;
+    return rc;
+  }
+  std::vector<uint64_t> cand;
+  if ((rc = fuse_candidates(d, snap.keys, T_D_S, &cand))) return rc;
+  const size_t nc = cand.size();
+  if (stats) stats->tiles_candidate = nc;
+  const size_t per_chunk = (size_t)std::min<uint64_t>(f->max_workspace_bytes / kFuseTileBytes, nc);
+  if (per_chunk == 0) {
+    if (stats) stats->workspace_bytes = kFuseTileBytes;
+    d->err = "ks_fuse_map: max_workspace_bytes is below what one tile needs";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (stats) stats->workspace_bytes = per_chunk * kFuseTileBytes;
+  if ((rc = d->fuse_ws.reserve(d, per_chunk * kTileVoxels * 8, per_chunk * kTileVoxels * 8))) return rc;
+  if ((rc = d->fuse_keys.reserve(d, 2 * per_chunk, 2 * per_chunk))) return rc;
+  if ((rc = d->fuse_u32.reserve(d, 3 * per_chunk + 1, 3 * per_chunk + 1))) return rc;
+  hipStream_t st = d->stream;
+  const uint32_t tiles_before = d->tiles_initialised;
+  std::vector<uint32_t> counts, offs, idx;
+  std::vector<uint64_t> ukeys;
+  for (size_t first = 0; first < nc; first += per_chunk) {
+    const size_t m = std::min(per_chunk, nc - first);
+    uint64_t* d_cand = d->fuse_keys;
+    uint64_t* d_ukeys = d->fuse_keys + per_chunk;
+    uint32_t* d_counts = d->fuse_u32;
+    uint32_t* d_offs = d->fuse_u32 + per_chunk;
+    HIPCHK(d, hipMemcpyAsync(d_cand, cand.data() + first, m * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_fuse_resample, dim3((uint32_t)m), dim3(512), 0, st, s->table, s->pool, V, (const uint64_t*)d_cand, d->fuse_ws.get(), d_counts);
+    counts.resize(m);
+    HIPCHK(d, hipMemcpyAsync(counts.data(), d_counts, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(d, hipStreamSynchronize(st));
+    HIPCHK(d, hipGetLastError());
+    if (stats) stats->chunks += 1;
+    // the tiles that hold a touched voxel go to the existing insertion and merge: one incoming tile per key, picked by its index
+    ukeys.clear(), offs.clear(), idx.clear();
+    uint64_t voxels = 0;
+    for (size_t i = 0; i < m; ++i) {
+      if (!counts[i]) continue;
+      offs.push_back((uint32_t)ukeys.size());
+      ukeys.push_back(cand[first + i]);
+      idx.push_back((uint32_t)i);
+      voxels += counts[i];
+    }
+    const size_t nu = ukeys.size();
+    if (nu == 0) continue;
+    offs.push_back((uint32_t)nu);
+    uint32_t* d_idx = d_offs + (nu + 1);
+    HIPCHK(d, hipMemcpyAsync(d_ukeys, ukeys.data(), nu * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    HIPCHK(d, hipMemcpyAsync(d_offs, offs.data(), (nu + 1) * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    HIPCHK(d, hipMemcpyAsync(d_idx, idx.data(), nu * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    if ((rc = insert_tiles(d, d_ukeys, nu))) return rc;
+    const uint4* in = d->fuse_ws.get();
+    switch (d->cfg.color_mode) {
+      case KS_COLOR_MODE_COLOR:
+        hipLaunchKernelGGL(k_merge_tiles<KS_COLOR_MODE_COLOR>, dim3((uint32_t)nu), dim3(512), 0, st, d->table, d->pool, (const uint64_t*)d_ukeys,
+                           (const uint32_t*)d_offs, (const uint32_t*)d_idx, in, d->cfg.max_weight, (const uint32_t*)d->d_label_lut);
+        break;
+      case KS_COLOR_MODE_SEMANTIC:
+        hipLaunchKernelGGL(k_merge_tiles<KS_COLOR_MODE_SEMANTIC>, dim3((uint32_t)nu), dim3(512), 0, st, d->table, d->pool, (const uint64_t*)d_ukeys,
+                           (const uint32_t*)d_offs, (const uint32_t*)d_idx, in, d->cfg.max_weight, (const uint32_t*)d->d_label_lut);
+        break;
+      default:
+        hipLaunchKernelGGL(k_merge_tiles<KS_COLOR_MODE_SEMANTIC_PROBABILITY>, dim3((uint32_t)nu), dim3(512), 0, st, d->table, d->pool,
+                           (const uint64_t*)d_ukeys, (const uint32_t*)d_offs, (const uint32_t*)d_idx, in, d->cfg.max_weight,
+                           (const uint32_t*)d->d_label_lut);
+        break;
+    }
+    // what k_merge_tiles leaves to its callers: both sync flags of the tiles it folded into
+    hipLaunchKernelGGL(k_fuse_flag, dim3((uint32_t)((nu + 255) / 256)), dim3(256), 0, st, d->table, d->pool, (const uint64_t*)d_ukeys, (uint32_t)nu,
+                       d->tiles_initialised);
+    HIPCHK(d, hipStreamSynchronize(st));
+    HIPCHK(d, hipGetLastError());
+    if (stats) {
+      stats->tiles_touched += nu;
+      stats->voxels_fused += voxels;
+      stats->tiles_allocated = d->tiles_initialised - tiles_before;
+    }
+  }
+  return KS_OK;
 }
 
 int ks_clear_voxels(ks_ctx* c) {

@@ -81,6 +81,23 @@ int main(int argc, char** argv) {
   };
 #endif
   std::unique_ptr<vxb::TsdfIntegratorBase> integrator = make();
+  // KS_DEMO_FUSE="qw qx qy qz tx ty tz": a submap mapper — the first half of the frames goes into a SUBMAP integrator with layers of
+  // its own, the rest into the main one; then the submap is fused into the main map at the given pose (fuseSubmap: resampled and
+  // merged on the device) and the main integrator's host layers, which follow by its sync policy, are dumped
+  vxb::Layer<vxb::TsdfVoxel> sub_tsdf_layer(0.05f, 16);
+  vxb::Layer<kimera::SemanticVoxel> sub_semantic_layer(0.05f, 16);
+  std::unique_ptr<vxb::TsdfIntegratorBase> submap;
+  float fuse_T[7] = {1.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+  if (const char* fp = std::getenv("KS_DEMO_FUSE")) {
+    if (std::sscanf(fp, "%f %f %f %f %f %f %f", &fuse_T[0], &fuse_T[1], &fuse_T[2], &fuse_T[3], &fuse_T[4], &fuse_T[5], &fuse_T[6]) != 7) return 2;
+#ifdef KS_DEMO_REAL_FACTORY
+    submap = kimera::SemanticTsdfIntegratorFactory::create(method, cfg, sc, &sub_tsdf_layer, &sub_semantic_layer);
+#else
+    submap = kimera::HipSemanticTsdfIntegratorFactory::create(method, cfg, sc, &sub_tsdf_layer, &sub_semantic_layer, opt);
+#endif
+    if (pipeline)
+      if (auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(submap.get())) hip->setSyncPolicy(kimera::HipSemanticTsdfIntegrator::SyncPolicy::kOnDemand);
+  }
   auto on_demand = [&]() {
     if (!pipeline) return;
     if (auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get()))
@@ -165,7 +182,7 @@ int main(int argc, char** argv) {
     }
     if (f + 1 == n_frames && std::getenv("KS_DEMO_ALIGN")) last_points = pts;
     const auto t0 = std::chrono::steady_clock::now();
-    integrator->integratePointCloud(vxb::Transformation(T[0], T[1], T[2], T[3], vxb::Point(T[4], T[5], T[6])), pts, cols, false);
+    (submap && 2 * f < n_frames ? submap : integrator)->integratePointCloud(vxb::Transformation(T[0], T[1], T[2], T[3], vxb::Point(T[4], T[5], T[6])), pts, cols, false);
     const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     integrate_ms += ms;
     if (std::getenv("KS_DEMO_PRUNE")) {
@@ -183,6 +200,19 @@ int main(int argc, char** argv) {
     }
   }
   std::fclose(in);
+  if (submap) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    auto* sub = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(submap.get());
+    if (!hip || !sub) return 7;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->fuseSubmap(*sub, vxb::Transformation(fuse_T[0], fuse_T[1], fuse_T[2], fuse_T[3], vxb::Point(fuse_T[4], fuse_T[5], fuse_T[6])),
+                    kimera::HipSemanticTsdfIntegrator::FuseOptions());
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    const ks_fuse_stats& fs = hip->lastFuseStats();
+    std::printf("adapter_demo: fuseSubmap %.3f ms, %llu source tiles, %llu of %llu candidate tiles touched, %llu allocated, %llu voxels fused, submap host layers %zu blocks\n", ms,
+                (unsigned long long)fs.tiles_source, (unsigned long long)fs.tiles_touched, (unsigned long long)fs.tiles_candidate,
+                (unsigned long long)fs.tiles_allocated, (unsigned long long)fs.voxels_fused, sub_tsdf_layer.getNumberOfAllocatedBlocks());
+  }
   if (pipeline) {
     auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
     if (!hip) return 7;

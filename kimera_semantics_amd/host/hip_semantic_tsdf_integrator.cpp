@@ -413,6 +413,19 @@ bool HipSemanticTsdfIntegrator::alignPointCloud(const vxb::Transformation& T_G_C
   return last_align_stats_.iterations != 0;
 }
 
+bool HipSemanticTsdfIntegrator::fuseSubmap(HipSemanticTsdfIntegrator& submap, const vxb::Transformation& T_G_S, const FuseOptions& options) {
+  const float T[7] = {T_G_S.qw(),          T_G_S.qvec().x(),        T_G_S.qvec().y(),       T_G_S.qvec().z(),
+                      T_G_S.getPosition().x(), T_G_S.getPosition().y(), T_G_S.getPosition().z()};
+  ks_fuse_config fc;
+  ks_fuse_default_config(&fc);
+  fc.min_weight = options.min_weight;
+  fc.max_workspace_bytes = options.max_workspace_bytes;
+  check(ks_fuse_map(ctx_, submap.ctx_, T, &fc, &last_fuse_stats_), "ks_fuse_map");
+  // the touched tiles are flagged `updated` and their voxels marked: the host layers follow like after a frame
+  if (options_.sync_policy == SyncPolicy::kEveryFrame) syncLayers();
+  return last_fuse_stats_.voxels_fused != 0;
+}
+
 bool HipSemanticTsdfIntegrator::extractObjects(const ObjectOptions& options, std::vector<ObjectInstance>* out) {
   CHECK_NOTNULL(out);
   out->clear();

@@ -211,6 +211,20 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// Returns true when `out` is not empty.
   bool extractObjects(const ObjectOptions& options, std::vector<ObjectInstance>* out);
   const ks_objects_stats& lastObjectsStats() const { return last_objects_stats_; }
+  /// Fuses the map of another integrator into this one at a rigid pose ON THE DEVICE (ks_fuse_map; the contract is DESIGN.md,
+  /// section 17): the submap's TSDF and semantics are resampled under T_G_S (submap frame -> this map's frame) into this map's grid and
+  /// folded in by the layer-merge rule — what a server does with a layer it receives on Voxblox's tsdf_map_in
+  /// (mergeLayerAintoLayerB(layer, T, ...)), or a submap mapper after a loop closure or alignPointCloud corrected the submap's pose.
+  /// Both integrators complete their frames in flight; the submap is only read (neither its device map nor its host layers change).
+  /// The touched tiles are flagged like integrated ones, so this integrator's host layers follow by its sync policy: at once under
+  /// kEveryFrame, at the next syncLayers() under kOnDemand.  Both must have the same voxel size and live on the same device; their
+  /// voxels_per_side may differ.  Returns true when at least one voxel was fused.
+  struct FuseOptions {
+    float min_weight = 1e-4f;
+    uint64_t max_workspace_bytes = 1ull << 30;
+  };
+  bool fuseSubmap(HipSemanticTsdfIntegrator& submap, const vxb::Transformation& T_G_S, const FuseOptions& options);
+  const ks_fuse_stats& lastFuseStats() const { return last_fuse_stats_; }
   SyncPolicy syncPolicy() const { return options_.sync_policy; }
 
   ks_ctx* context() { return ctx_; }
@@ -229,6 +243,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_align_stats last_align_stats_{};
   ks_objects_stats last_objects_stats_{};
   ks_remove_stats last_remove_stats_{};
+  ks_fuse_stats last_fuse_stats_{};
   vxb::FloatingPoint prune_distance_ = std::numeric_limits<vxb::FloatingPoint>::max();
   bool prune_keep_semantic_ = true;
   void pruneAfterFrame(const vxb::Transformation& T_G_C) {

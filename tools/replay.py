@@ -11,10 +11,12 @@ device before the frame is integrated (ks_align_points: what `enable_icp` select
 sync) and prints the correction; --objects clusters the surface of every label into object instances on the device at the end
 of the replay (ks_objects_update) and writes their records, centroids in metres and label names; --max-block-distance M prunes the
 map around the sensor position after every frame (ks_remove_distant_blocks: what voxblox::TsdfServer does with
-max_block_distance_from_body; completes the frames in flight), so that a long replay runs in a bounded pool; map saving stays on the host side of the drop-in boundary (out of scope).
+max_block_distance_from_body; completes the frames in flight), so that a long replay runs in a bounded pool; --submap-frames N
+maps like a submap mapper: every N frames go into a second context in the frame of their first camera pose, which is then fused
+into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and merged) and cleared; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
       [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
-      [--max-block-distance 3.0]
+      [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
 import argparse
@@ -67,6 +69,9 @@ def main():
     ap.add_argument("--objects-min-voxels", type=int, default=8, metavar="N")
     ap.add_argument("--max-block-distance", type=float, default=None, metavar="M", help="after every frame remove the blocks whose origin is further "
                     "than M metres from the sensor position (ks_remove_distant_blocks; completes the frames in flight)")
+    ap.add_argument("--submap-frames", type=int, default=0, metavar="N", help="integrate every N frames into a second context, in the frame of "
+                    "their first camera pose, and fuse it into the map at that pose (ks_fuse_map), then clear it")
+    ap.add_argument("--submap-min-weight", type=float, default=1e-4, metavar="W")
     a = ap.parse_args()
     if a.render_every and not a.render_out:
         ap.error("--render-every needs --render-out")
@@ -93,6 +98,35 @@ def main():
     integ = B.HipIntegrator(cfg)
     integ.set_color_to_label(lut[:21], np.arange(21, dtype=np.uint8))
     upd = 0
+
+    class Submapper:
+        """What FS.replay integrates into with --submap-frames: a second context that holds the current submap, in the frame of the
+        submap's first camera pose (T_G_S); after N frames it is fused into the map at T_G_S and emptied."""
+
+        def __init__(self):
+            self.ctx = B.HipIntegrator(cfg)
+            self.ctx.set_color_to_label(lut[:21], np.arange(21, dtype=np.uint8))
+            self.T_G_S, self.n, self.fused, self.seconds, self.updates = None, 0, [], 0.0, 0
+
+        def integrate_depth(self, T_G_C, depth, K, **kw):
+            if self.n == a.submap_frames:
+                self.fuse()
+            if self.T_G_S is None:
+                self.T_G_S = np.asarray(T_G_C, np.float32).copy()
+            self.n += 1
+            return self.ctx.integrate_depth(FS.compose(FS.inverse(self.T_G_S), T_G_C), depth, K, **kw)
+
+        def fuse(self):
+            if self.T_G_S is None:
+                return
+            t1 = time.perf_counter()
+            self.updates += self.ctx.flush().n_voxel_updates
+            self.fused.append(integ.fuse(self.ctx, self.T_G_S, min_weight=a.submap_min_weight))
+            self.ctx.clear()
+            self.seconds += time.perf_counter() - t1
+            self.T_G_S, self.n = None, 0
+
+    sub = Submapper() if a.submap_frames > 0 else None
 
     refresh_s, refreshes, n_seen = 0.0, [], 0
     esdf_s, esdf_ticks = 0.0, []
@@ -150,13 +184,22 @@ def main():
         return T_out
 
     t0 = time.perf_counter()
-    out = FS.replay(seq, integ, use_label_img=not a.bag, on_frame=acc, refine=refine if a.align else None)
+    out = FS.replay(seq, sub or integ, use_label_img=not a.bag, on_frame=acc, refine=refine if a.align else None)
+    if sub:
+        sub.fuse()
+        upd += sub.updates
     upd += integ.flush().n_voxel_updates
     integ.synchronize()
     dt = time.perf_counter() - t0
     print(f"{out['integrated']} frames integrated ({out['skipped_no_tf']} skipped: no tf) in {dt:.3f} s: "
           f"{out['integrated'] / dt:.1f} frames/s incl. H2D of the images, {upd / dt / 1e6:.1f} M voxel updates/s, "
           f"{len(integ.block_indices())} blocks")
+    if sub and sub.fused:
+        print(f"{len(sub.fused)} submaps of {a.submap_frames} frames fused (incl. their flush and clear) in {sub.seconds * 1e3:.1f} ms of the above: "
+              f"{sub.seconds / len(sub.fused) * 1e3:.2f} ms each; {sum(f['voxels_fused'] for f in sub.fused)} voxels fused into "
+              f"{sum(f['tiles_touched'] for f in sub.fused)} tiles ({sum(f['tiles_allocated'] for f in sub.fused)} new) from "
+              f"{sum(f['tiles_source'] for f in sub.fused)} submap tiles, work space at most {max(f['workspace_bytes'] for f in sub.fused) / 2 ** 20:.1f} MiB")
+        sub.ctx.close()
     if prunes:
         print(f"pruned after every frame beyond {a.max_block_distance} m in {prune_s * 1e3:.1f} ms of the above: {prune_s / len(prunes) * 1e3:.3f} ms each; "
               f"{sum(p['blocks_removed'] for p in prunes)} blocks removed, {sum(p['tiles_moved'] for p in prunes)} tiles moved, at most "
