@@ -667,6 +667,21 @@ int ks_integrate_round_exact(ks_ctx* marcher, ks_ctx* owner, void* rccl_comm, in
 /* Diagnostics (used by tests): stable LSD radix sort of n HOST keys (key_bits = 32 or 64, bits
  * [0,end_bit)) and optional u32 payload with the library's own GPU sort. */
 int ks_debug_radix_sort(ks_ctx* ctx, void* keys, uint32_t* vals, size_t n, int key_bits, unsigned end_bit);
+/* ... of the bits [begin_bit, end_bit) only (end_bit is clamped to key_bits; an empty range leaves the arrays as they are):
+ * keys that are equal in those bits keep their order, whatever their other bits hold, and every key arrives whole.  vals may be
+ * NULL.  In place on the host arrays, through the context's own sorts and their persistent workspace: consecutive calls on one
+ * context alternate between the workspace's halves as a context's frames do.  key_bits other than 32 / 64, or a NULL keys with
+ * n > 0: KS_ERR_INVALID_ARG. */
+int ks_debug_radix_sort_range(ks_ctx* ctx, void* keys, uint32_t* vals, size_t n, int key_bits, unsigned begin_bit, unsigned end_bit);
+/* ... and the form whose key counts live in device memory: nb (1 .. 8) sorts of u64 keys with u32 payload in one launch sequence,
+ * sort i over the first min(counts[i], cap) entries of keys[i * cap ...] / vals[i * cap ...], bits [begin_bit, end_bit) as above.
+ * The sort ping-pongs between the uploaded arrays (a) and a second buffer set (b) filled with the byte 0xA5, one 8-bit pass at a
+ * time; what comes back, in place, is the WHOLE buffer that holds the result, all cap entries of it: b after an odd number of
+ * passes, else a.  Its entries from the count on are therefore 0xA5 bytes (b), or whatever a holds there (after two passes: the
+ * input), unless the sort wrote where it must not.  No graph capture.  NULL arrays, cap = 0 or >= 2^32, an empty or reversed bit
+ * range, end_bit > 64 and whatever the batched sort itself refuses (nb < 1, nb > 8): KS_ERR_INVALID_ARG. */
+int ks_debug_radix_sort_batch(ks_ctx* ctx, uint64_t* keys, uint32_t* vals, const uint64_t* counts, int nb, size_t cap,
+                              unsigned begin_bit, unsigned end_bit);
 
 int ks_synchronize(ks_ctx* ctx);
 void* ks_stream(ks_ctx* ctx); /* the hipStream_t that reads the caller's device inputs (stage A; with

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "ks_default_config", "ks_create", "ks_destroy", "ks_last_error", "ks_set_color_to_label",
     "ks_integrate_points", "ks_integrate_points_device", "ks_integrate_depth", "ks_integrate_depth_device", "ks_num_blocks", "ks_get_block_indices",
     "ks_get_updated_block_indices", "ks_count_updated_voxels", "ks_download_updated_voxels", "ks_download_blocks", "ks_upload_blocks", "ks_host_alloc", "ks_host_free", "ks_get_tile_keys", "ks_export_tiles_device", "ks_merge_tiles_device", "ks_clear", "ks_clear_voxels", "ks_reset_tiles", "ks_tile_owner", "ks_reduce",
-    "ks_debug_radix_sort", "ks_synchronize", "ks_flush", "ks_stream",
+    "ks_debug_radix_sort", "ks_debug_radix_sort_range", "ks_debug_radix_sort_batch", "ks_synchronize", "ks_flush", "ks_stream",
     "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
@@ -236,6 +236,8 @@ def lib():
         L.ks_tile_owner.argtypes = [C.c_uint64, C.c_int]
         L.ks_reduce.argtypes = [vp, vp, C.c_int, C.c_int, C.POINTER(KsReduceStats)]
         L.ks_debug_radix_sort.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.c_uint]
+        L.ks_debug_radix_sort_range.argtypes = [vp, vp, vp, C.c_size_t, C.c_int, C.c_uint, C.c_uint]
+        L.ks_debug_radix_sort_batch.argtypes = [vp, vp, vp, vp, C.c_int, C.c_size_t, C.c_uint, C.c_uint]
         L.ks_synchronize.argtypes = [vp]
         L.ks_flush.argtypes = [vp, C.POINTER(KsFrameStats)]
         L.ks_stream.argtypes = [vp]
@@ -734,6 +736,25 @@ class HipIntegrator:
         vals = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint32).copy()
         self._chk(lib().ks_debug_radix_sort(self._h, _ptr(keys), _ptr(vals), keys.shape[0], bits,
                                             bits if end_bit is None else end_bit))
+        return keys, vals
+
+    def debug_radix_sort_range(self, keys: np.ndarray, vals=None, begin_bit=0, end_bit=None):
+        """ks_debug_radix_sort_range: (keys, vals) stably sorted by the bits [begin_bit, end_bit) of the keys (copies)."""
+        keys = np.ascontiguousarray(keys).copy()
+        bits = keys.dtype.itemsize * 8
+        vals = None if vals is None else np.ascontiguousarray(vals, dtype=np.uint32).copy()
+        self._chk(lib().ks_debug_radix_sort_range(self._h, _ptr(keys), _ptr(vals), keys.shape[0], bits, begin_bit,
+                                                  bits if end_bit is None else end_bit))
+        return keys, vals
+
+    def debug_radix_sort_batch(self, keys: np.ndarray, vals: np.ndarray, counts, begin_bit, end_bit):
+        """ks_debug_radix_sort_batch: keys u64 [nb, cap], vals u32 [nb, cap], counts [nb] -> the whole result buffers (copies)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64).copy()
+        vals = np.ascontiguousarray(vals, dtype=np.uint32).copy()
+        counts = np.ascontiguousarray(counts, dtype=np.uint64)
+        nb, cap = keys.shape
+        assert vals.shape == (nb, cap) and counts.shape == (nb,)
+        self._chk(lib().ks_debug_radix_sort_batch(self._h, _ptr(keys), _ptr(vals), _ptr(counts), nb, cap, begin_bit, end_bit))
         return keys, vals
 
     def synchronize(self):

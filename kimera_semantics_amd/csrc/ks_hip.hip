@@ -845,8 +845,8 @@ int sort_keys(ks_ctx* c, K* a, K* b, size_t n, unsigned end_bit, K** result, uns
 }
 template <typename K>
 int sort_pairs(ks_ctx* c, K* ka, K* kb, uint32_t* va, uint32_t* vb, size_t n, unsigned end_bit, K** kres,
-               uint32_t** vres) {
-  HIPCHK(c, (ksrs::sort<K, true>(c->sort_ws, ka, kb, va, vb, n, end_bit, c->stream, kres, vres)));
+               uint32_t** vres, unsigned begin_bit = 0) {
+  HIPCHK(c, (ksrs::sort<K, true>(c->sort_ws, ka, kb, va, vb, n, end_bit, c->stream, kres, vres, begin_bit)));
   return KS_OK;
 }
 
@@ -4021,7 +4021,7 @@ void ks_host_free(void* p) {
   if (p) (void)hipHostFree(p);
 }
 
-int ks_debug_radix_sort(ks_ctx* c, void* keys, uint32_t* vals, size_t n, int key_bits, unsigned end_bit) {
+int ks_debug_radix_sort_range(ks_ctx* c, void* keys, uint32_t* vals, size_t n, int key_bits, unsigned begin_bit, unsigned end_bit) {
   if (!c || (n && !keys) || (key_bits != 32 && key_bits != 64)) return KS_ERR_INVALID_ARG;
   if (n == 0) return KS_OK;
   const size_t kb = key_bits / 8;
@@ -4038,19 +4038,63 @@ int ks_debug_radix_sort(ks_ctx* c, void* keys, uint32_t* vals, size_t n, int key
   uint32_t* vres = nullptr;
   if (key_bits == 32) {
     uint32_t* r = nullptr;
-    rc = vals ? sort_pairs(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres)
-              : sort_keys(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), n, end_bit, &r);
+    rc = vals ? sort_pairs(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres, begin_bit)
+              : sort_keys(c, (uint32_t*)ka.get(), (uint32_t*)kbuf.get(), n, end_bit, &r, begin_bit);
     kres = r;
   } else {
     uint64_t* r = nullptr;
-    rc = vals ? sort_pairs(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres)
-              : sort_keys(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), n, end_bit, &r);
+    rc = vals ? sort_pairs(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), va.get(), vb.get(), n, end_bit, &r, &vres, begin_bit)
+              : sort_keys(c, (uint64_t*)ka.get(), (uint64_t*)kbuf.get(), n, end_bit, &r, begin_bit);
     kres = r;
   }
   if (rc) return rc;
   HIPCHK(c, hipStreamSynchronize(c->stream));
   HIPCHK(c, hipMemcpy(keys, kres, n * kb, hipMemcpyDeviceToHost));
   if (vals) HIPCHK(c, hipMemcpy(vals, vres, n * 4, hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+
+int ks_debug_radix_sort(ks_ctx* c, void* keys, uint32_t* vals, size_t n, int key_bits, unsigned end_bit) {
+  return ks_debug_radix_sort_range(c, keys, vals, n, key_bits, 0u, end_bit);
+}
+
+int ks_debug_radix_sort_batch(ks_ctx* c, uint64_t* keys, uint32_t* vals, const uint64_t* counts, int nb, size_t cap, unsigned begin_bit,
+                              unsigned end_bit) {
+  if (!c || !keys || !vals || !counts || nb < 1 || nb > ksrs::kRsBatch || cap == 0 || cap > 0xffffffffull || begin_bit >= end_bit || end_bit > 64)
+    return KS_ERR_INVALID_ARG;
+  const int passes = (int)((end_bit - begin_bit + 7) / 8);
+  const size_t ws_words = ksrs::ws_words_dev(cap, passes);
+  DevBuf<uint64_t> ka[ksrs::kRsBatch], kb[ksrs::kRsBatch];
+  DevBuf<uint32_t> va[ksrs::kRsBatch], vb[ksrs::kRsBatch], ws[ksrs::kRsBatch];
+  DevBuf<unsigned long long> d_counts;
+  int rc;
+  if ((rc = d_counts.alloc(c, (size_t)nb))) return rc;
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "counts are copied as they are");
+  HIPCHK(c, hipMemcpy(d_counts, counts, (size_t)nb * sizeof(uint64_t), hipMemcpyHostToDevice));
+  ksrs::DevBatch<uint64_t> B{};
+  for (int y = 0; y < nb; ++y) {
+    if ((rc = ka[y].alloc(c, cap)) || (rc = kb[y].alloc(c, cap)) || (rc = va[y].alloc(c, cap)) || (rc = vb[y].alloc(c, cap)) || (rc = ws[y].alloc(c, ws_words)))
+      return rc;
+    HIPCHK(c, hipMemcpy(ka[y], keys + (size_t)y * cap, cap * sizeof(uint64_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemcpy(va[y], vals + (size_t)y * cap, cap * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIPCHK(c, hipMemsetAsync(kb[y], 0xA5, cap * sizeof(uint64_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(vb[y], 0xA5, cap * sizeof(uint32_t), c->stream));
+    B.keys_a[y] = ka[y];
+    B.keys_b[y] = kb[y];
+    B.vals_a[y] = va[y];
+    B.vals_b[y] = vb[y];
+    B.n_dev[y] = d_counts.get() + y;
+    B.ws[y] = ws[y];
+  }
+  const hipError_t e = ksrs::sort_dev_batch<uint64_t>(B, nb, ws_words, cap, begin_bit, end_bit, c->stream);
+  if (e == hipErrorInvalidValue) return KS_ERR_INVALID_ARG;   // (what the sort refuses: it has launched nothing)
+  HIPCHK(c, e);
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  const bool in_b = (passes & 1) != 0;
+  for (int y = 0; y < nb; ++y) {
+    HIPCHK(c, hipMemcpy(keys + (size_t)y * cap, in_b ? kb[y].get() : ka[y].get(), cap * sizeof(uint64_t), hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(vals + (size_t)y * cap, in_b ? vb[y].get() : va[y].get(), cap * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  }
   return KS_OK;
 }
 

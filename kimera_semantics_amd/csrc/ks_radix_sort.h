@@ -26,9 +26,16 @@ constexpr int kMaxBins = 2048;
 constexpr size_t kHistBlocks = 2048;   // workgroups of the histogram kernel at most
 constexpr uint32_t kFlagLocal = 1u << 30, kFlagPrefix = 2u << 30, kCountMask = (1u << 30) - 1u;
 
-template <int RB, typename K>
-__device__ __forceinline__ uint32_t digit_of(K key, int shift) {
-  return (uint32_t)(key >> shift) & (uint32_t)((1 << RB) - 1);
+// mask: the RB ones of a full digit, fewer in a sort's last pass (last_digit_mask).  Never more: the digit indexes 2^RB bins.
+template <typename K>
+__device__ __forceinline__ uint32_t digit_of(K key, int shift, uint32_t mask) {
+  return (uint32_t)(key >> shift) & mask;
+}
+// The last pass of a sort of [begin_bit, end_bit) sees only the bits that remain below end_bit: its digit mask is this, every
+// other pass's (1 << rb) - 1.  The histogram and the passes must use the same digit, or the scatter leaves its bins.
+inline uint32_t last_digit_mask(unsigned begin_bit, unsigned end_bit, int rb) {
+  const unsigned rem = (end_bit - begin_bit) - ((end_bit - begin_bit + rb - 1) / rb - 1) * rb;   // 1 .. rb
+  return (1u << rem) - 1u;
 }
 
 // lanes of this wave (among `active`) that hold the same RB-bit digit: multi-split by ballots
@@ -48,12 +55,12 @@ __device__ __forceinline__ unsigned long long match_digit(uint32_t d, unsigned l
 // It also clears the workspace half the PREVIOUS sort used (zero_ptr, zero_words: a multiple of 4),
 // which becomes the next sort's workspace: no memset launch per sort.
 template <typename K, int RB>
-__device__ __forceinline__ void rs_hist_body(const K* __restrict__ keys, uint32_t n, int passes, int begin_bit,
+__device__ __forceinline__ void rs_hist_body(const K* __restrict__ keys, uint32_t n, int passes, int begin_bit, uint32_t last_mask,
                                              uint32_t* __restrict__ hist, uint32_t* __restrict__ zero_ptr,
                                              uint32_t zero_words, const unsigned long long* __restrict__ n_dev, uint32_t* s_hist) {
   constexpr int kBins = 1 << RB;
   const uint32_t tid = threadIdx.x, lane = tid & 63u;
-  if (n_dev) n = (uint32_t)(*n_dev < (unsigned long long)n ? *n_dev : (unsigned long long)n);   // sort_dev: the key count lives on the device (n = capacity)
+  if (n_dev) n = (uint32_t)(*n_dev < (unsigned long long)n ? *n_dev : (unsigned long long)n);   // sort_dev_batch: the key count lives on the device (n = capacity)
   for (uint32_t i = blockIdx.x * 256u + tid; i < zero_words / 4u; i += gridDim.x * 256u)
     ((uint4*)zero_ptr)[i] = make_uint4(0u, 0u, 0u, 0u);
   for (int i = tid; i < passes * kBins; i += 256) s_hist[i] = 0;
@@ -70,7 +77,7 @@ __device__ __forceinline__ void rs_hist_body(const K* __restrict__ keys, uint32_
       const K key = valid ? keys[idx] : (K)0;
       const unsigned long long active = __ballot(valid);
       for (int p = 0; p < passes; ++p) {
-        const uint32_t d = digit_of<RB>(key, begin_bit + p * RB);
+        const uint32_t d = digit_of(key, begin_bit + p * RB, p == passes - 1 ? last_mask : (uint32_t)(kBins - 1));
         // the upper digits of these keys are nearly constant: one add for a wave-uniform digit,
         // per-lane LDS atomics otherwise
         const uint32_t d0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)d);
@@ -100,11 +107,11 @@ __device__ __forceinline__ void rs_hist_body(const K* __restrict__ keys, uint32_
   }
 }
 template <typename K, int RB>
-__global__ void __launch_bounds__(256) k_rs_hist(const K* __restrict__ keys, uint32_t n, int passes, int begin_bit,
+__global__ void __launch_bounds__(256) k_rs_hist(const K* __restrict__ keys, uint32_t n, int passes, int begin_bit, uint32_t last_mask,
                                                  uint32_t* __restrict__ hist, uint32_t* __restrict__ zero_ptr,
-                                                 uint32_t zero_words, const unsigned long long* __restrict__ n_dev = nullptr) {
+                                                 uint32_t zero_words) {
   extern __shared__ uint32_t s_hist[];  // [passes][kBins]
-  rs_hist_body<K, RB>(keys, n, passes, begin_bit, hist, zero_ptr, zero_words, n_dev, s_hist);
+  rs_hist_body<K, RB>(keys, n, passes, begin_bit, last_mask, hist, zero_ptr, zero_words, nullptr, s_hist);
 }
 // Up to kRsBatch independent sorts of the same capacity per launch (blockIdx.y = sort): their launches are latency bound,
 // and a launch costs the same for one sort or four.
@@ -119,9 +126,9 @@ struct DevBatch {
   uint32_t* ws[kRsBatch];
 };
 template <typename K, int RB>
-__global__ void __launch_bounds__(256) k_rs_hist_b(DevBatch<K> B, uint32_t cap, int passes, int begin_bit) {
+__global__ void __launch_bounds__(256) k_rs_hist_b(DevBatch<K> B, uint32_t cap, int passes, int begin_bit, uint32_t last_mask) {
   extern __shared__ uint32_t s_hist[];
-  rs_hist_body<K, RB>(B.keys_a[blockIdx.y], cap, passes, begin_bit, B.ws[blockIdx.y], nullptr, 0u, B.n_dev[blockIdx.y], s_hist);
+  rs_hist_body<K, RB>(B.keys_a[blockIdx.y], cap, passes, begin_bit, last_mask, B.ws[blockIdx.y], nullptr, 0u, B.n_dev[blockIdx.y], s_hist);
 }
 
 // One pass.  THREADS x ITEMS keys per tile.  REORDER (keys only, large inputs): the tile's keys are first put in
@@ -130,7 +137,7 @@ __global__ void __launch_bounds__(256) k_rs_hist_b(DevBatch<K> B, uint32_t cap, 
 template <typename K, bool HAS_VALUES, int THREADS, int ITEMS, int RB, bool REORDER = false>
 __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* __restrict__ keys_out,
                                              const uint32_t* __restrict__ vals_in,
-                                             uint32_t* __restrict__ vals_out, uint32_t n, int shift,
+                                             uint32_t* __restrict__ vals_out, uint32_t n, int shift, uint32_t mask,
                                              const uint32_t* __restrict__ bin_hist,
                                              uint32_t* __restrict__ status, uint32_t* __restrict__ ticket,
                                              const unsigned long long* __restrict__ n_dev) {
@@ -138,7 +145,7 @@ __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* _
   constexpr int kChunks = kBins / 64;
   constexpr int kWaves = THREADS / 64;
   constexpr int kTile = THREADS * ITEMS;
-  if (n_dev) n = (uint32_t)(*n_dev < (unsigned long long)n ? *n_dev : (unsigned long long)n);   // sort_dev (the grid covers the capacity)
+  if (n_dev) n = (uint32_t)(*n_dev < (unsigned long long)n ? *n_dev : (unsigned long long)n);   // sort_dev_batch (the grid covers the capacity)
   __shared__ uint32_t s_cnt[kWaves][kBins];  // per-wave digit counters, later exclusive wave bases
   __shared__ uint32_t s_off[kBins];          // global offset of this tile's first key of each digit
   __shared__ uint32_t s_chunk[kChunks];      // sums of 64-bin chunks of the pass histogram
@@ -154,7 +161,7 @@ __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* _
   for (int i = tid; i < kWaves * kBins; i += THREADS) (&s_cnt[0][0])[i] = 0;
   __syncthreads();
   const uint32_t tile = s_tile;
-  // (sort_dev: tickets are handed out in arrival order, so the tiles past the last key are exactly those that arrive
+  // (sort_dev_batch: tickets are handed out in arrival order, so the tiles past the last key are exactly those that arrive
   // after every tile with keys has its ticket: nothing ever looks back at them)
   if (n_dev && (unsigned long long)tile * kTile >= (unsigned long long)n) return;
   const uint32_t wbase = tile * kTile + wave * (ITEMS * 64);
@@ -170,7 +177,7 @@ __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* _
   for (int i = 0; i < ITEMS; ++i) {
     const uint32_t idx = wbase + i * 64 + lane;
     const bool valid = idx < n;
-    const uint32_t d = digit_of<RB>(key[i], shift);
+    const uint32_t d = digit_of(key[i], shift, mask);
     const unsigned long long peers = match_digit<RB>(d, __ballot(valid));
     const uint32_t prev = s_cnt[wave][d];
     rd[i] = (prev + (uint32_t)__popcll(peers & ((1ull << lane) - 1ull))) | (d << 20);
@@ -278,7 +285,7 @@ __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* _
     const uint32_t count = (n - t0 < (uint32_t)kTile) ? n - t0 : (uint32_t)kTile;
     for (uint32_t j = tid; j < count; j += THREADS) {
       const K k = s_keys[j];
-      const uint32_t d = digit_of<RB>(k, shift);
+      const uint32_t d = digit_of(k, shift, mask);
       keys_out[s_off[d] + (j - s_loc[d])] = k;
     }
     return;
@@ -298,26 +305,26 @@ __device__ __forceinline__ void rs_pass_body(const K* __restrict__ keys_in, K* _
 template <typename K, bool HAS_VALUES, int THREADS, int ITEMS, int RB, bool REORDER = false>
 __global__ void __launch_bounds__(THREADS) k_rs_pass(const K* __restrict__ keys_in, K* __restrict__ keys_out,
                                                      const uint32_t* __restrict__ vals_in,
-                                                     uint32_t* __restrict__ vals_out, uint32_t n, int shift,
+                                                     uint32_t* __restrict__ vals_out, uint32_t n, int shift, uint32_t mask,
                                                      const uint32_t* __restrict__ bin_hist,
-                                                     uint32_t* __restrict__ status, uint32_t* __restrict__ ticket,
-                                                     const unsigned long long* __restrict__ n_dev = nullptr) {
-  rs_pass_body<K, HAS_VALUES, THREADS, ITEMS, RB, REORDER>(keys_in, keys_out, vals_in, vals_out, n, shift, bin_hist, status, ticket, n_dev);
+                                                     uint32_t* __restrict__ status, uint32_t* __restrict__ ticket) {
+  rs_pass_body<K, HAS_VALUES, THREADS, ITEMS, RB, REORDER>(keys_in, keys_out, vals_in, vals_out, n, shift, mask, bin_hist, status, ticket, nullptr);
 }
 // pass p of the batched sorts: odd passes read the b buffers
 template <typename K, int THREADS, int ITEMS, int RB>
-__global__ void __launch_bounds__(THREADS) k_rs_pass_b(DevBatch<K> B, uint32_t cap, int begin_bit, int p, uint32_t tiles) {
+__global__ void __launch_bounds__(THREADS) k_rs_pass_b(DevBatch<K> B, uint32_t cap, int begin_bit, int p, uint32_t tiles, uint32_t mask) {
   const uint32_t y = blockIdx.y;
   uint32_t* ws = B.ws[y];
   const bool odd = (p & 1) != 0;
   rs_pass_body<K, true, THREADS, ITEMS, RB, false>(odd ? B.keys_b[y] : B.keys_a[y], odd ? B.keys_a[y] : B.keys_b[y], odd ? B.vals_b[y] : B.vals_a[y],
-                                                   odd ? B.vals_a[y] : B.vals_b[y], cap, begin_bit + p * RB, ws + (size_t)p * kMaxBins,
+                                                   odd ? B.vals_a[y] : B.vals_b[y], cap, begin_bit + p * RB, mask, ws + (size_t)p * kMaxBins,
                                                    ws + ((size_t)kMaxPasses * kMaxBins + kMaxPasses) + (size_t)p * tiles * (1 << RB),
                                                    ws + (size_t)kMaxPasses * kMaxBins + p, B.n_dev[y]);
 }
 
-// Host-side workspace + launcher.  Sorts bits [begin_bit, end_bit) of the keys; the result is
-// in (*keys_result, *vals_result), each pointing at one of the two ping-pong buffers.
+// Host-side workspace + launcher.  Sorts bits [begin_bit, end_bit) of the keys and no others: keys that are equal in those bits
+// keep their order whatever their other bits hold (the last pass masks its digit to the bits that remain; tests/sort_case.py
+// holds the sort to this).  The result is in (*keys_result, *vals_result), each pointing at one of the two ping-pong buffers.
 // Two halves used alternately: while a sort runs in one half its histogram kernel clears what the
 // previous sort left in the other, so a sort never needs a memset of its own.
 struct Workspace {
@@ -344,7 +351,7 @@ inline hipError_t ensure(Workspace& w, size_t words, hipStream_t stream) {
 
 template <typename K, bool HAS_VALUES, int THREADS, int ITEMS, int RB, bool REORDER = false>
 inline void launch_passes(Workspace& w, K*& kin, K*& kout, uint32_t*& vin, uint32_t*& vout, size_t n, int passes,
-                          uint32_t tiles, unsigned begin_bit, hipStream_t stream) {
+                          uint32_t tiles, unsigned begin_bit, uint32_t last_mask, hipStream_t stream) {
   constexpr int kBins = 1 << RB;
   uint32_t* base = w.d_ws + (size_t)w.cur * w.words;
   uint32_t* hist = base;
@@ -352,7 +359,7 @@ inline void launch_passes(Workspace& w, K*& kin, K*& kout, uint32_t*& vin, uint3
   uint32_t* status = base + kHeadWords;
   for (int p = 0; p < passes; ++p) {
     hipLaunchKernelGGL((k_rs_pass<K, HAS_VALUES, THREADS, ITEMS, RB, REORDER>), dim3(tiles), dim3(THREADS), 0, stream, kin, kout,
-                       vin, vout, (uint32_t)n, (int)begin_bit + p * RB, hist + (size_t)p * kMaxBins,
+                       vin, vout, (uint32_t)n, (int)begin_bit + p * RB, p == passes - 1 ? last_mask : (uint32_t)(kBins - 1), hist + (size_t)p * kMaxBins,
                        status + (size_t)p * tiles * kBins, tickets + p);
     K* tk = kin; kin = kout; kout = tk;
     uint32_t* tv = vin; vin = vout; vout = tv;
@@ -365,6 +372,7 @@ inline hipError_t sort_rb(Workspace& w, K* keys_a, K* keys_b, uint32_t* vals_a, 
                           uint32_t** vals_result) {
   constexpr int kBins = 1 << RB;
   const int passes = (int)((end_bit - begin_bit + RB - 1) / RB);
+  const uint32_t last_mask = last_digit_mask(begin_bit, end_bit, RB);
   // tile size: 2048 keys keeps per-tile latency low for per-frame sizes; larger tiles shorten
   // the look-back chain for million-scale inputs
   // keys-only sorts of more than 2^20 keys (the pair sort of large frames) take the LDS-reordering variant
@@ -376,7 +384,7 @@ inline hipError_t sort_rb(Workspace& w, K* keys_a, K* keys_b, uint32_t* vals_a, 
   if (e != hipSuccess) return e;
   const int h = w.cur ^ 1;  // this sort's half is clean; the histogram kernel clears the other one
   hipLaunchKernelGGL((k_rs_hist<K, RB>), dim3((uint32_t)std::min<size_t>((n + 2047) / 2048, kHistBlocks)), dim3(256),
-                     (size_t)passes * kBins * sizeof(uint32_t), stream, keys_a, (uint32_t)n, passes, (int)begin_bit,
+                     (size_t)passes * kBins * sizeof(uint32_t), stream, keys_a, (uint32_t)n, passes, (int)begin_bit, last_mask,
                      w.d_ws + (size_t)h * w.words, w.d_ws + (size_t)(h ^ 1) * w.words,
                      (uint32_t)((w.dirty[h ^ 1] + 3) & ~(size_t)3));
   w.dirty[h ^ 1] = 0;
@@ -386,68 +394,31 @@ inline hipError_t sort_rb(Workspace& w, K* keys_a, K* keys_b, uint32_t* vals_a, 
   K* kout = keys_b;
   uint32_t* vin = vals_a;
   uint32_t* vout = vals_b;
-  if (tile == 2048) launch_passes<K, HAS_VALUES, 256, 8, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, stream);
+  if (tile == 2048) launch_passes<K, HAS_VALUES, 256, 8, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, last_mask, stream);
   else if (tile == 8192 && reorder) {
-    if constexpr (!HAS_VALUES) launch_passes<K, false, 512, 16, RB, true>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, stream);
-  } else if (tile == 8192) launch_passes<K, HAS_VALUES, 512, 16, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, stream);
-  else launch_passes<K, HAS_VALUES, 512, 32, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, stream);
+    if constexpr (!HAS_VALUES) launch_passes<K, false, 512, 16, RB, true>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, last_mask, stream);
+  } else if (tile == 8192) launch_passes<K, HAS_VALUES, 512, 16, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, last_mask, stream);
+  else launch_passes<K, HAS_VALUES, 512, 32, RB>(w, kin, kout, vin, vout, n, passes, tiles, begin_bit, last_mask, stream);
   *keys_result = kin;
   if (vals_result) *vals_result = vin;
   return hipGetLastError();
 }
 
-// The same sort with the key count in DEVICE memory and nothing on the host that changes from call to call: the launch
-// sequence depends only on `cap` (capacity of the buffers) and can be captured into a graph and replayed.  `ws` holds
-// ws_words_dev(cap, passes) words and is cleared by a memset node at the head of the sequence.  Keys + values, tiles of
-// 2048 (cap <= 2^20) / 8192 / 16384 keys.  The result is in (keys_b, vals_b) after an odd number of passes, else in (a).
+// The sort with the key counts in DEVICE memory and nothing on the host that changes from call to call: the launch sequence
+// depends only on `cap` (capacity of the buffers) and can be captured into a graph and replayed.  Keys + values, tiles of
+// 2048 (cap <= 2^20) / 8192 / 16384 keys; a workspace holds ws_words_dev(cap, passes) words.
 inline size_t dev_tile(size_t cap) { return cap <= (1u << 20) ? 2048 : cap <= (1u << 24) ? 8192 : 16384; }
 inline size_t ws_words_dev(size_t cap, int passes) { return kHeadWords + (size_t)passes * ((cap + dev_tile(cap) - 1) / dev_tile(cap)) * 256; }
-template <typename K>
-inline hipError_t sort_dev(uint32_t* ws, size_t ws_words, K* keys_a, K* keys_b, uint32_t* vals_a, uint32_t* vals_b,
-                           const unsigned long long* n_dev, size_t cap, unsigned begin_bit, unsigned end_bit, hipStream_t stream,
-                           K** keys_result, uint32_t** vals_result) {
-  constexpr int RB = 8;
-  constexpr int kBins = 1 << RB;
-  const int passes = (int)((end_bit - begin_bit + RB - 1) / RB);
-  const size_t tile = dev_tile(cap);
-  const uint32_t tiles = (uint32_t)((cap + tile - 1) / tile);
-  if (kHeadWords + (size_t)passes * tiles * kBins > ws_words) return hipErrorInvalidValue;
-  hipError_t e = hipMemsetAsync(ws, 0, (kHeadWords + (size_t)passes * tiles * kBins) * sizeof(uint32_t), stream);
-  if (e != hipSuccess) return e;
-  uint32_t* hist = ws;
-  uint32_t* tickets = ws + (size_t)kMaxPasses * kMaxBins;
-  uint32_t* status = ws + kHeadWords;
-  hipLaunchKernelGGL((k_rs_hist<K, RB>), dim3((uint32_t)std::min<size_t>((cap + 2047) / 2048, kHistBlocks)), dim3(256),
-                     (size_t)passes * kBins * sizeof(uint32_t), stream, (const K*)keys_a, (uint32_t)cap, passes, (int)begin_bit, hist,
-                     (uint32_t*)nullptr, 0u, n_dev);
-  K* kin = keys_a;
-  K* kout = keys_b;
-  uint32_t* vin = vals_a;
-  uint32_t* vout = vals_b;
-  for (int p = 0; p < passes; ++p) {
-#define KS_RS_DEV_PASS(THREADS, ITEMS)                                                                                                 \
-  hipLaunchKernelGGL((k_rs_pass<K, true, THREADS, ITEMS, RB>), dim3(tiles), dim3(THREADS), 0, stream, (const K*)kin, kout,             \
-                     (const uint32_t*)vin, vout, (uint32_t)cap, (int)begin_bit + p * RB, (const uint32_t*)(hist + (size_t)p * kMaxBins), \
-                     status + (size_t)p * tiles * kBins, tickets + p, n_dev)
-    if (tile == 2048) KS_RS_DEV_PASS(256, 8);
-    else if (tile == 8192) KS_RS_DEV_PASS(512, 16);
-    else KS_RS_DEV_PASS(512, 32);
-#undef KS_RS_DEV_PASS
-    K* tk = kin; kin = kout; kout = tk;
-    uint32_t* tv = vin; vin = vout; vout = tv;
-  }
-  *keys_result = kin;
-  *vals_result = vin;
-  return hipGetLastError();
-}
 
 // nb sorts of the same capacity in one launch sequence (memset per workspace, then hist + passes with blockIdx.y = sort).
-// Results as sort_dev: in the b buffers after an odd number of passes.
+// Sort y takes the first min(*n_dev[y], cap) keys of its a buffers; its result is in (keys_b, vals_b) after an odd number of passes,
+// else in (a), and nothing beyond the count is written in either.
 template <typename K>
 inline hipError_t sort_dev_batch(const DevBatch<K>& B, int nb, size_t ws_words, size_t cap, unsigned begin_bit, unsigned end_bit, hipStream_t stream) {
   constexpr int RB = 8;
   constexpr int kBins = 1 << RB;
   const int passes = (int)((end_bit - begin_bit + RB - 1) / RB);
+  const uint32_t last_mask = last_digit_mask(begin_bit, end_bit, RB);
   const size_t tile = dev_tile(cap);
   const uint32_t tiles = (uint32_t)((cap + tile - 1) / tile);
   if (kHeadWords + (size_t)passes * tiles * kBins > ws_words || nb < 1 || nb > kRsBatch) return hipErrorInvalidValue;
@@ -456,11 +427,12 @@ inline hipError_t sort_dev_batch(const DevBatch<K>& B, int nb, size_t ws_words, 
     if (e != hipSuccess) return e;
   }
   hipLaunchKernelGGL((k_rs_hist_b<K, RB>), dim3((uint32_t)std::min<size_t>((cap + 2047) / 2048, kHistBlocks), (uint32_t)nb), dim3(256),
-                     (size_t)passes * kBins * sizeof(uint32_t), stream, B, (uint32_t)cap, passes, (int)begin_bit);
+                     (size_t)passes * kBins * sizeof(uint32_t), stream, B, (uint32_t)cap, passes, (int)begin_bit, last_mask);
   for (int p = 0; p < passes; ++p) {
-    if (tile == 2048) hipLaunchKernelGGL((k_rs_pass_b<K, 256, 8, RB>), dim3(tiles, (uint32_t)nb), dim3(256), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles);
-    else if (tile == 8192) hipLaunchKernelGGL((k_rs_pass_b<K, 512, 16, RB>), dim3(tiles, (uint32_t)nb), dim3(512), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles);
-    else hipLaunchKernelGGL((k_rs_pass_b<K, 512, 32, RB>), dim3(tiles, (uint32_t)nb), dim3(512), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles);
+    const uint32_t mask = p == passes - 1 ? last_mask : (uint32_t)(kBins - 1);
+    if (tile == 2048) hipLaunchKernelGGL((k_rs_pass_b<K, 256, 8, RB>), dim3(tiles, (uint32_t)nb), dim3(256), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles, mask);
+    else if (tile == 8192) hipLaunchKernelGGL((k_rs_pass_b<K, 512, 16, RB>), dim3(tiles, (uint32_t)nb), dim3(512), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles, mask);
+    else hipLaunchKernelGGL((k_rs_pass_b<K, 512, 32, RB>), dim3(tiles, (uint32_t)nb), dim3(512), 0, stream, B, (uint32_t)cap, (int)begin_bit, p, tiles, mask);
   }
   return hipGetLastError();
 }
