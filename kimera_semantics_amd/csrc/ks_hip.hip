@@ -2570,6 +2570,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
       c->xl_parallel = atoi(xl) != 0;
       if (atoi(xl) == 2) c->xl_min_pairs = 0ull;
     }   // A/B: 0 = every such run through k_apply_xlong
+    // tests: room for this many chunk summaries per frame (k_xl_number hands the runs that do not fit to k_apply_xlong)
+    if (const char* xc = dbg_env("KS_XL_CAP_CHUNKS")) c->cap_xl_chunks = (uint32_t)std::max(1, atoi(xc));
     if (c->stream_xlong && c->xl_parallel) {
       CRKS(c->d_xl_runs.alloc(c, kXlMaxRuns));
       CRKS(c->d_xl_idx.alloc(c, kXlMaxRuns));

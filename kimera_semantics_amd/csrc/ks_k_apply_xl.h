@@ -28,7 +28,11 @@
 //
 // Same arithmetic as the reference's sequential loop ([K:src/semantic_integrator_base.cpp:283-380] through k_apply_xlong):
 // the records are identical bit for bit — tests/test_apply_runs_gpu.py, tests/test_emu_parity.py, and the full-size frames
-// against the real sources.
+// against the real sources.  The edges of the shortcut — rounding ties, runs that leave the eight binades or exceed the replay
+// budget, the weight meeting its clamp inside a chunk, an update that moves the distance, runs of exactly 1025 updates, start
+// states k_xl_measure must refuse, two runs in one frame — are stated one by one in tests/xl_case.py (hand-built clouds, each
+// with its precondition proved by the plain model tests/xl_model.py) and run by tests/test_xl_cpu.py on the functional
+// model and by tests/test_xl_gpu.py on the device (the only direct check of wave_sum_i32_dpp: its merged_lanes_* cases).
 #pragma once
 #include "ks_k_apply.h"
 

@@ -1552,6 +1552,21 @@ int ko_get_block(ko_ctx* ctx, const int32_t idx[3], void* tsdf_out, void* sem_ou
   return absent;
 }
 
+// The inverse of ko_get_block: the block is created in BOTH layers (as an integration that touches it does); a NULL pointer leaves
+// that layer's voxels as they are (default-constructed in a new block).
+int ko_set_block(ko_ctx* ctx, const int32_t idx[3], const void* tsdf_in, const void* sem_in) {
+  const B3 b = {idx[0], idx[1], idx[2]};
+  const size_t nvox = static_cast<size_t>(ctx->vps) * ctx->vps * ctx->vps;
+  auto& tb = ctx->tsdf_layer.blocks[b];
+  if (!tb) tb = std::make_shared<Block<TsdfVoxel>>(ctx->vps);
+  auto& sb = ctx->semantic_layer.blocks[b];
+  if (!sb) sb = std::make_shared<Block<SemanticVoxel>>(ctx->vps);
+  if (tsdf_in) std::memcpy(tb->voxels.data(), tsdf_in, nvox * sizeof(TsdfVoxel));
+  if (sem_in) std::memcpy(sb->voxels.data(), sem_in, nvox * sizeof(SemanticVoxel));
+  tb->updated = sb->updated = true;
+  return 0;
+}
+
 // ---- pure functions for KATs ----
 void ko_transform_point(const float Tq[7], const float p[3], float out[3]) {
   Transform T;

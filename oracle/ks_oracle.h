@@ -121,6 +121,10 @@ void ko_get_semantic_block_indices(ko_ctx* ctx, int32_t* out_xyz);
  * (outputs then hold default-constructed voxels). */
 int ko_get_block(ko_ctx* ctx, const int32_t idx[3], void* tsdf_out, void* sem_out);
 
+/* The inverse of ko_get_block (same layouts): creates the block in both layers if it is absent; either pointer may
+ * be NULL (that layer's voxels stay as they are, default-constructed in a new block).  Returns 0. */
+int ko_set_block(ko_ctx* ctx, const int32_t idx[3], const void* tsdf_in, const void* sem_in);
+
 /* ---- pure functions exposed for known-answer tests ---- */
 void ko_transform_point(const float T_G_C[7], const float p[3], float out[3]);
 void ko_grid_index_from_point(const float p[3], float grid_size_inv, int64_t out[3]);

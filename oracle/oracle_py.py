@@ -76,6 +76,8 @@ def lib():
         L.ko_get_semantic_block_indices.argtypes = [C.c_void_p, C.c_void_p]
         L.ko_get_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.ko_get_block.restype = C.c_int
+        L.ko_set_block.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.ko_set_block.restype = C.c_int
         L.ko_transform_point.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.ko_grid_index_from_point.argtypes = [C.c_void_p, C.c_float, C.c_void_p]
         L.ko_cast_ray.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_float, C.c_float, C.c_float,
@@ -190,6 +192,17 @@ class Oracle:
             i = np.ascontiguousarray(idx, dtype=np.int32)
             lib().ko_get_block(self._h, _ptr(i), _ptr(t[k]), _ptr(s[k]))
         return indices, t, s
+
+    def upload(self, indices, tsdf=None, sem=None):
+        """Seed / overwrite blocks (inverse of download; the signature of HipIntegrator.upload)."""
+        indices = np.ascontiguousarray(indices, dtype=np.int32).reshape(-1, 3)
+        nv = self.vps ** 3
+        if tsdf is not None:
+            tsdf = np.ascontiguousarray(tsdf, dtype=TSDF_DTYPE).reshape(len(indices), nv)
+        if sem is not None:
+            sem = np.ascontiguousarray(sem, dtype=SEM_DTYPE).reshape(len(indices), nv)
+        for k in range(len(indices)):
+            lib().ko_set_block(self._h, _ptr(indices[k]), None if tsdf is None else _ptr(tsdf[k]), None if sem is None else _ptr(sem[k]))
 
 
 # ---- pure-function helpers for KATs ----

@@ -264,3 +264,55 @@ def test_merged_reference_order_vs_canonical_order_same_sets():
     assert np.all(dp <= 1e-4 * np.abs(sa_["priors"]) + 1e-3)  # f32 summation order only
     mism = (sa_["label"] != sb_["label"]).sum()
     assert mism <= 0.005 * sa_["label"].size  # only exact count-ties may flip
+
+
+# ---- ko_set_block / Oracle.upload: the oracle can be seeded (the inverse of ko_get_block) ----
+def _room_frames(n, w=64, h=48):
+    sc = synth.make_scene("room")
+    return [synth.render_frame(sc, synth.trajectory_pose(5 * k), w, h, seed=40 + k) for k in range(n)]
+
+
+def test_set_block_is_the_inverse_of_get_block():
+    o = O.Oracle(O.default_config(integrator_threads=1, **COMMON))
+    f = _room_frames(1)[0]
+    o.integrate(f.T_G_C, f.xyz, f.rgba, f.labels)
+    idx, t, s = o.download()
+    assert len(idx) > 4 and (t["weight"] > 0).any()
+    fresh = O.Oracle(O.default_config(integrator_threads=1, **COMMON))
+    fresh.upload(idx, t, s)
+    assert fresh.block_indices().tobytes() == idx.tobytes() and fresh.semantic_block_indices().tobytes() == idx.tobytes()
+    _, t2, s2 = fresh.download(idx)
+    assert t2.tobytes() == t.tobytes() and s2.tobytes() == s.tobytes()
+    # either pointer may be missing: the block appears in both layers, the other layer's voxels default-constructed / left alone
+    t_def, s_def, absent = fresh.get_block([99, 99, 99])
+    assert absent
+    half = O.Oracle(O.default_config(integrator_threads=1, **COMMON))
+    half.upload(idx[:1], tsdf=t[:1])
+    ht, hs, absent = half.get_block(idx[0])
+    assert not absent and ht.tobytes() == t[0].tobytes() and hs.tobytes() == s_def.tobytes()
+    assert half.semantic_block_indices().tobytes() == idx[:1].tobytes()
+    half.upload(idx[:1], sem=s[:1])
+    ht, hs, _ = half.get_block(idx[0])
+    assert ht.tobytes() == t[0].tobytes() and hs.tobytes() == s[0].tobytes()
+
+
+@pytest.mark.parametrize("method,kw", [(1, {}), (0, dict(max_consecutive_ray_collisions=1 << 30))])
+def test_an_uploaded_map_continues_like_one_that_never_stopped(method, kw):
+    """Frames 0..1, copied into a fresh oracle through upload, then frame 2: the bytes of an oracle that integrated all three.
+    (`fast` without its early-out: the approximate sets of the early-out are not part of a block.)"""
+    cfg = dict(COMMON, method=method, **kw)
+    frames = _room_frames(3)
+    whole = O.Oracle(O.default_config(integrator_threads=1, **cfg))
+    first = O.Oracle(O.default_config(integrator_threads=1, **cfg))
+    for f in frames[:2]:
+        whole.integrate(f.T_G_C, f.xyz, f.rgba, f.labels)
+        first.integrate(f.T_G_C, f.xyz, f.rgba, f.labels)
+    resumed = O.Oracle(O.default_config(integrator_threads=1, **cfg))
+    resumed.upload(*first.download())
+    for o in (whole, resumed):
+        o.integrate(frames[2].T_G_C, frames[2].xyz, frames[2].rgba, frames[2].labels)
+    idx, t, s = whole.download()
+    idx2, t2, s2 = resumed.download()
+    assert len(idx) > len(first.block_indices()) or (t["weight"] != first.download(idx)[1]["weight"]).any()   # (frame 2 did something)
+    assert idx.tobytes() == idx2.tobytes() and t.tobytes() == t2.tobytes() and s.tobytes() == s2.tobytes()
+    assert resumed.semantic_block_indices().tobytes() == whole.semantic_block_indices().tobytes()
