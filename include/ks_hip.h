@@ -601,6 +601,42 @@ typedef struct ks_fuse_stats {
 } ks_fuse_stats; /* 56 bytes */
 int ks_fuse_default_config(ks_fuse_config* cfg);
 int ks_fuse_map(ks_ctx* dst, ks_ctx* src, const float T_D_S[7], const ks_fuse_config* cfg, ks_fuse_stats* stats /* may be NULL */);
+
+/* ---- indexed view of the stored mesh: shared vertices (new: consumers of the mesh — deformation after a loop closure, objects
+ * as vertex sets, smooth shading, a PLY that is one surface — need connectivity, and had to weld positions on the host) ----
+ * The contract is DESIGN.md §18.  The input is the STORED MESH exactly as ks_mesh_download presents it: C corners (three per
+ * triangle) numbered 0 .. C-1 in that layout, with that block directory.  In short:
+ *   identity   corners i and j are the same vertex iff their three xyz floats are bit-equal (the cubes around an edge compute
+ *              the same bits: no tolerance, no quantisation);
+ *   ORDER      (part of the ABI) vertices ascend by the smallest corner number that references them; indices[i] is the vertex
+ *              of corner i, so indices[0] == 0, every new maximum of indices is the previous one plus one, triangle k is
+ *              indices[3k .. 3k+2], and first_vertex / n_vertices of ks_mesh_download's directory address indices unchanged;
+ *   position, colour, label   those of the vertex's first corner;
+ *   normal     from exact integer sums: N_k = sum over the corners of the vertex of (int32) rint(n_k * 65536.0f) (half to even)
+ *              of their triangles' stored normals; s = (float) N; len = sqrtf((s_x*s_x + s_y*s_y) + s_z*s_z); s / len, or
+ *              (0, 0, 0) if len is 0.  Nothing depends on the order of the additions;
+ *   object id  what ks_objects_query returns for the vertex position, read when the index is built; KS_OBJECT_NONE everywhere
+ *              if no objects are stored (no error).
+ * Two calls on the same stored mesh give the same bytes.  The index is a SNAPSHOT of the stored mesh at the call: a later
+ * ks_mesh_update (successful or not), ks_clear or ks_clear_voxels drops it; ks_remove_blocks* and ks_fuse_map leave it, as they
+ * leave the stored mesh, until the next ks_mesh_update.  It is not incremental: its cost follows the corners of the stored mesh,
+ * not the map.  The call reads only: the map, its flags, the stored mesh, ESDF and objects stay as they were.  It completes
+ * the frames in flight first (their statistics stay owed).
+ * ks_mesh_index           builds the index on the device.  stats (zeroed first): corners, vertices, the most corners on one
+ *                         vertex, the bytes of work space and outputs in use.  A stored mesh of no triangle is no error.
+ * ks_mesh_index_size      V and C of the current index.
+ * ks_mesh_index_download  per vertex xyz and normals (3 floats), rgba (4 bytes), labels (1 byte), object_ids (u32); per corner
+ *                         indices (u32).  Any output may be NULL.  The block directory is the one of ks_mesh_download.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx; no stored mesh; size or download without a current index; a capacity that is too small;
+ * a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact), KS_ERR_HIP (no index stays
+ * stored). */
+typedef struct ks_mesh_index_stats {
+  uint64_t corners, vertices, max_corners_per_vertex, workspace_bytes;
+} ks_mesh_index_stats; /* 32 bytes */
+int ks_mesh_index(ks_ctx* ctx, ks_mesh_index_stats* stats /* may be NULL */);
+int ks_mesh_index_size(ks_ctx* ctx, size_t* n_vertices, size_t* n_indices);
+int ks_mesh_index_download(ks_ctx* ctx, float* xyz, float* normals, uint8_t* rgba, uint8_t* labels, uint32_t* object_ids,
+                           size_t cap_vertices, uint32_t* indices, size_t cap_indices);
 /* Resets the tiles at the given slots to the empty state (a rank that has handed tiles to their owner keeps
  * them as empty deltas). */
 int ks_reset_tiles(ks_ctx* ctx, const uint32_t* slots, size_t n);

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "ks_objects_default_config", "ks_objects_update", "ks_objects_size", "ks_objects_download", "ks_objects_download_blocks", "ks_objects_query",
     "ks_remove_blocks", "ks_remove_distant_blocks", "ks_removed_blocks",
     "ks_fuse_default_config", "ks_fuse_map",
+    "ks_mesh_index", "ks_mesh_index_size", "ks_mesh_index_download",
 ]
 
 
@@ -158,6 +159,10 @@ class KsFuseStats(C.Structure):
                 ("voxels_fused", C.c_uint64), ("chunks", C.c_uint64), ("workspace_bytes", C.c_uint64)]
 
 
+class KsMeshIndexStats(C.Structure):
+    _fields_ = [("corners", C.c_uint64), ("vertices", C.c_uint64), ("max_corners_per_vertex", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
 # ks_object: 72 bytes; centroid_k = (sum_k / n_voxels + 0.5) * voxel_size (object_centroids)
 OBJECT_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
                          ("sum", "<i8", (3,)), ("label", "<u4"), ("pad", "<u4")])
@@ -184,7 +189,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -279,6 +284,9 @@ def lib():
         L.ks_removed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ks_fuse_default_config.argtypes = [C.POINTER(KsFuseConfig)]
         L.ks_fuse_map.argtypes = [vp, vp, vp, C.POINTER(KsFuseConfig), C.POINTER(KsFuseStats)]
+        L.ks_mesh_index.argtypes = [vp, C.POINTER(KsMeshIndexStats)]
+        L.ks_mesh_index_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.ks_mesh_index_download.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]
         _lib = L
     return _lib
 
@@ -442,6 +450,27 @@ class HipIntegrator:
         rgba, labels = np.zeros((nv.value, 4), np.uint8), np.zeros(nv.value, np.uint8)
         self._chk(lib().ks_mesh_download(self._h, _ptr(blocks), nb.value, _ptr(xyz), _ptr(normals), _ptr(rgba), _ptr(labels), nv.value))
         return Mesh(blocks, xyz, normals, rgba, labels, {k: int(getattr(st, k)) for k, _ in KsMeshStats._fields_})
+
+    def mesh_index(self, build=True):
+        """Builds the indexed view of the STORED mesh on the device (ks_mesh_index: shared vertices, a smooth normal and the object
+        id per vertex) and fetches it: kimera_semantics_amd.mesh.IndexedMesh.  mesh() must have run; the index is a snapshot that
+        the next mesh() or clear() drops.  `blocks` is the directory of the stored mesh: first_vertex / n_vertices address `indices`.
+        build=False fetches the index that is stored (stats all zero)."""
+        from .mesh import IndexedMesh
+        st = KsMeshIndexStats()
+        if build:
+            self._chk(lib().ks_mesh_index(self._h, C.byref(st)))
+        nv, ni, nb, nc = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        self._chk(lib().ks_mesh_index_size(self._h, C.byref(nv), C.byref(ni)))
+        self._chk(lib().ks_mesh_size(self._h, C.byref(nb), C.byref(nc)))
+        blocks = np.zeros(nb.value, dtype=MESH_BLOCK_DTYPE)
+        self._chk(lib().ks_mesh_download(self._h, _ptr(blocks), nb.value, None, None, None, None, 0))
+        xyz, normals = np.zeros((nv.value, 3), np.float32), np.zeros((nv.value, 3), np.float32)
+        rgba, labels = np.zeros((nv.value, 4), np.uint8), np.zeros(nv.value, np.uint8)
+        object_ids, indices = np.zeros(nv.value, np.uint32), np.zeros(ni.value, np.uint32)
+        self._chk(lib().ks_mesh_index_download(self._h, _ptr(xyz), _ptr(normals), _ptr(rgba), _ptr(labels), _ptr(object_ids), nv.value,
+                                               _ptr(indices), ni.value))
+        return IndexedMesh(blocks, xyz, normals, rgba, labels, object_ids, indices, {k: int(getattr(st, k)) for k, _ in KsMeshIndexStats._fields_})
 
     def mesh_changed_blocks(self) -> np.ndarray:
         """Blocks whose segment the last mesh() replaced (including ones that are empty now), ascending."""

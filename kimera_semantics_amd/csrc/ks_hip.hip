@@ -67,6 +67,7 @@ using namespace ksd;
 #include "ks_k_shard_merged.h"
 #include "ks_k_io.h"
 #include "ks_k_mesh.h"
+#include "ks_k_mesh_index.h"
 #include "ks_k_esdf.h"
 #include "ks_k_render.h"
 #include "ks_k_align.h"
@@ -488,6 +489,17 @@ struct ks_ctx {
   std::vector<ks_mesh_block> mesh_dir;     // one entry per element of mesh_blocks as of the last update (n_vertices may be 0)
   std::vector<int32_t> mesh_changed;       // blocks whose segment the last update replaced
   DevBuf<uint8_t> d_mesh_buf[10];          // grow-only scratch of the passes (mesh_scratch)
+  // ks_mesh_index (ks_k_mesh_index.h): the indexed view of the stored mesh, a snapshot that the next ks_mesh_update or clear drops.
+  // Work space and outputs follow the corner count of the stored mesh (grow-only), never the map.
+  DevBuf<uint32_t> mi_key32[2], mi_val[2]; // sort 1 (z) and the payloads; afterwards run numbers | corner flags, and the first corners
+  DevBuf<uint64_t> mi_key64[2];            // sort 2 (x, y)
+  DevBuf<uint32_t> mi_partial, mi_counts;  // the scans' slice sums; {vertices, largest valence, runs}
+  DevBuf<float> mi_xyz, mi_nrm;            // the indexed mesh: per vertex ...
+  DevBuf<uint32_t> mi_rgba, mi_obj, mi_valence;
+  DevBuf<uint8_t> mi_label;
+  DevBuf<uint32_t> mi_indices;             // ... and per corner
+  bool mi_valid = false;
+  size_t mi_corners = 0, mi_vertices = 0;
   // ks_esdf_update / ks_esdf_refresh (ks_k_esdf.h).  The store holds 512 records per tile slot: the ESDF of the map as it
   // was at the last update or refresh; the buffers grow only.  A removal moves the records with their tiles and lowers
   // esdf_tiles to the new tile count (remove_tiles).
@@ -3002,6 +3014,7 @@ int ks_mesh_default_config(ks_mesh_config* m) {
 
 int ks_mesh_update(ks_ctx* c, const ks_mesh_config* m, ks_mesh_stats* stats) {
   if (!c || !m) return KS_ERR_INVALID_ARG;
+  c->mi_valid = false;   // the indexed view is a snapshot of the mesh this call replaces (rule 7)
   if (stats) std::memset(stats, 0, sizeof(*stats));
   if (!(m->min_weight > 0.0f) || !std::isfinite(m->min_weight)) {
     c->err = "ks_mesh_update: min_weight must be a finite positive number";
@@ -3164,6 +3177,142 @@ int ks_mesh_download(ks_ctx* c, ks_mesh_block* blocks, size_t cap_blocks, float*
 
 int ks_mesh_changed_blocks(ks_ctx* c, int32_t* out_xyz, size_t cap, size_t* n) {
   return c ? copy_block_list(c, "ks_mesh_changed_blocks", c->mesh_changed, out_xyz, cap, n) : KS_ERR_INVALID_ARG;
+}
+
+// ---- indexed view of the stored mesh (ks_k_mesh_index.h) ------------------------------------
+// inclusive scan of n words in place; the total -> *total
+static void mi_scan(ks_ctx* c, uint32_t* v, uint32_t n, uint32_t* total) {
+  const uint32_t nb = (n + kMiSlice - 1) / kMiSlice;
+  hipLaunchKernelGGL(k_mi_scan_partial, dim3(nb), dim3(256), 0, c->stream, (const uint32_t*)v, n, c->mi_partial.get());
+  hipLaunchKernelGGL(k_mi_scan_top, dim3(1), dim3(1024), 0, c->stream, c->mi_partial.get(), nb, total);
+  hipLaunchKernelGGL(k_mi_scan_apply, dim3(nb), dim3(256), 0, c->stream, v, n, (const uint32_t*)c->mi_partial.get());
+}
+static int mesh_index_ready(ks_ctx* c, const char* who) {
+  if (int rc = holds_voxels(c, who)) return rc;
+  if (c->fatal) {
+    c->err = std::string(who) + ": context is in a failed state (earlier pool/index error)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (c->mi_valid) return KS_OK;
+  c->err = std::string(who) + ": no index is stored (ks_mesh_index has not run since the last ks_mesh_update or clear)";
+  return KS_ERR_INVALID_ARG;
+}
+
+int ks_mesh_index(ks_ctx* c, ks_mesh_index_stats* stats) {
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = holds_voxels(c, "ks_mesh_index")) return rc;
+  if (c->fatal) {
+    c->err = "ks_mesh_index: context is in a failed state (earlier pool/index error)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (int rc = quiesce(c)) return rc;   // (the frames in flight; their statistics stay owed)
+  if (!c->mesh_valid) {
+    c->err = "ks_mesh_index: no mesh is stored (ks_mesh_update has not succeeded since the map was created or cleared)";
+    return KS_ERR_INVALID_ARG;
+  }
+  c->mi_valid = false;   // (a failure below leaves no index)
+  size_t nc = 0;
+  ks_mesh_size(c, nullptr, &nc);
+  if (nc >= ((size_t)1 << 31)) {
+    c->err = "ks_mesh_index: too many corners for one call";
+    return KS_ERR_UNSUPPORTED;
+  }
+  uint32_t counts[2] = {0, 0};
+  uint64_t workspace = 0;
+  if (nc) {
+    const uint32_t n = (uint32_t)nc;
+    const size_t cap = std::max<size_t>(nc + nc / 2, 256), nb = (nc + kMiSlice - 1) / kMiSlice;
+    int rc;
+    for (int k = 0; k < 2; ++k)
+      if ((rc = c->mi_key32[k].reserve(c, nc, cap)) || (rc = c->mi_val[k].reserve(c, nc, cap)) || (rc = c->mi_key64[k].reserve(c, nc, cap))) return rc;
+    if ((rc = c->mi_partial.reserve(c, nb, nb + nb / 2 + 16)) || (rc = c->mi_counts.reserve(c, 4, 4)) || (rc = c->mi_xyz.reserve(c, 3 * nc, 3 * cap)) ||
+        (rc = c->mi_nrm.reserve(c, 3 * nc, 3 * cap)) || (rc = c->mi_rgba.reserve(c, nc, cap)) || (rc = c->mi_obj.reserve(c, nc, cap)) ||
+        (rc = c->mi_valence.reserve(c, nc, cap)) || (rc = c->mi_label.reserve(c, nc, cap)) || (rc = c->mi_indices.reserve(c, nc, cap)))
+      return rc;
+    workspace = (uint64_t)nc * (2 * 4 + 2 * 4 + 2 * 8 + 12 + 12 + 4 + 4 + 4 + 1 + 4) + (uint64_t)nb * 4 + 16;
+    hipStream_t st = c->stream;
+    const MeshArena& A = c->mesh_arena[c->mesh_cur];
+    const dim3 per_corner((n + 255u) / 256u);
+    // 1) the corners grouped by position: stable sorts on the bits of z, then of (x, y)
+    hipLaunchKernelGGL(k_mi_keys_z, per_corner, dim3(256), 0, st, (const float*)A.xyz, n, c->mi_key32[0].get(), c->mi_val[0].get());
+    uint32_t* k32 = nullptr;
+    uint32_t* perm = nullptr;
+    if ((rc = sort_pairs(c, c->mi_key32[0].get(), c->mi_key32[1].get(), c->mi_val[0].get(), c->mi_val[1].get(), nc, 32, &k32, &perm))) return rc;
+    hipLaunchKernelGGL(k_mi_keys_xy, per_corner, dim3(256), 0, st, (const float*)A.xyz, (const uint32_t*)perm, n, c->mi_key64[0].get());
+    uint64_t* k64 = nullptr;
+    uint32_t* other = perm == c->mi_val[0].get() ? c->mi_val[1].get() : c->mi_val[0].get();
+    if ((rc = sort_pairs(c, c->mi_key64[0].get(), c->mi_key64[1].get(), perm, other, nc, 64, &k64, &perm))) return rc;
+    // (the 32-bit key buffers and the payload buffer the result is not in are free from here on)
+    uint32_t* run = c->mi_key32[0].get();
+    uint32_t* vertex_of = c->mi_key32[1].get();
+    uint32_t* first_corner = perm == c->mi_val[0].get() ? c->mi_val[1].get() : c->mi_val[0].get();
+    uint32_t* d_counts = c->mi_counts.get();
+    HIPCHK(c, hipMemsetAsync(d_counts, 0, 16, st));
+    HIPCHK(c, hipMemsetAsync(vertex_of, 0, nc * 4, st));
+    HIPCHK(c, hipMemsetAsync(c->mi_nrm, 0, nc * 12, st));
+    HIPCHK(c, hipMemsetAsync(c->mi_valence, 0, nc * 4, st));
+    // 2) runs of equal positions, their first corners, the vertex numbers in corner order
+    hipLaunchKernelGGL(k_mi_heads, per_corner, dim3(256), 0, st, (const float*)A.xyz, (const uint32_t*)perm, n, run);
+    mi_scan(c, run, n, d_counts + 2);
+    hipLaunchKernelGGL(k_mi_first, per_corner, dim3(256), 0, st, (const uint32_t*)perm, (const uint32_t*)run, n, first_corner, vertex_of);
+    mi_scan(c, vertex_of, n, d_counts);
+    // 3) indices, attributes, normal sums; normals
+    MeshIndexOut O{c->mi_xyz, c->mi_nrm, c->mi_rgba, c->mi_label, c->mi_indices, c->mi_valence};
+    hipLaunchKernelGGL(k_mi_emit, per_corner, dim3(256), 0, st, A, (const uint32_t*)perm, (const uint32_t*)run, (const uint32_t*)first_corner,
+                       (const uint32_t*)vertex_of, n, O);
+    hipLaunchKernelGGL(k_mi_finish, per_corner, dim3(256), 0, st, O, d_counts);
+    HIPCHK(c, hipMemcpyAsync(counts, d_counts, sizeof(counts), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the one read-back: vertices, largest valence
+    // 4) the object of every vertex, as ks_objects_query answers for its position
+    if (c->obj_valid) {
+      hipLaunchKernelGGL(k_obj_query, dim3((counts[0] + 255u) / 256u), dim3(256), 0, st, c->table, (const uint32_t*)c->obj_ids.get(), c->obj_tiles,
+                         (const float*)c->mi_xyz.get(), (size_t)counts[0], c->voxel_size_inv, c->mi_obj.get());
+    } else {
+      HIPCHK(c, hipMemsetAsync(c->mi_obj, 0xff, (size_t)counts[0] * 4, st));
+    }
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+  }
+  c->mi_corners = nc;
+  c->mi_vertices = counts[0];
+  c->mi_valid = true;
+  if (stats) {
+    stats->corners = nc;
+    stats->vertices = counts[0];
+    stats->max_corners_per_vertex = counts[1];
+    stats->workspace_bytes = workspace;
+  }
+  return KS_OK;
+}
+
+int ks_mesh_index_size(ks_ctx* c, size_t* n_vertices, size_t* n_indices) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = mesh_index_ready(c, "ks_mesh_index_size")) return rc;
+  if (n_vertices) *n_vertices = c->mi_vertices;
+  if (n_indices) *n_indices = c->mi_corners;
+  return KS_OK;
+}
+
+int ks_mesh_index_download(ks_ctx* c, float* xyz, float* normals, uint8_t* rgba, uint8_t* labels, uint32_t* object_ids, size_t cap_vertices,
+                           uint32_t* indices, size_t cap_indices) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = mesh_index_ready(c, "ks_mesh_index_download")) return rc;
+  const size_t nv = c->mi_vertices, nc = c->mi_corners;
+  if (((xyz || normals || rgba || labels || object_ids) && cap_vertices < nv) || (indices && cap_indices < nc)) {
+    c->err = "ks_mesh_index_download: output buffer too small (call ks_mesh_index_size first)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (nc == 0) return KS_OK;
+  hipStream_t st = c->stream;
+  if (xyz) HIPCHK(c, hipMemcpyAsync(xyz, c->mi_xyz, nv * 12, hipMemcpyDeviceToHost, st));
+  if (normals) HIPCHK(c, hipMemcpyAsync(normals, c->mi_nrm, nv * 12, hipMemcpyDeviceToHost, st));
+  if (rgba) HIPCHK(c, hipMemcpyAsync(rgba, c->mi_rgba, nv * 4, hipMemcpyDeviceToHost, st));
+  if (labels) HIPCHK(c, hipMemcpyAsync(labels, c->mi_label, nv, hipMemcpyDeviceToHost, st));
+  if (object_ids) HIPCHK(c, hipMemcpyAsync(object_ids, c->mi_obj, nv * 4, hipMemcpyDeviceToHost, st));
+  if (indices) HIPCHK(c, hipMemcpyAsync(indices, c->mi_indices, nc * 4, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  return KS_OK;
 }
 
 // ---- batch ESDF (ks_k_esdf.h) ----------------------------------------------------------------------------
@@ -4671,6 +4820,7 @@ int ks_integrate_round_exact(ks_ctx* m, ks_ctx* o, void* rccl_comm, int rank, in
 // entered its marks); without it a frame that was never applied is dropped with the map.
 static void mesh_reset(ks_ctx* c) {
   c->mesh_valid = false;
+  c->mi_valid = false;     // (the indexed view of the mesh)
   c->mesh_blocks.clear();
   c->mesh_dir.clear();
   c->mesh_changed.clear();

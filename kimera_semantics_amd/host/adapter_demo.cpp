@@ -254,6 +254,32 @@ int main(int argc, char** argv) {
     std::printf("adapter_demo: updateMesh %.3f ms, %u blocks, %zu triangles\n", ms, n_mesh_blocks, n_vertices / 3);
   }
 
+  // KS_DEMO_MESH_INDEXED=<file>: that mesh with shared vertices (indexMesh, no layer sync either), written as
+  // { u32 vertices, u32 indices; V x Point vertices, V x Point normals, V x Color, V x u8 label, V x u32 object id, C x u32 index }
+  if (const char* indexed_path = std::getenv("KS_DEMO_MESH_INDEXED")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    std::vector<kimera::HipSemanticTsdfIntegrator::MeshBlock> changed;
+    hip->updateMesh(true, &changed);   // (brings the stored mesh up to date: everything, if KS_DEMO_MESH has not made it)
+    kimera::HipSemanticTsdfIntegrator::IndexedMesh im;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->indexMesh(&im);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* mf = std::fopen(indexed_path, "wb");
+    if (!mf) return 9;
+    const uint32_t counts[2] = {(uint32_t)im.vertices.size(), (uint32_t)im.indices.size()};
+    std::fwrite(counts, 4, 2, mf);
+    std::fwrite(im.vertices.data(), sizeof(vxb::Point), counts[0], mf);
+    std::fwrite(im.normals.data(), sizeof(vxb::Point), counts[0], mf);
+    std::fwrite(im.colors.data(), sizeof(vxb::Color), counts[0], mf);
+    std::fwrite(im.labels.data(), 1, counts[0], mf);
+    std::fwrite(im.object_ids.data(), 4, counts[0], mf);
+    std::fwrite(im.indices.data(), 4, counts[1], mf);
+    std::fclose(mf);
+    std::printf("adapter_demo: indexMesh %.3f ms, %u vertices for %u corners in %zu blocks, at most %llu corners on a vertex\n", ms, counts[0],
+                counts[1], im.blocks.size(), (unsigned long long)im.stats.max_corners_per_vertex);
+  }
+
   // KS_DEMO_ESDF=<file>: the batch ESDF with nearest-surface labels, made on the device without any layer sync (updateEsdf,
   // min_distance_m 0.1, max_distance_m 0.4), written as
   // { u32 blocks, u32 voxels_per_side; per block: i32 index[3], vps^3 x { f32 distance, u8 flags, u8 nearest_label, u8 pad[2] } }

@@ -314,6 +314,29 @@ bool HipSemanticTsdfIntegrator::updateMesh(bool only_mesh_updated_blocks, std::v
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::indexMesh(IndexedMesh* out) {
+  CHECK_NOTNULL(out);
+  *out = IndexedMesh();
+  check(ks_mesh_index(ctx_, &out->stats), "ks_mesh_index");
+  size_t n_vertices = 0, n_indices = 0, n_blocks = 0;
+  check(ks_mesh_index_size(ctx_, &n_vertices, &n_indices), "ks_mesh_index_size");
+  check(ks_mesh_size(ctx_, &n_blocks, nullptr), "ks_mesh_size");
+  static_assert(sizeof(vxb::Point) == 12 && sizeof(vxb::Color) == 4, "mesh element layout");
+  out->blocks.resize(n_blocks);
+  check(ks_mesh_download(ctx_, out->blocks.data(), n_blocks, nullptr, nullptr, nullptr, nullptr, 0), "ks_mesh_download");
+  out->vertices.resize(n_vertices);
+  out->normals.resize(n_vertices);
+  out->colors.resize(n_vertices);
+  out->labels.resize(n_vertices);
+  out->object_ids.resize(n_vertices);
+  out->indices.resize(n_indices);
+  check(ks_mesh_index_download(ctx_, reinterpret_cast<float*>(out->vertices.data()), reinterpret_cast<float*>(out->normals.data()),
+                               reinterpret_cast<uint8_t*>(out->colors.data()), out->labels.data(), out->object_ids.data(), n_vertices,
+                               out->indices.data(), n_indices),
+        "ks_mesh_index_download");
+  return n_indices != 0;
+}
+
 bool HipSemanticTsdfIntegrator::updateEsdf(const EsdfOptions& options, std::vector<EsdfBlock>* out) {
   CHECK_NOTNULL(out);
   out->clear();

@@ -130,6 +130,24 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   bool updateMesh(bool only_mesh_updated_blocks, std::vector<MeshBlock>* changed);
   const ks_mesh_stats& lastMeshStats() const { return last_mesh_stats_; }
 
+  /// The mesh updateMesh() left on the device with SHARED vertices (ks_mesh_index; the contract is DESIGN.md §18): what a consumer
+  /// that needs connectivity takes instead of welding positions — mesh deformation after a loop closure, objects as vertex
+  /// sets, smooth shading.  Vertices ascend by the first corner that references them; triangle k is indices[3k .. 3k+2];
+  /// `blocks` is the directory of the stored mesh (first_vertex / n_vertices address `indices`); object_ids are
+  /// KS_OBJECT_NONE unless updateObjects() has run.
+  struct IndexedMesh {
+    std::vector<vxb::Point> vertices, normals;
+    std::vector<vxb::Color> colors;
+    std::vector<uint8_t> labels;
+    std::vector<uint32_t> object_ids, indices;
+    std::vector<ks_mesh_block> blocks;
+    ks_mesh_index_stats stats{};
+  };
+  /// Builds the index of the STORED mesh on the device and fetches it.  Needs no syncLayers() and no mesh update of its own:
+  /// call updateMesh() first (it throws where no mesh is stored).  Not incremental: the cost follows the triangles of the
+  /// stored mesh.  Returns true when the mesh has a triangle.
+  bool indexMesh(IndexedMesh* out);
+
   /// Batch ESDF with nearest-surface labels (ks_esdf_update; the contract is DESIGN.md, "ESDF") in this adapter's own types:
   /// there is no Voxblox EsdfVoxel behind it and no parity with vxb::EsdfIntegrator is claimed.  Defaults as
   /// vxb::EsdfIntegrator::Config.  With use_region only the blocks region_min .. region_max (inclusive) get results.

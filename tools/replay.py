@@ -14,7 +14,7 @@ map around the sensor position after every frame (ks_remove_distant_blocks: what
 max_block_distance_from_body; completes the frames in flight), so that a long replay runs in a bounded pool; --submap-frames N
 maps like a submap mapper: every N frames go into a second context in the frame of their first camera pose, which is then fused
 into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and merged) and cleared; map saving stays on the host side of the drop-in boundary (out of scope).
-  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
+  python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
       [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
@@ -47,6 +47,8 @@ def main():
     ap.add_argument("--voxel-size", type=float, default=0.05)
     ap.add_argument("--pipeline-frames", type=int, default=4)
     ap.add_argument("--mesh", metavar="OUT.ply", help="extract the semantic mesh at the end of the replay and write it (binary PLY with a label property)")
+    ap.add_argument("--mesh-indexed", metavar="OUT.ply", help="write the mesh with SHARED vertices (ks_mesh_index on the stored mesh: faces reference the "
+                    "vertices, smooth normals, label and object_id vertex properties; object ids where --objects has made objects)")
     ap.add_argument("--mesh-every", type=int, default=0, metavar="N", help="refresh the mesh on the device (only_stale) every N frames")
     ap.add_argument("--esdf", metavar="OUT.npz", help="compute the batch ESDF with nearest-surface labels at the end of the replay and write it "
                     "(block_indices (N, 3), distance / flags / label (N, vps^3) in host block layout, voxel_size, voxels_per_side)")
@@ -252,6 +254,16 @@ def main():
         print(f"objects: {st['objects']} objects of {st['components']} components over {st['voxels_surface']} surface voxels "
               f"({st['voxels_in_objects']} in objects, the largest {st['largest_object_voxels']}), labels {sorted(set(rec['label'].tolist()))}, "
               f"work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_obj * 1e3:.2f} ms (update + download) -> {a.objects}")
+    if a.mesh_indexed:   # (after --objects, so that the vertices carry their ids)
+        from kimera_semantics_amd.mesh import write_ply
+        integ.mesh(only_stale=True)        # the stored mesh up to date (everything, if nothing has meshed yet)
+        t1 = time.perf_counter()
+        im = integ.mesh_index()
+        t_index = time.perf_counter() - t1
+        write_ply(a.mesh_indexed, im)
+        print(f"indexed mesh: {im.n_vertices} vertices for {im.stats['corners']} corners ({im.n_triangles} triangles), at most "
+              f"{im.stats['max_corners_per_vertex']} corners on a vertex, {int((im.object_ids != B.KS_OBJECT_NONE).sum())} vertices in objects, "
+              f"{t_index * 1e3:.2f} ms (index + download) -> {a.mesh_indexed}")
 
 
 if __name__ == "__main__":
