@@ -753,6 +753,19 @@ int ks_pipeline_shape(ks_ctx* ctx, int32_t out[4]);
  * the context would otherwise need more streams than the budget — below a budget of 8: from there on every context has the
  * layout it always had.  The map is the same for every plan. */
 int ks_stream_plan(ks_ctx* ctx, int32_t out[8]);
+/* The tail of a pipelined `fast` context.  Stage B goes out per batch of frames (ks_pipeline_shape's out[2]);
+ * where every frame of a batch is one the tail would simply sort and apply, the batch's updates are sorted and applied in ONE
+ * pass at the tail of its first frame — every voxel in (frame, integration position) order: the same map, the same
+ * ks_frame_stats at every call.  Since the context was created: out[0] = batches applied in one pass, out[1] = frames in them,
+ * out[2] = batches whose frames' tails ran one by one instead (a frame with an error, a fix point that fell back, pairs that
+ * did not fit, a frame large enough for k_apply_runs, the stage profile, KS_DEBUG=1 KS_TAIL_BATCH=0), out[3] = updates applied by
+ * the passes of out[0].  Batches of one frame and contexts whose pair keys carry no frame index count nowhere. */
+int ks_tail_batch_stats(ks_ctx* ctx, uint64_t out[4]);
+/* Diagnostics (host arithmetic, no device involved): the rule behind out[0] / out[2] above for a batch of nb frames whose
+ * snapshots hold the error bits err[k] and the update counts n_pairs[k], in a context that is (not) a marcher of
+ * ks_integrate_round_exact, at that profiling level, with k_apply_runs from apply_runs_min_pairs updates per frame on.
+ * Returns 1 (one pass), 0 (frame by frame) or KS_ERR_INVALID_ARG. */
+int ks_tail_batch_rule(const uint32_t* err, const uint64_t* n_pairs, int32_t nb, int32_t marcher, int32_t profiling, uint64_t apply_runs_min_pairs);
 /* Diagnostics (host arithmetic, no device involved): the launch shape of the early-out's ordered phases for a context whose
  * frame slots hold cap_points points, integration_order_mode and early_out_phase_growth (16..4096) as in ks_config.  Per phase
  * j < max_phases: out[3 j] and out[3 j + 1] = its generations [g0, g1), out[3 j + 2] = wavefronts launched per frame = the most

@@ -37,7 +37,7 @@ ABI_SYMBOLS = [
     "ks_integrate_points", "ks_integrate_points_device", "ks_integrate_depth", "ks_integrate_depth_device", "ks_num_blocks", "ks_get_block_indices",
     "ks_get_updated_block_indices", "ks_count_updated_voxels", "ks_download_updated_voxels", "ks_download_blocks", "ks_upload_blocks", "ks_host_alloc", "ks_host_free", "ks_get_tile_keys", "ks_export_tiles_device", "ks_merge_tiles_device", "ks_clear", "ks_clear_voxels", "ks_reset_tiles", "ks_tile_owner", "ks_reduce",
     "ks_debug_radix_sort", "ks_debug_radix_sort_range", "ks_debug_radix_sort_batch", "ks_synchronize", "ks_flush", "ks_stream",
-    "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
+    "ks_profile_enable", "ks_profile_get", "ks_early_out_iterations", "ks_early_out_stats", "ks_pipeline_shape", "ks_stream_plan", "ks_tail_batch_stats", "ks_tail_batch_rule", "ks_seed_launch_shape", "ks_update_stats", "ks_integrate_round_exact",
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
     "ks_esdf_refresh", "ks_esdf_changed_blocks",
@@ -253,6 +253,8 @@ def lib():
         L.ks_early_out_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ks_pipeline_shape.argtypes = [vp, C.POINTER(C.c_int32)]
         L.ks_stream_plan.argtypes = [vp, C.POINTER(C.c_int32)]
+        L.ks_tail_batch_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
+        L.ks_tail_batch_rule.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_int32, C.c_int32, C.c_int32, C.c_uint64]
         L.ks_seed_launch_shape.argtypes = [C.c_int32, C.c_int32, C.c_uint64, C.POINTER(C.c_uint32), C.c_int32]
         L.ks_update_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
         L.ks_integrate_round_exact.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_uint64, vp, vp, vp, vp, C.c_size_t, C.c_int, C.POINTER(KsRoundStats)]
@@ -841,6 +843,13 @@ class HipIntegrator:
         side = {1: "own", 0: "tail", -1: "none"}
         return dict(budget=int(out[0]), streams=int(out[1]), march_streams=int(out[2]), long=side[int(out[3])], xlong=side[int(out[4])],
                     march="own" if out[5] else "A", tail="own" if out[6] else "A", streams_held=int(out[7]))
+
+    def tail_batch_stats(self):
+        """dict(batches, frames, per_frame_batches, pairs): batches of frames whose tail ran as one pass, the frames in them, batches
+        whose frames' tails ran one by one, updates applied by the passes (ks_tail_batch_stats)."""
+        out = (C.c_uint64 * 4)()
+        self._chk(lib().ks_tail_batch_stats(self._h, out))
+        return dict(batches=int(out[0]), frames=int(out[1]), per_frame_batches=int(out[2]), pairs=int(out[3]))
 
     def early_out_iterations(self):
         """(frames, fix-point iterations) of a KS_EARLY_OUT_EXACT context."""

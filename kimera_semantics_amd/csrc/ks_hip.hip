@@ -178,6 +178,11 @@ struct FrameSlot {
   bool tail_recorded = false;
   bool join_recorded = false;
   bool b_launched = false;    // stage B of the frame has been enqueued (with its batch)
+  // the batch the frame's stage B went out with (launch_batch): its index in it, the batch's size and slots in frame order
+  int batch_index = 0, batch_nb = 1;
+  FrameSlot* batch_slots[kBatchMax] = {};
+  bool tail_batched = false;  // the frame's updates were applied with its whole batch's, at the tail of the batch's first frame (tail_batch)
+  uint32_t tb_blocks = 0;     // ... and the tiles that tail made valid on this frame's account (ks_frame_stats::n_blocks_allocated)
   size_t steps_max = 0;       // longest possible ray of the frame, in voxels
   uint64_t frame_no = 0;      // the frame the slot holds
   FrameParams F{};
@@ -197,6 +202,7 @@ struct ProfSet {
   Event k0, k1;  // begin/end of the k_apply dispatch itself
   bool used = false, complete = false, stages = false, apply = false, applied = false;
   uint64_t n_pairs = 0, n_points = 0;
+  uint64_t n_applied = 0;   // updates the timed k_apply launch applied: the frame's, or its whole batch's (tail_batch)
 };
 
 // ---- the stream plan: which chain of a frame runs on which stream -------------------------------------------------------
@@ -360,6 +366,14 @@ struct ks_ctx {
   DevBuf<uint32_t> d_okeys, d_okeys2, d_ovals;
   size_t cap_pairs = 0;
   DevBuf<uint64_t> d_pairs2_[2];
+  // the tail of a whole batch in one pass (tail_batch): the batch's pair lists one behind the other (the sort's input) and its
+  // frame table, by parity like the sets above
+  DevBuf<uint64_t> d_pairs_cat_[2];
+  DevBuf<TailFrame> d_tail_frames_[2];
+  size_t cap_cat = 0;
+  int last_par = -1;                     // parity set of the last update enqueued
+  bool tail_batch_on = true;             // KS_DEBUG=1 KS_TAIL_BATCH=0 (tests / A-B): every frame's tail on its own
+  uint64_t tb_stats[4] = {0, 0, 0, 0};   // batches applied in one pass | frames in them | batches that went frame by frame | pairs of the first (ks_tail_batch_stats)
   hipEvent_t pending_join = nullptr;     // (a view: some slot's join) recorded on stream_long; the next k_apply / k_apply_long wait for it
   ksrs::Workspace sort_ws, sort_ws_tail;
   // fast, early-out in the reference's serial order (ks_k_exact.h): marks (two sets for the sort), slot ranges,
@@ -868,6 +882,16 @@ inline unsigned bits_for(uint64_t n) {  // number of bits needed to represent va
   return b;
 }
 
+// Bits of a pair key's sequence field that hold the frame's index in its batch, above the ray sequence (0: this context's
+// keys have none).  `fast` contexts that launch stage B per batch: the tail of such a batch sorts and applies the pairs of all
+// its frames in one pass (tail_batch), and the stable sort, which skips the sequence field, leaves every voxel's updates in
+// (frame, integration position) order.  The field then has the same width for every frame — that of the slot capacity, not of
+// the frame's own point count — and must leave room for the 9 + 23 bits of the largest voxel id under the key's info byte.
+inline unsigned tail_frame_bits(const ks_ctx* c) {
+  if (c->batch <= 1 || c->cfg.method != KS_METHOD_FAST || c->shard_export) return 0u;
+  const unsigned fb = bits_for((uint64_t)c->batch);
+  return bits_for(c->cap_points) + fb + 9u + 23u <= 56u ? fb : 0u;
+}
 int launch_batch(ks_ctx* c);
 int quiesce(ks_ctx* c);
 // ApproxHashSet::resetApproxSet.  `observed`: the early-out set, whose entries carry a frame tag
@@ -936,7 +960,7 @@ void resolve_prof(ks_ctx* c, int set) {
     if (hipEventElapsedTime(&kms, P.k0, P.k1) == hipSuccess) {
       c->prof.apply_kernel_ms += kms;
       c->prof.apply_kernel_launches += 1;
-      c->prof.apply_kernel_updates += P.n_pairs;
+      c->prof.apply_kernel_updates += P.n_applied;
     }
   }
   c->prof.frames += 1;
@@ -1393,6 +1417,11 @@ int launch_batch(ks_ctx* c) {
     FrameSlot& S = *slots[k];
     S.F.observed = observed_table(c, S.frame_no);
     if (c->exact_early_out) S.F.eo_frame = c->eo_frame_no++;
+    if (S.F.frame_bits) S.F.frame_bits = (S.F.frame_bits & 0xffu) | (k << 8);
+    S.batch_index = (int)k;
+    S.batch_nb = (int)nb;
+    for (uint32_t j = 0; j < (uint32_t)kBatchMax; ++j) S.batch_slots[j] = j < nb ? slots[j] : nullptr;
+    S.tail_batched = false;
     PB.F[k] = S.F;
     PB.out[k] = S.d_F;
     V.s[k] = slot_view(S);
@@ -1456,6 +1485,10 @@ void fill_frame_params(ks_ctx* c, FrameParams& F, const float Tq[7], size_t n, i
   F.point_mask = (1u << pb) - 1u;
   F.clear_bit = (cfg.method == KS_METHOD_MERGED) ? (1u << pb) : 0u;
   F.seq_bits = pb + (cfg.method == KS_METHOD_MERGED ? 1u : 0u);
+  if (const unsigned fb = tail_frame_bits(c)) {   // (point_mask stays the frame's own: key & point_mask is the ray sequence on every path)
+    F.frame_bits = bits_for(c->cap_points);   // (the index joins it in launch_batch)
+    F.seq_bits = F.frame_bits + fb;
+  }
   F.inv_order = F.sorted_order ? c->d_inv_order : nullptr;
   std::memcpy(F.dynamic_labels, cfg.dynamic_labels, 32);
   // the early-out can never fire if the threshold exceeds the longest possible ray
@@ -1865,6 +1898,30 @@ struct UpdateLaunch {
     long_runs<MODE>();
   }
 };
+// ... of a whole batch of `fast` frames: the short runs, the xlong runs, the long runs (what differs between the frames comes from `tab`)
+struct BatchUpdateLaunch {
+  ks_ctx* c;
+  const FrameParams& F;
+  hipStream_t st, sl, sx;
+  int set;                  // the profile set whose k0 / k1 time k_apply_batch (-1: none)
+  uint64_t* sp;
+  unsigned long long n_pairs, *d_long_list, *d_xlong_list;
+  const TailFrame* tab;
+  Counters* C;
+  template <int MODE> void launch() const {
+    const uint32_t ab = (uint32_t)((n_pairs + 255) / 256);
+    KS_LAUNCH_TIMED_IF(set >= 0, c->pset[set].k0, c->pset[set].k1, (k_apply_batch<MODE>), dim3(ab), dim3(256), st, F, n_pairs, (const uint64_t*)sp, tab,
+                       c->table, c->pool, (const uint32_t*)c->d_label_lut.get());
+    if (sx) {
+      const uint32_t xb = (uint32_t)std::min<unsigned long long>(n_pairs / kXLongRun + 1, 512);
+      hipLaunchKernelGGL(k_apply_xlong_batch<MODE>, dim3(xb), dim3(256), 0, sx, F, n_pairs, (const uint64_t*)sp, tab, c->table, c->pool,
+                         (const uint32_t*)c->d_label_lut.get(), (const unsigned long long*)d_xlong_list, (const uint32_t*)&C->n_xlong);
+    }
+    const uint32_t lb = (uint32_t)std::min<unsigned long long>(n_pairs / kLongRun + 1, 4096);
+    hipLaunchKernelGGL(k_apply_long_batch<MODE>, dim3(lb), dim3(128), 0, sl, F, n_pairs, (const uint64_t*)sp, tab, c->table, c->pool,
+                       (const uint32_t*)c->d_label_lut.get(), (const unsigned long long*)d_long_list, (const Counters*)C);
+  }
+};
 #undef KS_LAUNCH_TIMED_IF
 // The frame's n_pairs updates into the map: sorted by voxel, then k_apply with the long and xlong runs forked off beside it
 int enqueue_update(ks_ctx* c, FrameSlot& S, hipStream_t st, unsigned long long n_pairs, uint32_t new_tiles, int set) {
@@ -1885,12 +1942,22 @@ int enqueue_update(ks_ctx* c, FrameSlot& S, hipStream_t st, unsigned long long n
   // k_emit wrote the pairs in integration order; the stable sort only groups them by voxel (it skips
   // the sequence bits), so every voxel replays its updates in the reference's single-thread order.
   const int par = (int)(S.frame_no & 1u);
+  // (the update before this one used the same set — a batch's tail, or a frame that was not applied, lies between: its long runs
+  // end before the sort writes into the set)
+  if (par == c->last_par && c->pending_join) {
+    HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
+    c->pending_join = nullptr;
+  }
+  c->last_par = par;
   unsigned long long* const d_long_list = c->d_long_list_[par];
   if ((rc = sort_keys(c, S.d_pairs.get(), c->d_pairs2_[par].get(), n_pairs, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
   stage_mark(c, set, 8);
   const bool by_runs = n_pairs >= c->apply_runs_min_pairs;
   const bool time_apply = set >= 0 && c->pset[set].apply;
-  if (time_apply) c->pset[set].applied = true;
+  if (time_apply) {
+    c->pset[set].applied = true;
+    c->pset[set].n_applied = n_pairs;
+  }
   // long runs (voxels next to the sensor) are listed first; then the two update kernels run side by side:
   // k_apply on the tail stream, k_apply_long on its own stream (disjoint voxels)
   hipStream_t sl = c->stream_long, sx = c->stream_xlong;
@@ -1946,6 +2013,152 @@ int enqueue_update(ks_ctx* c, FrameSlot& S, hipStream_t st, unsigned long long n
   return KS_OK;
 }
 
+// ---- the tail of a whole batch in one pass ----
+// Whether a batch's tail may run as one pass: a pure function of what the frames' snapshots say (ks_tail_batch_rule).  Every
+// frame must be one the per-frame tail would simply sort and apply through k_apply: no error bit (a label out of range, a
+// fix point that fell back, pairs that did not fit: the frame is reported or repaired at its own call), fewer pairs than
+// k_apply_runs and the integer-sum path of the xlong runs start at; not a marcher, not under the stage profile.
+bool tail_batch_rule(const uint32_t* err, const unsigned long long* n_pairs, int nb, bool marcher, int profiling, unsigned long long runs_min_pairs,
+                     unsigned long long xl_min_pairs) {
+  if (nb < 2 || nb > kBatchMax || marcher || profiling == 1) return false;
+  unsigned long long total = 0;
+  for (int k = 0; k < nb; ++k) {
+    if (err[k] || n_pairs[k] >= runs_min_pairs || n_pairs[k] >= xl_min_pairs) return false;
+    total += n_pairs[k];
+  }
+  return total > 0;
+}
+int ensure_tail_batch(ks_ctx* c, size_t n) {
+  int rc;
+  for (int b = 0; b < 2; ++b)
+    if (!c->d_tail_frames_[b] && (rc = c->d_tail_frames_[b].alloc(c, kBatchMax))) return rc;
+  if (n <= c->cap_cat) return KS_OK;
+  const size_t cap = std::max<size_t>(n + n / 4, 1 << 20);
+  c->cap_cat = 0;
+  HIPCHK(c, hipStreamSynchronize(c->stream_long));  // (as ensure_pairs_out: the sorted pairs of the batch before may be in one of them)
+  if (c->stream_xlong) HIPCHK(c, hipStreamSynchronize(c->stream_xlong));
+  if (c->stream_tail) HIPCHK(c, hipStreamSynchronize(c->stream_tail));
+  for (int b = 0; b < 2; ++b)
+    if ((rc = c->d_pairs_cat_[b].alloc(c, cap))) return rc;
+  c->cap_cat = cap;
+  return KS_OK;
+}
+// Called by the tail of a batch's FIRST frame (S0; its snapshot has landed).  Stage B of a batch is one launch sequence and its
+// frames finish together, so the pairs of every frame of the batch are on the device by now.  Where the rule allows it, ONE
+// sort and ONE voxel update take them all: the lists go one behind the other in frame order, the stable sort groups them by
+// voxel and skips the sequence field — ray sequence and, above it, the frame's index — so that every voxel replays its
+// updates in (frame, integration position) order: the record is bit for bit what one pass per frame leaves, and the map is
+// read and written once instead of once per frame.  Each frame's slot is marked (tail_batched); its own frame_tail call then
+// only accounts for it.  Otherwise nothing is done here and every frame's tail runs on its own, as it does without batches.
+int tail_batch(ks_ctx* c, FrameSlot& S0) {
+  const int nb = S0.batch_nb;
+  FrameSlot* const* slots = S0.batch_slots;
+  if (nb < 2 || !S0.F.frame_bits) return KS_OK;   // (nothing to share, or keys without frame bits)
+  int rc;
+  if (!c->tail_batch_on) {
+    c->tb_stats[2] += 1;
+    return KS_OK;
+  }
+  hipStream_t st = c->stream_tail;
+  HIPCHK(c, hipEventSynchronize(slots[nb - 1]->ready));   // (recorded behind the batch's last launch, like every slot's)
+  uint32_t err[kBatchMax];
+  unsigned long long np[kBatchMax], total = 0;
+  bool same_keys = true;
+  for (int k = 0; k < nb; ++k) {
+    err[k] = slots[k]->counters().err;
+    np[k] = slots[k]->counters().n_pairs;
+    total += np[k];
+    same_keys = same_keys && (k == 0 || slots[k]->pending) && slots[k]->F.seq_bits == S0.F.seq_bits && (slots[k]->F.frame_bits & 0xffu) == (S0.F.frame_bits & 0xffu);
+  }
+  if (!same_keys || !tail_batch_rule(err, np, nb, c->shard_export, c->profiling, c->apply_runs_min_pairs,
+                                     c->stream_xlong && c->xl_parallel ? c->xl_min_pairs : ~0ull)) {
+    c->tb_stats[2] += 1;
+    return KS_OK;
+  }
+  // the tiles the batch's fronts allocated: valid before anything is applied; each frame's share as its own tail would count it
+  uint32_t tiles = c->tiles_initialised;
+  for (int k = 0; k < nb; ++k) {
+    const uint32_t nt = std::min(slots[k]->n_tiles(), c->cfg.max_tiles);
+    slots[k]->tb_blocks = nt > tiles ? nt - tiles : 0u;
+    tiles = std::max(tiles, nt);
+  }
+  if (tiles > c->tiles_initialised) {
+    hipLaunchKernelGGL(k_init_tiles, dim3(tiles - c->tiles_initialised), dim3(512), 0, st, c->pool, c->tiles_initialised);
+    c->tiles_initialised = tiles;
+  }
+  if ((rc = ensure_pairs_out(c, total)) || (rc = ensure_tail_batch(c, total))) return rc;
+  const int par = c->last_par == 0 ? 1 : 0;   // the set the update before this one did not use
+  c->last_par = par;
+  const FrameParams& F = S0.F;   // (the configuration: the same for every frame of the batch)
+  TailFrames TF{};
+  PairLists L{};
+  unsigned long long longest = 0;
+  for (int k = 0; k < kBatchMax; ++k) {
+    const FrameSlot& S = *slots[std::min(k, nb - 1)];   // (entries past the batch repeat its last frame: no key names them)
+    TF.f[k].rays = S.d_rays;
+    TF.f[k].t = S.F.T.t;
+    TF.f[k].point_mask = S.F.point_mask;
+    TF.f[k].order_groups = S.F.order_groups;
+    TF.f[k].order_per = S.F.order_per;
+    L.src[k] = S.d_pairs;
+    L.off[k + 1] = L.off[k] + (k < nb ? np[k] : 0ull);
+    longest = std::max(longest, k < nb ? np[k] : 0ull);
+  }
+  TailFrame* const tab = c->d_tail_frames_[par];
+  hipLaunchKernelGGL(k_set_tail_frames, dim3(kBatchMax), dim3(64), 0, st, TF, tab);
+  hipLaunchKernelGGL(k_cat_pairs, dim3((uint32_t)std::min<unsigned long long>((longest + 1023) / 1024, 2048), (uint32_t)nb), dim3(256), 0, st, L,
+                     c->d_pairs_cat_[par].get());
+  const unsigned end_bit = F.seq_bits + 9 + bits_for(tiles);
+  uint64_t* sp = nullptr;
+  if ((rc = sort_keys(c, c->d_pairs_cat_[par].get(), c->d_pairs2_[par].get(), total, std::min(56u, end_bit), &sp, F.seq_bits, /*tail=*/true))) return rc;
+  // from here on as enqueue_update: the long runs listed, then the three kernels side by side where the plan gives them streams
+  hipStream_t sl = c->stream_long, sx = c->stream_xlong;
+  const bool long_beside = sl != st, xlong_beside = sx && sx != st;
+  unsigned long long* const d_long_list = c->d_long_list_[par];
+  unsigned long long* const d_xlong_list = sx ? d_long_list + (c->cap_pairs / kLongRunLanes + 64) : nullptr;
+  const dim3 find_grid((uint32_t)((total + 256 * kFindLongItems - 1) / (256 * kFindLongItems)));
+  hipLaunchKernelGGL(k_find_long, find_grid, dim3(256), 0, st, F.seq_bits, total, (const uint64_t*)sp, d_long_list, d_xlong_list, S0.d_counters, kLongRun);
+  if (c->pending_join) HIPCHK(c, hipStreamWaitEvent(st, c->pending_join, 0));
+  c->pending_join = nullptr;
+  if (long_beside || xlong_beside) HIPCHK(c, hipEventRecord(S0.fork, st));
+  if (long_beside) HIPCHK(c, hipStreamWaitEvent(sl, S0.fork, 0));
+  if (xlong_beside) HIPCHK(c, hipStreamWaitEvent(sx, S0.fork, 0));
+  int timed = -1;   // level-2 profile: the batch's k_apply carries the events of its first frame that is due for them
+  for (int k = 0; k < nb && timed < 0; ++k)
+    if (slots[k]->prof_set >= 0 && c->pset[slots[k]->prof_set].apply) timed = slots[k]->prof_set;
+  if (timed >= 0) {
+    c->pset[timed].applied = true;
+    c->pset[timed].n_applied = total;
+  }
+  const BatchUpdateLaunch U{c, F, st, sl, sx, timed, sp, total, d_long_list, d_xlong_list, tab, S0.d_counters};
+  switch (c->cfg.color_mode) {
+    case KS_COLOR_MODE_COLOR: U.launch<KS_COLOR_MODE_COLOR>(); break;
+    case KS_COLOR_MODE_SEMANTIC: U.launch<KS_COLOR_MODE_SEMANTIC>(); break;
+    default: U.launch<KS_COLOR_MODE_SEMANTIC_PROBABILITY>(); break;
+  }
+  if (xlong_beside) {
+    HIPCHK(c, hipEventRecord(S0.join_x, sx));
+    HIPCHK(c, hipStreamWaitEvent(sl, S0.join_x, 0));
+  }
+  // every slot of the batch is free for stage A once the batch's update has read its rays (and its long runs have ended)
+  for (int k = 0; k < nb; ++k) {
+    FrameSlot& S = *slots[k];
+    if (long_beside) {
+      HIPCHK(c, hipEventRecord(S.join, sl));
+      S.join_recorded = true;
+    }
+    HIPCHK(c, hipEventRecord(S.tail_done, st));
+    S.tail_recorded = true;
+    S.tail_batched = true;
+  }
+  if (long_beside) c->pending_join = S0.join;   // deferred, as in enqueue_update
+  HIPCHK(c, hipGetLastError());
+  c->tb_stats[0] += 1;
+  c->tb_stats[1] += (uint64_t)nb;
+  c->tb_stats[3] += total;
+  return KS_OK;
+}
+
 int frame_tail(ks_ctx* c, FrameSlot& S) {
   if (!S.pending) return KS_OK;
   S.pending = false;
@@ -1958,6 +2171,8 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
   hipStream_t st = c->stream_tail;  // the host wait below orders the tail after the slot's front
   const auto w0 = std::chrono::steady_clock::now();
   HIPCHK(c, hipEventSynchronize(S.ready));  // the frame's only host wait
+  // the first frame of a batch decides for all of them whether the batch's tail is one pass
+  if (S.batch_index == 0 && (rc = tail_batch(c, S))) return rc;
   if (c->profiling) c->prof.host_wait_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - w0).count();
   Counters cnt = S.counters();
   uint32_t new_tiles = std::min(S.n_tiles(), c->cfg.max_tiles);
@@ -1971,6 +2186,14 @@ int frame_tail(ks_ctx* c, FrameSlot& S) {
   }
   if ((cnt.err & kErrExact) && !(cnt.err & (kErrLabel | kErrIndex)) && (rc = repair_after_fallback(c, S, st, &cnt, &new_tiles))) return rc;
   c->pairs_hint.store(std::max<size_t>(c->pairs_hint.load(std::memory_order_relaxed), cnt.n_pairs), std::memory_order_relaxed);
+  if (S.tail_batched) {
+    // applied with its batch (no error bit, tiles valid, events recorded: tail_batch): what is left is the frame's account
+    S.tail_batched = false;
+    skip_update_stages(c, set);
+    finish_prof(c, set, st, cnt.n_pairs);
+    owe_stats(c, S, cnt, cnt.n_pairs, S.tb_blocks);
+    return KS_OK;
+  }
   if ((cnt.err & kErrPairs) && !(cnt.err & ~kErrPairs) && (rc = repair_after_overflow(c, S, st, &cnt, &new_tiles))) return rc;
   // tiles allocated by the front exist in the table whatever happens next: make them valid
   if (new_tiles > c->tiles_initialised) {
@@ -2572,6 +2795,7 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
     if (P.xlong_own) CRKS(new_stream(&c->stream_xlong));
     else if (c->xlong) c->stream_xlong = c->stream_tail;
     if (const char* ar = dbg_env("KS_APPLY_RUNS")) c->apply_runs_min_pairs = atoi(ar) ? 0ull : ~0ull;   // tests / A-B: always / never
+    if (const char* tb = dbg_env("KS_TAIL_BATCH")) c->tail_batch_on = atoi(tb) != 0;   // tests / A-B: 0 = every frame's tail on its own (the same map)
     if (const char* ll = dbg_env("KS_LONG_LANES")) {   // A/B: 0 = k_apply_long (two wavefronts per run) for all of them, 2 = lanes for frames of any size (tests)
       c->long_lanes = atoi(ll) != 0;
       if (atoi(ll) == 2) c->long_lanes_min_pairs = 0ull;
@@ -5325,6 +5549,19 @@ int ks_pipeline_shape(ks_ctx* c, int32_t out[4]) {
   out[2] = c->batch;
   out[3] = c->n_march;
   return KS_OK;
+}
+
+int ks_tail_batch_stats(ks_ctx* c, uint64_t out[4]) {
+  if (!c || !out) return KS_ERR_INVALID_ARG;
+  for (int i = 0; i < 4; ++i) out[i] = c->tb_stats[i];
+  return KS_OK;
+}
+
+int ks_tail_batch_rule(const uint32_t* err, const uint64_t* n_pairs, int32_t nb, int32_t marcher, int32_t profiling, uint64_t apply_runs_min_pairs) {
+  if (!err || !n_pairs || nb < 0 || nb > kBatchMax) return KS_ERR_INVALID_ARG;
+  unsigned long long np[kBatchMax];
+  for (int k = 0; k < nb; ++k) np[k] = n_pairs[k];
+  return tail_batch_rule(err, np, nb, marcher != 0, profiling, apply_runs_min_pairs, ~0ull) ? 1 : 0;
 }
 
 int ks_stream_plan(ks_ctx* c, int32_t out[8]) {

@@ -45,14 +45,25 @@ struct UpdateOps {
 // HOT_ONLY: only the first 16 bytes of the ray descriptor (point_G, weight) are gathered; label /
 // kind / clearing come from the top byte of the pair key, where k_march put them.  That is all the
 // `fast` integrator needs unless colours are blended: one random 16-B gather per update, not two.
-template <bool HOT_ONLY>
+// BATCH: a tail over a batch of frames — the ray descriptors and the sensor origin are those of the frame the key names (`tab`).
+template <bool HOT_ONLY, bool BATCH = false>
 __device__ __forceinline__ UpdateOps load_update_ops(const FrameParams& F, const RayDesc* __restrict__ rays, uint64_t key,
-                                                     const VoxelRef& v) {
+                                                     const VoxelRef& v, const TailFrame* __restrict__ tab = nullptr) {
   UpdateOps u;
-  u.rp = (uint32_t)key & F.point_mask;
-  const uint4* r4 = (const uint4*)rays + (size_t)ray_index(F, u.rp) * 2;
+  const uint4* r4;
+  f3 origin;
+  if constexpr (BATCH) {
+    const TailFrame& f = tail_frame(F, tab, key);
+    u.rp = (uint32_t)key & f.point_mask;
+    r4 = (const uint4*)f.rays + (size_t)tail_ray_index(f, key) * 2;
+    origin = f.t;
+  } else {
+    u.rp = (uint32_t)key & F.point_mask;
+    r4 = (const uint4*)rays + (size_t)ray_index(F, u.rp) * 2;
+    origin = F.T.t;
+  }
   const uint4 d0 = r4[0];
-  tsdf_operands(F.tsdf, F.T.t, {__uint_as_float(d0.x), __uint_as_float(d0.y), __uint_as_float(d0.z)}, v.vx, v.vy, v.vz,
+  tsdf_operands(F.tsdf, origin, {__uint_as_float(d0.x), __uint_as_float(d0.y), __uint_as_float(d0.z)}, v.vx, v.vy, v.vz,
                 __uint_as_float(d0.w), u.sdf, u.uw);
   if (HOT_ONLY) {
     const uint32_t b = (uint32_t)(key >> 56);
@@ -70,14 +81,29 @@ __device__ __forceinline__ UpdateOps load_update_ops(const FrameParams& F, const
   return u;
 }
 
+// the ray descriptor / the sensor origin of the update `key` stands for (BATCH: of its frame of the batch, through `tab`)
+template <bool BATCH>
+__device__ __forceinline__ RayDesc pair_ray(const FrameParams& F, const RayDesc* __restrict__ rays, const TailFrame* __restrict__ tab, uint64_t key) {
+  if constexpr (BATCH) {
+    const TailFrame& f = tail_frame(F, tab, key);
+    return f.rays[tail_ray_index(f, key)];
+  } else {
+    return rays[ray_index(F, (uint32_t)key & F.point_mask)];
+  }
+}
+template <bool BATCH>
+__device__ __forceinline__ f3 pair_origin(const FrameParams& F, const TailFrame* __restrict__ tab, uint64_t key) {
+  if constexpr (BATCH) return tail_frame(F, tab, key).t;
+  else return F.T.t;
+}
+
 // MERGED is a compile-time copy of F.method == KS_METHOD_MERGED (per-bundle increments, mixed-label
 // increment vectors): uniform run-time tests in the step loop are not free.
-template <int COLOR_MODE, bool MERGED>
-__global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long n_pairs,
-                                               const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
-                                               const float* __restrict__ deltas, TileTable T, Pool P,
-                                               const uint32_t* __restrict__ label_lut,
-                                               unsigned long long* __restrict__ long_list, Counters* C) {
+template <int COLOR_MODE, bool MERGED, bool BATCH>
+__device__ __forceinline__ void apply_body(FrameParams F, unsigned long long n_pairs,
+                                           const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                           const float* __restrict__ deltas, TileTable T, Pool P,
+                                           const uint32_t* __restrict__ label_lut, const TailFrame* __restrict__ tab) {
   // Phase A — one lane per pair (64 consecutive pairs per wavefront): ray-descriptor gather and
   //   the voxel-state-independent half of updateTsdfVoxel, all 64 in flight at once.
   // Phase B — EIGHT LANES COOPERATE PER VOXEL: lane `sub` of a group moves 16 bytes of the
@@ -101,7 +127,7 @@ __global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long
     vox = (uint32_t)(key >> F.seq_bits);
     head = (i == 0) || ((uint32_t)(pairs[i - 1] >> F.seq_bits) != vox);
     if (head) is_long = (i + kLongRun < n_pairs) && ((uint32_t)(pairs[i + kLongRun] >> F.seq_bits) == vox);
-    u = load_update_ops<!MERGED && COLOR_MODE != KS_COLOR_MODE_COLOR>(F, rays, key, voxel_ref(T, vox));
+    u = load_update_ops<!MERGED && COLOR_MODE != KS_COLOR_MODE_COLOR, BATCH>(F, rays, key, voxel_ref(T, vox), tab);
   }
   __syncthreads();  // s_lut
 
@@ -223,7 +249,7 @@ __global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long
       for (unsigned long long j = wbase + 64ull; j < n_pairs; ++j) {
         const uint64_t k = pairs[j];
         if ((uint32_t)(k >> F.seq_bits) != hvox) break;
-        const UpdateOps t = load_update_ops<!MERGED && COLOR_MODE != KS_COLOR_MODE_COLOR>(F, rays, k, v);
+        const UpdateOps t = load_update_ops<!MERGED && COLOR_MODE != KS_COLOR_MODE_COLOR, BATCH>(F, rays, k, v, tab);
         if (sub == 0u) {
           tsdf_combine<COLOR_MODE == KS_COLOR_MODE_COLOR>(F.tsdf, t.sdf, t.uw, t.color, dist, weight, color);
         } else if (sub < 7u) {
@@ -274,6 +300,21 @@ __global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long
     const bool wr = active && sub < 7u;
     rec[wr ? sub : 7u] = wr ? outv : make_uint4(0u, 0u, 0u, 0u);
   }
+}
+template <int COLOR_MODE, bool MERGED>
+__global__ void __launch_bounds__(256) k_apply(FrameParams F, unsigned long long n_pairs,
+                                               const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                               const float* __restrict__ deltas, TileTable T, Pool P,
+                                               const uint32_t* __restrict__ label_lut,
+                                               unsigned long long* __restrict__ long_list, Counters* C) {
+  apply_body<COLOR_MODE, MERGED, false>(F, n_pairs, pairs, rays, deltas, T, P, label_lut, nullptr);
+}
+// ... over the sorted pairs of a whole batch of `fast` frames (F: the configuration, any frame's; tab: what differs between them)
+template <int COLOR_MODE>
+__global__ void __launch_bounds__(256) k_apply_batch(FrameParams F, unsigned long long n_pairs, const uint64_t* __restrict__ pairs,
+                                                     const TailFrame* __restrict__ tab, TileTable T, Pool P,
+                                                     const uint32_t* __restrict__ label_lut) {
+  apply_body<COLOR_MODE, false, true>(F, n_pairs, pairs, nullptr, nullptr, T, P, label_lut, tab);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -851,13 +892,13 @@ __global__ void __launch_bounds__(256) k_apply_long_lanes(FrameParams F, const u
   }
 }
 
-template <int COLOR_MODE>
-__global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long long n_pairs,
-                                                   const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
-                                                   const float* __restrict__ deltas, TileTable T, Pool P,
-                                                   const uint32_t* __restrict__ label_lut,
-                                                   const unsigned long long* __restrict__ long_list, const Counters* C,
-                                                   const LongHdr* __restrict__ H = nullptr) {
+template <int COLOR_MODE, bool BATCH>
+__device__ __forceinline__ void apply_long_body(FrameParams F, unsigned long long n_pairs,
+                                                const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                                const float* __restrict__ deltas, TileTable T, Pool P,
+                                                const uint32_t* __restrict__ label_lut,
+                                                const unsigned long long* __restrict__ long_list, const Counters* C,
+                                                const LongHdr* __restrict__ H, const TailFrame* __restrict__ tab) {
   // TWO wavefronts per run.  A lone wave is bound by instruction issue (one instruction every four
   // cycles): wave 0 (producer) gathers the rays of a 64-update batch, evaluates the state-
   // independent half of the update per lane, walks the weight / distance recurrences and writes
@@ -950,7 +991,7 @@ __global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long
       key_n[i] = pairs[min(base + 64ull * (PF + i) + lane, last)];
     }
 #pragma unroll
-    for (int i = 0; i < PF; ++i) d_q[i] = rays[ray_index(F, (uint32_t)key_q[i] & F.point_mask)];
+    for (int i = 0; i < PF; ++i) d_q[i] = pair_ray<BATCH>(F, rays, tab, key_q[i]);
 
     // one batch; returns false when the run has ended
     auto batch = [&](const uint64_t key_cur, const RayDesc& d) -> bool {
@@ -964,9 +1005,11 @@ __global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long
       // ---- per-lane, voxel-state-independent part: computeDistance + weight drop-off ----
       float sdf = 0.f, uw = 0.f;
       if (in) {
-        const f3 v_point_origin = sub3({d.px, d.py, d.pz}, F.T.t);
+        const f3 origin = pair_origin<BATCH>(F, tab, key_cur);   // (BATCH: the update's own frame's, so the origin->centre vector too)
+        const f3 v_vo = BATCH ? sub3(c, origin) : v_voxel_origin;
+        const f3 v_point_origin = sub3({d.px, d.py, d.pz}, origin);
         const float dist_G = norm3(v_point_origin);
-        const float dist_G_V = dot3(v_voxel_origin, v_point_origin) / dist_G;
+        const float dist_G_V = dot3(v_vo, v_point_origin) / dist_G;
         sdf = dist_G - dist_G_V;
         uw = d.weight;
         if (Pm.use_dropoff && sdf < -Pm.voxel_size) {
@@ -1045,7 +1088,7 @@ __global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long
         // slot j takes the batch PF after the one it held: its keys arrived a ring ago, its descriptors are requested
         // now, and the keys of the batch after that one follow
         key_q[j] = key_n[j];
-        d_q[j] = rays[ray_index(F, (uint32_t)key_n[j] & F.point_mask)];
+        d_q[j] = pair_ray<BATCH>(F, rays, tab, key_n[j]);
         key_n[j] = pairs[min(base + 64ull * (2 * PF) + lane, last)];
         more = batch(key_cur, d);
         if (!more) break;
@@ -1065,6 +1108,23 @@ __global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long
     __syncthreads();  // LDS free for the next run
   }
 }
+template <int COLOR_MODE>
+__global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long long n_pairs,
+                                                   const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                                   const float* __restrict__ deltas, TileTable T, Pool P,
+                                                   const uint32_t* __restrict__ label_lut,
+                                                   const unsigned long long* __restrict__ long_list, const Counters* C,
+                                                   const LongHdr* __restrict__ H = nullptr) {
+  apply_long_body<COLOR_MODE, false>(F, n_pairs, pairs, rays, deltas, T, P, label_lut, long_list, C, H, nullptr);
+}
+// ... of the sorted pairs of a whole batch of `fast` frames (k_apply_batch)
+template <int COLOR_MODE>
+__global__ void __launch_bounds__(128) k_apply_long_batch(FrameParams F, unsigned long long n_pairs, const uint64_t* __restrict__ pairs,
+                                                         const TailFrame* __restrict__ tab, TileTable T, Pool P,
+                                                         const uint32_t* __restrict__ label_lut,
+                                                         const unsigned long long* __restrict__ long_list, const Counters* C) {
+  apply_long_body<COLOR_MODE, true>(F, n_pairs, pairs, nullptr, nullptr, T, P, label_lut, long_list, C, nullptr, tab);
+}
 
 // The runs of more than kXLongRun updates — the handful of voxels next to the sensor, ONE chain of 1e4 .. 1e5 updates each
 // in `merged` (every bundle's ray starts there) — bound the update stage, and what bounds such a chain is the number of
@@ -1077,12 +1137,13 @@ __global__ void __launch_bounds__(128) k_apply_long(FrameParams F, unsigned long
 //   wave 0      walks the weight / distance recurrences of the batch prepared two steps ago (operands from the table);
 //   wave 1      folds that batch's increments into the 21 class sums, in order.
 // Same operations in the same order as k_apply_long: the voxel's record is bit for bit what the single chain leaves.
-template <int COLOR_MODE>
-__global__ void __launch_bounds__(256) k_apply_xlong(FrameParams F, unsigned long long n_pairs,
-                                                    const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
-                                                    const float* __restrict__ deltas, TileTable T, Pool P,
-                                                    const uint32_t* __restrict__ label_lut,
-                                                    const unsigned long long* __restrict__ xlong_list, const uint32_t* __restrict__ n_runs_ptr) {
+template <int COLOR_MODE, bool BATCH>
+__device__ __forceinline__ void apply_xlong_body(FrameParams F, unsigned long long n_pairs,
+                                                 const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                                 const float* __restrict__ deltas, TileTable T, Pool P,
+                                                 const uint32_t* __restrict__ label_lut,
+                                                 const unsigned long long* __restrict__ xlong_list, const uint32_t* __restrict__ n_runs_ptr,
+                                                 const TailFrame* __restrict__ tab) {
   __shared__ float s_inc[2][16][kNumLabels][4];  // [batch parity][update / 4][class][update % 4]
   __shared__ float4 s_tab[3][64];                // per update of a batch: sdf, update weight, colour
   __shared__ int s_cnt[3];                       // updates in the batch (< 64: the run ends with it)
@@ -1109,7 +1170,7 @@ __global__ void __launch_bounds__(256) k_apply_xlong(FrameParams F, unsigned lon
       // (all loads unconditional, indices clamped: ks_k_apply.h, k_apply_long)
       auto key_of = [&](unsigned long long own) { return pairs[min(start + 64ull * ((unsigned long long)f + 2ull * own) + lane, last)]; };
       uint64_t key_q[2] = {key_of(0), key_of(1)}, key_n[2] = {key_of(2), key_of(3)};
-      RayDesc d_q[2] = {rays[ray_index(F, (uint32_t)key_q[0] & F.point_mask)], rays[ray_index(F, (uint32_t)key_q[1] & F.point_mask)]};
+      RayDesc d_q[2] = {pair_ray<BATCH>(F, rays, tab, key_q[0]), pair_ray<BATCH>(F, rays, tab, key_q[1])};
       unsigned long long own = 0;  // the own batch whose first half comes next
       // what the second half of a batch needs of the first
       bool h_in = false;
@@ -1119,15 +1180,17 @@ __global__ void __launch_bounds__(256) k_apply_xlong(FrameParams F, unsigned lon
         const unsigned long long b = (unsigned long long)f + 2ull * own;
         const uint64_t key_cur = key_q[0];
         const RayDesc d = d_q[0];
-        const RayDesc d_new = rays[ray_index(F, (uint32_t)key_n[0] & F.point_mask)];
+        const RayDesc d_new = pair_ray<BATCH>(F, rays, tab, key_n[0]);
         const uint64_t key_new = key_of(own + 4ull);
         const bool in = (start + 64ull * b + lane < n_pairs) && ((uint32_t)(key_cur >> F.seq_bits) == vox);
         const int cnt = (int)__popcll(__ballot(in));  // sorted => the in-lanes form a prefix
         float sdf = 0.f, uw = 0.f;
         if (in) {
-          const f3 v_point_origin = sub3({d.px, d.py, d.pz}, F.T.t);
+          const f3 origin = pair_origin<BATCH>(F, tab, key_cur);   // (BATCH: the update's own frame's, so the origin->centre vector too)
+          const f3 v_vo = BATCH ? sub3(c, origin) : v_voxel_origin;
+          const f3 v_point_origin = sub3({d.px, d.py, d.pz}, origin);
           const float dist_G = norm3(v_point_origin);
-          const float dist_G_V = dot3(v_voxel_origin, v_point_origin) / dist_G;
+          const float dist_G_V = dot3(v_vo, v_point_origin) / dist_G;
           sdf = dist_G - dist_G_V;
           uw = d.weight;
           if (Pm.use_dropoff && sdf < -Pm.voxel_size) {
@@ -1287,6 +1350,42 @@ __global__ void __launch_bounds__(256) k_apply_xlong(FrameParams F, unsigned lon
     }
     __syncthreads();  // LDS free for the next run
   }
+}
+template <int COLOR_MODE>
+__global__ void __launch_bounds__(256) k_apply_xlong(FrameParams F, unsigned long long n_pairs,
+                                                    const uint64_t* __restrict__ pairs, const RayDesc* __restrict__ rays,
+                                                    const float* __restrict__ deltas, TileTable T, Pool P,
+                                                    const uint32_t* __restrict__ label_lut,
+                                                    const unsigned long long* __restrict__ xlong_list, const uint32_t* __restrict__ n_runs_ptr) {
+  apply_xlong_body<COLOR_MODE, false>(F, n_pairs, pairs, rays, deltas, T, P, label_lut, xlong_list, n_runs_ptr, nullptr);
+}
+// ... of the sorted pairs of a whole batch of `fast` frames (k_apply_batch)
+template <int COLOR_MODE>
+__global__ void __launch_bounds__(256) k_apply_xlong_batch(FrameParams F, unsigned long long n_pairs, const uint64_t* __restrict__ pairs,
+                                                          const TailFrame* __restrict__ tab, TileTable T, Pool P,
+                                                          const uint32_t* __restrict__ label_lut,
+                                                          const unsigned long long* __restrict__ xlong_list, const uint32_t* __restrict__ n_runs_ptr) {
+  apply_xlong_body<COLOR_MODE, true>(F, n_pairs, pairs, nullptr, nullptr, T, P, label_lut, xlong_list, n_runs_ptr, tab);
+}
+
+// A batch of frames' pair lists, one behind the other in frame order (the input of the batch's one sort): block row y copies
+// list y; nothing else of the tail touches the slots' own lists
+struct PairLists {
+  const uint64_t* src[8];
+  unsigned long long off[9];   // list y goes to [off[y], off[y + 1])
+};
+__global__ void __launch_bounds__(256) k_cat_pairs(PairLists L, uint64_t* __restrict__ out) {
+  const uint64_t* __restrict__ src = L.src[blockIdx.y];
+  const unsigned long long n = L.off[blockIdx.y + 1] - L.off[blockIdx.y];
+  uint64_t* __restrict__ dst = out + L.off[blockIdx.y];
+  for (unsigned long long i = (unsigned long long)blockIdx.x * 256ull + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256ull) dst[i] = src[i];
+}
+// the batch's frame table into device memory, at the head of the batch's tail
+struct TailFrames {
+  TailFrame f[8];
+};
+__global__ void __launch_bounds__(64) k_set_tail_frames(TailFrames B, TailFrame* __restrict__ out) {
+  if (threadIdx.x == 0) out[blockIdx.x] = B.f[blockIdx.x];   // (a block per entry: the index is uniform)
 }
 
 }  // namespace ksk

@@ -690,7 +690,8 @@ __global__ void __launch_bounds__(1024) k_scan_local(BatchView V) {
 // ------------------------------------------------------------------------------------------
 // k_emit — every live ray writes its (voxel, ray) keys at its offset of the scan; allocates voxel
 // tiles on first touch (CAS + pool bump; waits for a slot another lane is publishing only after the
-// wave has reconverged).  Key = [63:56] label | kind | clearing, [..] voxel id << seq_bits | ray sequence.
+// wave has reconverged).  Key = [63:56] label | kind | clearing, [..] voxel id << seq_bits | ray sequence (`fast`, batched
+// stage B: | the frame's index in its batch above it, FrameParams::frame_bits).
 // The list is in integration order; total = Counters::n_pairs.
 // ------------------------------------------------------------------------------------------
 #define KS_SLOT_ARGS(V)                                       \
@@ -762,7 +763,7 @@ __global__ void __launch_bounds__(256) k_emit(BatchView V, TileTable T, Pool P) 
     count = cnt[si] & ~kCntBroke;
     base = s_bt[si / kScanBlock] + lp[si];
     key_lo = ((uint64_t)((d.info & 0x1fu) | (((d.info >> 8) & 3u) << 5) | (((d.info >> 10) & 1u) << 7)) << 56) |
-             (uint64_t)((F.method == KS_METHOD_MERGED && clearing) ? (p | F.clear_bit) : p);
+             (uint64_t)((F.method == KS_METHOD_MERGED && clearing) ? (p | F.clear_bit) : (p | ((F.frame_bits >> 8) << (F.frame_bits & 0xffu))));
     own_key = F.ray_keys ? F.ray_keys[p] : 0ull;
     round.setup(F.T.t, {d.px, d.py, d.pz}, clearing, F.carving != 0, F.max_ray, F.voxel_size_inv, F.trunc,
                 /*cast_from_origin=*/F.method == KS_METHOD_MERGED);
@@ -867,7 +868,7 @@ __global__ void __launch_bounds__(256) k_emit_lane(BatchView V, TileTable T, Poo
     count = cnt[si] & ~kCntBroke;
     base = s_bt[si / kScanBlock] + lp[si];
     key_lo = ((uint64_t)((d.info & 0x1fu) | (((d.info >> 8) & 3u) << 5) | (((d.info >> 10) & 1u) << 7)) << 56) |
-             (uint64_t)((F.method == KS_METHOD_MERGED && clearing) ? (p | F.clear_bit) : p);
+             (uint64_t)((F.method == KS_METHOD_MERGED && clearing) ? (p | F.clear_bit) : (p | ((F.frame_bits >> 8) << (F.frame_bits & 0xffu))));
     dda.setup(F.T.t, {d.px, d.py, d.pz}, clearing, F.carving != 0, F.max_ray, F.voxel_size_inv, F.trunc,
               /*cast_from_origin=*/F.method == KS_METHOD_MERGED);
   }

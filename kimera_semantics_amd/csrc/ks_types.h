@@ -204,6 +204,10 @@ struct FrameParams {
   float start_inv;           // start_voxel_subsampling_factor * voxel_size_inv
   float log_match, log_non_match;
   TsdfParams tsdf;
+  // `fast` in a context that launches stage B per batch of frames: [7:0] = where the frame's index in its batch sits in a pair
+  // key — bits [shift, seq_bits), above the ray sequence —, [15:8] = that index (k_emit ors it in).  0: keys without it.
+  // (In the four bytes between tsdf and the 8-aligned start_offset: no other member moves.)
+  uint32_t frame_bits;
   uint64_t start_offset, observed_offset;
   uint32_t obs_tag, obs_tag_lo;  // frame tag of this frame's marks; first tag of the current offset generation
   uint64_t* observed;            // the early-out table this frame uses (one per march stream)
@@ -236,6 +240,15 @@ struct FrameParams {
   uint8_t dynamic_labels[32];
 };
 
+// Stage T over a whole batch of frames (ks_hip.hip: tail_batch): what one update needs of ITS frame, looked up by the frame
+// bits of its pair key.  Everything else of FrameParams is configuration, the same for every frame of a batch.
+struct TailFrame {
+  const RayDesc* rays;
+  f3 t;                                         // the sensor origin (FrameParams::T.t)
+  uint32_t point_mask, order_groups, order_per; // ray_index() of a `fast` frame in a mixed order
+  uint32_t pad[2];
+};
+
 __device__ __forceinline__ uint32_t point_order(const FrameParams& F, const uint32_t* order, uint32_t p) {
   // vxb::MixedThreadSafeIndex — [K:src/semantic_tsdf_integrator_fast.cpp:172-174]
   if (F.sorted_order) return order[p];
@@ -266,6 +279,17 @@ __device__ __forceinline__ bool grazing_skip(const FrameParams& F, int cx, int c
 // per bundle, stored at the bundle's first position.
 __device__ __forceinline__ uint32_t ray_index(const FrameParams& F, uint32_t p) {
   return (F.method == KS_METHOD_FAST) ? point_order(F, F.order, p) : p;
+}
+
+// The frame of a batched tail's update: entry [frame bits of the key] of the batch's table (device memory: a per-lane index
+// into a kernel argument would go through scratch), and the update's ray descriptor index in that frame.
+__device__ __forceinline__ const TailFrame& tail_frame(const FrameParams& F, const TailFrame* __restrict__ tab, uint64_t key) {
+  return tab[((uint32_t)key & ((1u << F.seq_bits) - 1u)) >> (F.frame_bits & 0xffu)];
+}
+__device__ __forceinline__ uint32_t tail_ray_index(const TailFrame& f, uint64_t key) {
+  const uint32_t p = (uint32_t)key & f.point_mask;
+  if (f.order_groups * f.order_per <= p) return p;
+  return (p % f.order_groups) * f.order_per + p / f.order_groups;
 }
 
 // inverse of point_order: integration position of the point stored at index idx
