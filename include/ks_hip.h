@@ -367,6 +367,71 @@ int ks_esdf_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, void*
 int ks_esdf_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, float* distance, uint8_t* flags,
                   uint8_t* label /* any may be NULL */);
 
+/* ---- reads of the stored ESDF for a planner: trilinear samples with gradients, slice images, segments swept against a robot
+ * radius (new: the reference sets slice_level in every launch file and hands the ESDF layer to Voxblox's planners on the host;
+ * here the field is read where its records are) ----
+ * The contract is DESIGN.md, section "ESDF reads"; every operation is f32 in the order written there (no parity with Voxblox's
+ * interpolator is claimed: it is not part of the reference tree).  The STORE is what ks_esdf_query reads, as it is — nothing is
+ * refreshed: the record of a voxel whose coordinates lie inside the packed range and whose tile was resident when the store was
+ * made, otherwise the default record {0, flags 0, label 255}; tiles written since the last update or refresh hold what that call
+ * stored, tiles that joined later read as default records, and after ks_remove_blocks* the store has followed the moved tiles.
+ * A voxel is OBSERVED iff bit 0 of its flags is set.
+ * SAMPLE E(p): g = p * voxel_size_inv - 0.5, i = floorf(g), f = g - i per axis (as the renderer's S(p)); corner j is
+ * i + (j & 1, (j >> 1) & 1, j >> 2); n = the voxel ks_esdf_query takes for p.  status 0 (UNKNOWN) if a coordinate of p is not
+ * finite or one of i, i + 1 is not inside the packed range (|.| < 2^20 - 1).  Otherwise status 2 (INTERPOLATED) iff all eight
+ * corners are OBSERVED: distance = the interpolant of the corner distances along x, then y, then z, each step a + f * (b - a);
+ * gradient_x = lerp(lerp(d1 - d0, d3 - d2, fy), lerp(d5 - d4, d7 - d6, fy), fz) * voxel_size_inv, y and z alike (the analytic
+ * gradient of the interpolant, as ks_align_points takes it).  Else status 1 (NEAREST) iff n is OBSERVED: distance = that of n's
+ * record, gradient 0.  Else status 0: distance = the quiet NaN 0x7fc00000, gradient 0, label 255, flags 0.  In statuses 1 and
+ * 2 label and flags are those of n's record (nearest-surface label; observed | fixed << 1).
+ * ks_esdf_sample   E at n host points; any of the five outputs may be NULL, not all.  Completes the frames in flight first and
+ *                  stages large n in chunks.  n = 0 is no error.
+ * ks_esdf_slice    an image: pixel (i, j), index j * width + i, is E at (origin + (float)i * du) + (float)j * dv per axis.  A
+ *                  horizontal slice at height z: origin = (x0, y0, z), du = (voxel_size, 0, 0), dv = (0, voxel_size, 0).
+ * ks_esdf_sweep    n segments {a, b} against a sphere of radius_m: d = b - a, L = sqrtf((dx dx + dy dy) + dz dz).  INVALID if a
+ *                  coordinate or L is not finite or L > (float)(max_samples - 2) * min_step (min_step = min_step_m, or half the
+ *                  voxel size when that is 0): t_stop 0, min_clearance +inf, t_min 0.  Otherwise u = d / L (0 when L == 0),
+ *                  t = 0, and at most max_samples times: (st, dist) = E(a + t * u); st == 0 and !unknown_is_free: UNKNOWN at
+ *                  t_stop = t; st != 0: c = dist - radius_m, a c below min_clearance replaces it (t_min = t), c < 0: COLLISION
+ *                  at t_stop = t; then t >= L: FREE with t_stop = L; else t = fminf(t + (st != 0 ? fmaxf(c, min_step) :
+ *                  min_step), L).  A segment still walking after max_samples samples is INVALID (rounding alone can do that).
+ *                  Non-finite points and segments are data, not errors.
+ * The *_device calls take DEVICE pointers, read and written on ks_stream(ctx): enqueued after the frames in flight have
+ * completed; the host waits for the kernel only when stats is non-NULL.  The statistics are integer sums.  Two calls on the same
+ * store give the same bytes.  The calls only READ: the map, the `updated` and `dirty` flags, both stale bits, the stored mesh, the
+ * stored ESDF, the objects and the mesh index stay as they were.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx; NULL input with n > 0; every output NULL (with n > 0); no stored ESDF; width or height
+ * outside 1..8192; a non-finite origin, du or dv; radius_m or min_step_m negative or not finite; max_samples outside 2..65536;
+ * n >= 2^32 segments; a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact),
+ * KS_ERR_HIP. */
+typedef struct ks_esdf_sample_stats { uint64_t points_interpolated, points_nearest, points_unknown; } ks_esdf_sample_stats; /* 24 bytes */
+enum { KS_ESDF_UNKNOWN = 0, KS_ESDF_NEAREST = 1, KS_ESDF_INTERPOLATED = 2 };
+int ks_esdf_sample(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, float* distance, float* gradient /* 3 per point */,
+                   uint8_t* status, uint8_t* label, uint8_t* flags /* any may be NULL, not all */, ks_esdf_sample_stats* stats /* may be NULL */);
+int ks_esdf_sample_device(ks_ctx* ctx, const float* d_xyz, size_t n, float* d_distance, float* d_gradient, uint8_t* d_status,
+                          uint8_t* d_label, uint8_t* d_flags, ks_esdf_sample_stats* stats);
+int ks_esdf_slice(ks_ctx* ctx, const float origin[3], const float du[3], const float dv[3], int width, int height, float* distance,
+                  float* gradient, uint8_t* status, uint8_t* label, uint8_t* flags, ks_esdf_sample_stats* stats);
+int ks_esdf_slice_device(ks_ctx* ctx, const float origin[3], const float du[3], const float dv[3], int width, int height,
+                         float* d_distance, float* d_gradient, uint8_t* d_status, uint8_t* d_label, uint8_t* d_flags,
+                         ks_esdf_sample_stats* stats);
+typedef struct ks_esdf_sweep_config {
+  float radius_m;          /* 0.3; >= 0 */
+  float min_step_m;        /* 0: half the context's voxel_size */
+  int32_t unknown_is_free; /* 0 */
+  int32_t max_samples;     /* 4096; 2..65536 */
+} ks_esdf_sweep_config;   /* 16 bytes */
+typedef struct ks_esdf_sweep_stats {
+  uint64_t segments_free, segments_collision, segments_unknown, segments_invalid, samples;
+} ks_esdf_sweep_stats; /* 40 bytes */
+enum { KS_SWEEP_FREE = 0, KS_SWEEP_COLLISION = 1, KS_SWEEP_UNKNOWN = 2, KS_SWEEP_INVALID = 3 };
+int ks_esdf_sweep_default_config(ks_esdf_sweep_config* cfg);
+int ks_esdf_sweep(ks_ctx* ctx, const float* segments /* host, n x {ax ay az bx by bz} */, size_t n, const ks_esdf_sweep_config* cfg,
+                  uint8_t* status, float* t_stop, float* min_clearance, float* t_min /* any may be NULL, not all */,
+                  ks_esdf_sweep_stats* stats /* may be NULL */);
+int ks_esdf_sweep_device(ks_ctx* ctx, const float* d_segments, size_t n, const ks_esdf_sweep_config* cfg, uint8_t* d_status,
+                         float* d_t_stop, float* d_min_clearance, float* d_t_min, ks_esdf_sweep_stats* stats);
+
 /* ---- view rendering: what the map looks like from a camera pose (new: the reference has no such product; a caller of it
  * downloads the layers and ray-casts on the host) ----
  * The contract is DESIGN.md, section "View rendering"; every operation is f32 in the order written there.  In short, for

@@ -41,6 +41,8 @@ ABI_SYMBOLS = [
     "ks_mesh_default_config", "ks_mesh_update", "ks_mesh_size", "ks_mesh_download", "ks_mesh_changed_blocks",
     "ks_esdf_default_config", "ks_esdf_update", "ks_esdf_download_blocks", "ks_esdf_query",
     "ks_esdf_refresh", "ks_esdf_changed_blocks",
+    "ks_esdf_sample", "ks_esdf_sample_device", "ks_esdf_slice", "ks_esdf_slice_device",
+    "ks_esdf_sweep_default_config", "ks_esdf_sweep", "ks_esdf_sweep_device",
     "ks_render_default_config", "ks_render_view", "ks_render_view_device",
     "ks_align_default_config", "ks_align_points", "ks_align_points_device",
     "ks_objects_default_config", "ks_objects_update", "ks_objects_size", "ks_objects_download", "ks_objects_download_blocks", "ks_objects_query",
@@ -117,6 +119,23 @@ class KsEsdfRefreshStats(C.Structure):
 ESDF_DTYPE = np.dtype([("distance", "<f4"), ("flags", "u1"), ("label", "u1"), ("pad", "u1", (2,))])
 
 
+class KsEsdfSampleStats(C.Structure):
+    _fields_ = [("points_interpolated", C.c_uint64), ("points_nearest", C.c_uint64), ("points_unknown", C.c_uint64)]
+
+
+class KsEsdfSweepConfig(C.Structure):
+    _fields_ = [("radius_m", C.c_float), ("min_step_m", C.c_float), ("unknown_is_free", C.c_int32), ("max_samples", C.c_int32)]
+
+
+class KsEsdfSweepStats(C.Structure):
+    _fields_ = [("segments_free", C.c_uint64), ("segments_collision", C.c_uint64), ("segments_unknown", C.c_uint64),
+                ("segments_invalid", C.c_uint64), ("samples", C.c_uint64)]
+
+
+KS_ESDF_UNKNOWN, KS_ESDF_NEAREST, KS_ESDF_INTERPOLATED = 0, 1, 2
+KS_SWEEP_FREE, KS_SWEEP_COLLISION, KS_SWEEP_UNKNOWN, KS_SWEEP_INVALID = 0, 1, 2, 3
+
+
 class KsRenderConfig(C.Structure):
     _fields_ = [("min_weight", C.c_float), ("min_range_m", C.c_float), ("max_range_m", C.c_float)]
 
@@ -189,7 +208,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -269,6 +288,13 @@ def lib():
         L.ks_esdf_query.argtypes = [vp, vp, C.c_size_t, vp, vp, vp]
         L.ks_esdf_refresh.argtypes = [vp, C.c_uint64, C.POINTER(KsEsdfRefreshStats)]
         L.ks_esdf_changed_blocks.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        for name in ("ks_esdf_sample", "ks_esdf_sample_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, vp, C.POINTER(KsEsdfSampleStats)]
+        for name in ("ks_esdf_slice", "ks_esdf_slice_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp, C.POINTER(KsEsdfSampleStats)]
+        L.ks_esdf_sweep_default_config.argtypes = [C.POINTER(KsEsdfSweepConfig)]
+        for name in ("ks_esdf_sweep", "ks_esdf_sweep_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_size_t, C.POINTER(KsEsdfSweepConfig), vp, vp, vp, vp, C.POINTER(KsEsdfSweepStats)]
         L.ks_render_default_config.argtypes = [C.POINTER(KsRenderConfig)]
         L.ks_render_view.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
         L.ks_render_view_device.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(KsRenderConfig), vp, vp, vp, vp, C.POINTER(KsRenderStats)]
@@ -550,6 +576,97 @@ class HipIntegrator:
         out = np.zeros(n, dtype=ESDF_DTYPE)
         out["distance"], out["flags"], out["label"] = d, f, l
         return out
+
+    @staticmethod
+    def _stats_dict(st) -> dict:
+        return {k: int(getattr(st, k)) for k, _ in st._fields_}
+
+    def esdf_sample(self, xyz, outputs=("distance", "gradient", "status", "label", "flags"), stats=True) -> dict:
+        """ks_esdf_sample: the trilinear sample E(p) of the STORED ESDF at world points xyz (n, 3).  Returns a dict of the asked
+        outputs — distance (n,) f32 (NaN where unknown), gradient (n, 3) f32, status / label / flags (n,) u8 — plus "stats".
+        The contract is DESIGN.md, section "ESDF reads"."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = self._esdf_sample_arrays((len(xyz),), outputs)
+        st = KsEsdfSampleStats()
+        self._chk(lib().ks_esdf_sample(self._h, _ptr(xyz), len(xyz), *[_ptr(out.get(k)) for k in self._ESDF_SAMPLE_OUTPUTS],
+                                       C.byref(st) if stats else None))
+        out["stats"] = self._stats_dict(st) if stats else None
+        return out
+
+    _ESDF_SAMPLE_OUTPUTS = ("distance", "gradient", "status", "label", "flags")
+
+    @classmethod
+    def _esdf_sample_arrays(cls, shape, outputs) -> dict:
+        for k in outputs:
+            if k not in cls._ESDF_SAMPLE_OUTPUTS:
+                raise AttributeError(k)
+        # (filled with a pattern no result has, so that an element the library did not write shows)
+        make = {"distance": lambda: np.full(shape, -7.0, np.float32), "gradient": lambda: np.full(shape + (3,), -7.0, np.float32)}
+        return {k: make.get(k, lambda: np.full(shape, 0xee, np.uint8))() for k in outputs}
+
+    def esdf_sample_device(self, d_xyz: int, n: int, d_distance: int = 0, d_gradient: int = 0, d_status: int = 0, d_label: int = 0,
+                           d_flags: int = 0, stats=True):
+        """ks_esdf_sample_device: raw device addresses (e.g. torch.Tensor.data_ptr()); 0 / None = not wanted.  The kernel is
+        enqueued on self.stream; with stats=False the host does not wait for it and None is returned."""
+        st = KsEsdfSampleStats()
+        self._chk(lib().ks_esdf_sample_device(self._h, d_xyz or None, int(n), d_distance or None, d_gradient or None, d_status or None,
+                                              d_label or None, d_flags or None, C.byref(st) if stats else None))
+        return self._stats_dict(st) if stats else None
+
+    def esdf_slice(self, origin, du, dv, width, height, outputs=("distance", "gradient", "status", "label", "flags"), stats=True) -> dict:
+        """ks_esdf_slice: E at (origin + i du) + j dv for the pixels (i, j) of a width x height image: a dict of (H, W[, 3]) arrays
+        as esdf_sample returns them, plus "stats"."""
+        o, u, v = (np.ascontiguousarray(a, dtype=np.float32).reshape(3) for a in (origin, du, dv))
+        w, h = int(width), int(height)
+        out = self._esdf_sample_arrays((max(h, 0), max(w, 0)), outputs)
+        st = KsEsdfSampleStats()
+        self._chk(lib().ks_esdf_slice(self._h, _ptr(o), _ptr(u), _ptr(v), w, h, *[_ptr(out.get(k)) for k in self._ESDF_SAMPLE_OUTPUTS],
+                                      C.byref(st) if stats else None))
+        out["stats"] = self._stats_dict(st) if stats else None
+        return out
+
+    def esdf_slice_device(self, origin, du, dv, width, height, d_distance: int = 0, d_gradient: int = 0, d_status: int = 0,
+                          d_label: int = 0, d_flags: int = 0, stats=True):
+        """ks_esdf_slice_device: as esdf_sample_device."""
+        o, u, v = (np.ascontiguousarray(a, dtype=np.float32).reshape(3) for a in (origin, du, dv))
+        st = KsEsdfSampleStats()
+        self._chk(lib().ks_esdf_slice_device(self._h, _ptr(o), _ptr(u), _ptr(v), int(width), int(height), d_distance or None, d_gradient or None,
+                                             d_status or None, d_label or None, d_flags or None, C.byref(st) if stats else None))
+        return self._stats_dict(st) if stats else None
+
+    def esdf_sweep_config(self, **cfg) -> KsEsdfSweepConfig:
+        sc = KsEsdfSweepConfig()
+        lib().ks_esdf_sweep_default_config(C.byref(sc))
+        for k, v in cfg.items():
+            if k not in [f for f, _ in KsEsdfSweepConfig._fields_]:
+                raise AttributeError(k)
+            if v is not None:
+                setattr(sc, k, v)
+        return sc
+
+    _ESDF_SWEEP_OUTPUTS = ("status", "t_stop", "min_clearance", "t_min")
+
+    def esdf_sweep(self, segments, outputs=("status", "t_stop", "min_clearance", "t_min"), stats=True, **cfg) -> dict:
+        """ks_esdf_sweep: segments (n, 6) {a, b} against a sphere of radius_m over the STORED ESDF.  Returns a dict of status (n,)
+        u8 (KS_SWEEP_*), t_stop / min_clearance / t_min (n,) f32, plus "stats"; cfg are the fields of KsEsdfSweepConfig."""
+        seg = np.ascontiguousarray(segments, dtype=np.float32).reshape(-1, 6)
+        for k in outputs:
+            if k not in self._ESDF_SWEEP_OUTPUTS:
+                raise AttributeError(k)
+        out = {k: (np.full(len(seg), 0xee, np.uint8) if k == "status" else np.full(len(seg), -7.0, np.float32)) for k in outputs}
+        sc, st = self.esdf_sweep_config(**cfg), KsEsdfSweepStats()
+        self._chk(lib().ks_esdf_sweep(self._h, _ptr(seg), len(seg), C.byref(sc), *[_ptr(out.get(k)) for k in self._ESDF_SWEEP_OUTPUTS],
+                                      C.byref(st) if stats else None))
+        out["stats"] = self._stats_dict(st) if stats else None
+        return out
+
+    def esdf_sweep_device(self, d_segments: int, n: int, d_status: int = 0, d_t_stop: int = 0, d_min_clearance: int = 0, d_t_min: int = 0,
+                          stats=True, **cfg):
+        """ks_esdf_sweep_device: as esdf_sample_device."""
+        sc, st = self.esdf_sweep_config(**cfg), KsEsdfSweepStats()
+        self._chk(lib().ks_esdf_sweep_device(self._h, d_segments or None, int(n), C.byref(sc), d_status or None, d_t_stop or None,
+                                             d_min_clearance or None, d_t_min or None, C.byref(st) if stats else None))
+        return self._stats_dict(st) if stats else None
 
     def render_config(self, **cfg) -> KsRenderConfig:
         rc = KsRenderConfig()

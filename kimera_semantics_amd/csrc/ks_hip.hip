@@ -69,6 +69,7 @@ using namespace ksd;
 #include "ks_k_mesh.h"
 #include "ks_k_mesh_index.h"
 #include "ks_k_esdf.h"
+#include "ks_k_esdf_read.h"
 #include "ks_k_render.h"
 #include "ks_k_align.h"
 #include "ks_k_objects.h"
@@ -532,6 +533,11 @@ struct ks_ctx {
   DevBuf<uint64_t> esdf_bricks[2];         // refresh: the bricks of lists X and Y
   DevBuf<uint64_t> esdf_lists;             // ... the sorted positions of X | Y | Z
   DevBuf<uint32_t> esdf_zslots;            // ... the pool slot of each position of Z
+  // ks_esdf_sample / ks_esdf_slice / ks_esdf_sweep (ks_k_esdf_read.h): the counters, and what the host-pointer calls stage per chunk
+  DevBuf<unsigned long long> esdf_read_counters;
+  DevBuf<float> esdf_read_in, esdf_read_f;   // points or segments in; distance | gradient, or t_stop | min_clearance | t_min out
+  DevBuf<uint8_t> esdf_read_b;             // status | label | flags
+  size_t esdf_read_chunk = size_t(1) << 20;   // points, segments or pixels staged at a time
   // ks_render_view (ks_k_render.h): the images of the host-pointer call before they are copied out, and the three counters
   DevBuf<float> render_depth, render_normals;
   DevBuf<uint32_t> render_rgba;
@@ -2895,6 +2901,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   if (const char* e = dbg_env("KS_EXACT_CAP_X")) eo_x0 = std::max<size_t>(8, (size_t)atoll(e));
   // (tests: a seed launch that covers fewer items than a frame has — the frame must end in the error path, not lose rays)
   if (const char* e = dbg_env("KS_SEED_CAP_ITEMS")) c->seed_cap_items = std::max<size_t>(1, (size_t)atoll(e));
+  // (tests: a host-pointer ESDF read of about a thousand points that crosses several chunk boundaries)
+  if (const char* e = dbg_env("KS_ESDF_READ_CHUNK")) c->esdf_read_chunk = std::max<size_t>(1, (size_t)atoll(e));
   if (eo_marks_first > eo_marks0) c->eo_want_marks.store(eo_marks_first, std::memory_order_relaxed);
   if (ensure_points(c, cfg->max_points) != KS_OK || ensure_exact_slots(c, eo_marks0, eo_x0) != KS_OK) {
     g_create_error = c->err;
@@ -3943,6 +3951,285 @@ int ks_esdf_query(ks_ctx* c, const float* xyz, size_t n, float* distance, uint8_
   }
   HIPCHK(c, hipGetLastError());
   return KS_OK;
+}
+
+// ---- reads of the stored ESDF ("ESDF reads"; ks_k_esdf_read.h) ----------------------------------
+// what all six calls ask of the context, then the frames in flight are completed
+static int esdf_read_begin(ks_ctx* c, const char* who) {
+  if (int rc = holds_voxels(c, who)) return rc;
+  if (c->fatal) {
+    c->err = std::string(who) + ": context is in a failed state (earlier pool/index error)";
+    return KS_ERR_INVALID_ARG;
+  }
+  if (int rc = esdf_ready(c, who)) return rc;
+  if (int rc = quiesce(c)) return rc;
+  if (int rc = c->esdf_read_counters.reserve(c, 8, 8)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->esdf_read_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+  return KS_OK;
+}
+static int esdf_read_refuse(ks_ctx* c, const char* who, const char* why) {
+  c->err = std::string(who) + ": " + why;
+  return KS_ERR_INVALID_ARG;
+}
+static EsdfReadStore esdf_read_view(ks_ctx* c) { return EsdfReadStore{c->esdf_store.get(), c->esdf_tiles, c->voxel_size_inv}; }
+// waits for the stream and reads k counters
+static int esdf_read_counts(ks_ctx* c, uint64_t* out, int k) {
+  unsigned long long counts[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(counts, c->esdf_read_counters, (size_t)k * sizeof(unsigned long long), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  for (int a = 0; a < k; ++a) out[a] = counts[a];
+  return KS_OK;
+}
+static int esdf_sample_stats(ks_ctx* c, ks_esdf_sample_stats* stats) {
+  uint64_t v[3];
+  if (int rc = esdf_read_counts(c, v, 3)) return rc;
+  stats->points_interpolated = v[0];
+  stats->points_nearest = v[1];
+  stats->points_unknown = v[2];
+  return KS_OK;
+}
+// the five staged outputs of m points (or pixels) to the caller's arrays at element `off`; O holds the staging addresses
+static int esdf_sample_copy_out(ks_ctx* c, const EsdfSampleOut& O, size_t off, size_t m, float* distance, float* gradient, uint8_t* status,
+                                uint8_t* label, uint8_t* flags) {
+  hipStream_t st = c->stream;
+  if (distance) HIPCHK(c, hipMemcpyAsync(distance + off, O.distance, m * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (gradient) HIPCHK(c, hipMemcpyAsync(gradient + 3 * off, O.gradient, 3 * m * sizeof(float), hipMemcpyDeviceToHost, st));
+  if (status) HIPCHK(c, hipMemcpyAsync(status + off, O.status, m, hipMemcpyDeviceToHost, st));
+  if (label) HIPCHK(c, hipMemcpyAsync(label + off, O.label, m, hipMemcpyDeviceToHost, st));
+  if (flags) HIPCHK(c, hipMemcpyAsync(flags + off, O.flags, m, hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));   // (the staging is reused by the next chunk)
+  return KS_OK;
+}
+// room for m_max points (or pixels) in the staging of the host-pointer calls, and where each wanted output lies in it
+static int esdf_sample_staging(ks_ctx* c, size_t m_max, bool distance, bool gradient, bool status, bool label, bool flags, EsdfSampleOut* O) {
+  int rc;
+  if ((rc = c->esdf_read_f.reserve(c, 4 * m_max, 4 * m_max)) || (rc = c->esdf_read_b.reserve(c, 3 * m_max, 3 * m_max))) return rc;
+  O->distance = distance ? c->esdf_read_f.get() : nullptr;
+  O->gradient = gradient ? c->esdf_read_f.get() + m_max : nullptr;
+  O->status = status ? c->esdf_read_b.get() : nullptr;
+  O->label = label ? c->esdf_read_b.get() + m_max : nullptr;
+  O->flags = flags ? c->esdf_read_b.get() + 2 * m_max : nullptr;
+  O->counters = c->esdf_read_counters;
+  return KS_OK;
+}
+// k_esdf_sample over n points at a DEVICE address (a launch takes at most 2^30 of them)
+static void esdf_sample_launch(ks_ctx* c, const float* d_xyz, size_t n, const EsdfSampleOut& O) {
+  const size_t per = size_t(1) << 30;
+  for (size_t off = 0; off < n; off += per) {
+    const size_t m = std::min(per, n - off);
+    EsdfSampleOut P = O;
+    if (P.distance) P.distance += off;
+    if (P.gradient) P.gradient += 3 * off;
+    if (P.status) P.status += off;
+    if (P.label) P.label += off;
+    if (P.flags) P.flags += off;
+    hipLaunchKernelGGL(k_esdf_sample, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, esdf_read_view(c), d_xyz + 3 * off, m, P);
+  }
+}
+
+int ks_esdf_sample_device(ks_ctx* c, const float* d_xyz, size_t n, float* d_distance, float* d_gradient, uint8_t* d_status, uint8_t* d_label,
+                          uint8_t* d_flags, ks_esdf_sample_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_sample_device";
+  if (n && !d_xyz) return esdf_read_refuse(c, who, "xyz is NULL");
+  if (n && !d_distance && !d_gradient && !d_status && !d_label && !d_flags) return esdf_read_refuse(c, who, "all five outputs are NULL");
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  esdf_sample_launch(c, d_xyz, n, EsdfSampleOut{d_distance, d_gradient, d_status, d_label, d_flags, c->esdf_read_counters});
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sample_stats(c, stats) : KS_OK;
+}
+
+int ks_esdf_sample(ks_ctx* c, const float* xyz, size_t n, float* distance, float* gradient, uint8_t* status, uint8_t* label, uint8_t* flags,
+                   ks_esdf_sample_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_sample";
+  if (n && !xyz) return esdf_read_refuse(c, who, "xyz is NULL");
+  if (n && !distance && !gradient && !status && !label && !flags) return esdf_read_refuse(c, who, "all five outputs are NULL");
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  const size_t m_max = std::min(c->esdf_read_chunk, n);
+  EsdfSampleOut O{};
+  int rc;
+  if ((rc = c->esdf_read_in.reserve(c, 3 * m_max, 3 * m_max)) || (rc = esdf_sample_staging(c, m_max, distance, gradient, status, label, flags, &O))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->esdf_read_in, xyz + 3 * off, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    esdf_sample_launch(c, c->esdf_read_in, m, O);
+    if ((rc = esdf_sample_copy_out(c, O, off, m, distance, gradient, status, label, flags))) return rc;
+  }
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sample_stats(c, stats) : KS_OK;
+}
+
+// the checks of both slice calls
+static int esdf_slice_check(ks_ctx* c, const char* who, const float origin[3], const float du[3], const float dv[3], int width, int height,
+                            bool any_output) {
+  if (!origin || !du || !dv) return esdf_read_refuse(c, who, "origin, du or dv is NULL");
+  if (width < 1 || width > 8192 || height < 1 || height > 8192) return esdf_read_refuse(c, who, "width and height must lie in 1..8192");
+  for (int k = 0; k < 3; ++k)
+    if (!std::isfinite(origin[k]) || !std::isfinite(du[k]) || !std::isfinite(dv[k])) return esdf_read_refuse(c, who, "origin, du and dv must be finite");
+  if (!any_output) return esdf_read_refuse(c, who, "all five outputs are NULL");
+  return KS_OK;
+}
+static void esdf_slice_launch(ks_ctx* c, const float origin[3], const float du[3], const float dv[3], int width, int row0, int rows,
+                              const EsdfSampleOut& O) {
+  EsdfSlice V{};
+  for (int k = 0; k < 3; ++k) {
+    V.origin[k] = origin[k];
+    V.du[k] = du[k];
+    V.dv[k] = dv[k];
+  }
+  V.width = width;
+  V.row0 = row0;
+  V.rows = rows;
+  hipLaunchKernelGGL(k_esdf_slice, dim3((uint32_t)((width + 15) / 16), (uint32_t)((rows + 15) / 16)), dim3(256), 0, c->stream, c->table,
+                     esdf_read_view(c), V, O);
+}
+
+int ks_esdf_slice_device(ks_ctx* c, const float origin[3], const float du[3], const float dv[3], int width, int height, float* d_distance,
+                         float* d_gradient, uint8_t* d_status, uint8_t* d_label, uint8_t* d_flags, ks_esdf_sample_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_slice_device";
+  if (int rc = esdf_slice_check(c, who, origin, du, dv, width, height, d_distance || d_gradient || d_status || d_label || d_flags)) return rc;
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  esdf_slice_launch(c, origin, du, dv, width, 0, height, EsdfSampleOut{d_distance, d_gradient, d_status, d_label, d_flags, c->esdf_read_counters});
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sample_stats(c, stats) : KS_OK;
+}
+
+int ks_esdf_slice(ks_ctx* c, const float origin[3], const float du[3], const float dv[3], int width, int height, float* distance, float* gradient,
+                  uint8_t* status, uint8_t* label, uint8_t* flags, ks_esdf_sample_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_slice";
+  if (int rc = esdf_slice_check(c, who, origin, du, dv, width, height, distance || gradient || status || label || flags)) return rc;
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  // bands of whole rows, about a chunk of pixels each
+  const int band = (int)std::min<size_t>((size_t)height, std::max<size_t>(1, c->esdf_read_chunk / (size_t)width));
+  const size_t m_max = (size_t)band * (size_t)width;
+  EsdfSampleOut O{};
+  int rc;
+  if ((rc = esdf_sample_staging(c, m_max, distance, gradient, status, label, flags, &O))) return rc;
+  for (int row0 = 0; row0 < height; row0 += band) {
+    const int rows = std::min(band, height - row0);
+    esdf_slice_launch(c, origin, du, dv, width, row0, rows, O);
+    if ((rc = esdf_sample_copy_out(c, O, (size_t)row0 * (size_t)width, (size_t)rows * (size_t)width, distance, gradient, status, label, flags))) return rc;
+  }
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sample_stats(c, stats) : KS_OK;
+}
+
+int ks_esdf_sweep_default_config(ks_esdf_sweep_config* s) {
+  if (!s) return KS_ERR_INVALID_ARG;
+  s->radius_m = 0.3f;
+  s->min_step_m = 0.0f;
+  s->unknown_is_free = 0;
+  s->max_samples = 4096;
+  return KS_OK;
+}
+
+// the checks of both sweep calls and the kernel's parameters but for its pointers
+static int esdf_sweep_check(ks_ctx* c, const char* who, size_t n, const ks_esdf_sweep_config* s, EsdfSweep* W) {
+  if (!s) return esdf_read_refuse(c, who, "the configuration is NULL");
+  if (!std::isfinite(s->radius_m) || s->radius_m < 0.0f || !std::isfinite(s->min_step_m) || s->min_step_m < 0.0f)
+    return esdf_read_refuse(c, who, "radius_m and min_step_m must be finite and not negative");
+  if (s->max_samples < 2 || s->max_samples > 65536) return esdf_read_refuse(c, who, "max_samples must lie in 2..65536");
+  if ((uint64_t)n >= (1ull << 32)) return esdf_read_refuse(c, who, "2^32 segments or more in one call");
+  W->radius = s->radius_m;
+  W->min_step = s->min_step_m > 0.0f ? s->min_step_m : 0.5f * c->cfg.voxel_size;
+  W->max_length = (float)(s->max_samples - 2) * W->min_step;
+  W->unknown_is_free = s->unknown_is_free != 0;
+  W->max_samples = s->max_samples;
+  return KS_OK;
+}
+static int esdf_sweep_stats(ks_ctx* c, ks_esdf_sweep_stats* stats) {
+  uint64_t v[5];
+  if (int rc = esdf_read_counts(c, v, 5)) return rc;
+  stats->segments_free = v[0];
+  stats->segments_collision = v[1];
+  stats->segments_unknown = v[2];
+  stats->segments_invalid = v[3];
+  stats->samples = v[4];
+  return KS_OK;
+}
+// k_esdf_sweep over W.n segments at a DEVICE address (a launch takes at most 2^30 of them)
+static void esdf_sweep_launch(ks_ctx* c, const EsdfSweep& W) {
+  const size_t per = size_t(1) << 30;
+  for (size_t off = 0; off < W.n; off += per) {
+    EsdfSweep P = W;
+    P.n = std::min(per, W.n - off);
+    P.segments += 6 * off;
+    if (P.status) P.status += off;
+    if (P.t_stop) P.t_stop += off;
+    if (P.min_clearance) P.min_clearance += off;
+    if (P.t_min) P.t_min += off;
+    hipLaunchKernelGGL(k_esdf_sweep, dim3((uint32_t)((P.n + 255) / 256)), dim3(256), 0, c->stream, c->table, esdf_read_view(c), P);
+  }
+}
+
+int ks_esdf_sweep_device(ks_ctx* c, const float* d_segments, size_t n, const ks_esdf_sweep_config* s, uint8_t* d_status, float* d_t_stop,
+                         float* d_min_clearance, float* d_t_min, ks_esdf_sweep_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_sweep_device";
+  EsdfSweep W{};
+  if (int rc = esdf_sweep_check(c, who, n, s, &W)) return rc;
+  if (n && !d_segments) return esdf_read_refuse(c, who, "segments is NULL");
+  if (n && !d_status && !d_t_stop && !d_min_clearance && !d_t_min) return esdf_read_refuse(c, who, "all four outputs are NULL");
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  W.segments = d_segments;
+  W.n = n;
+  W.status = d_status;
+  W.t_stop = d_t_stop;
+  W.min_clearance = d_min_clearance;
+  W.t_min = d_t_min;
+  W.counters = c->esdf_read_counters;
+  esdf_sweep_launch(c, W);
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sweep_stats(c, stats) : KS_OK;
+}
+
+int ks_esdf_sweep(ks_ctx* c, const float* segments, size_t n, const ks_esdf_sweep_config* s, uint8_t* status, float* t_stop, float* min_clearance,
+                  float* t_min, ks_esdf_sweep_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_esdf_sweep";
+  EsdfSweep W{};
+  if (int rc = esdf_sweep_check(c, who, n, s, &W)) return rc;
+  if (n && !segments) return esdf_read_refuse(c, who, "segments is NULL");
+  if (n && !status && !t_stop && !min_clearance && !t_min) return esdf_read_refuse(c, who, "all four outputs are NULL");
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  const size_t m_max = std::min(c->esdf_read_chunk, n);
+  int rc;
+  if ((rc = c->esdf_read_in.reserve(c, 6 * m_max, 6 * m_max)) || (rc = c->esdf_read_f.reserve(c, 3 * m_max, 3 * m_max)) ||
+      (rc = c->esdf_read_b.reserve(c, m_max, m_max)))
+    return rc;
+  W.segments = c->esdf_read_in;
+  W.status = status ? c->esdf_read_b.get() : nullptr;
+  W.t_stop = t_stop ? c->esdf_read_f.get() : nullptr;
+  W.min_clearance = min_clearance ? c->esdf_read_f.get() + m_max : nullptr;
+  W.t_min = t_min ? c->esdf_read_f.get() + 2 * m_max : nullptr;
+  W.counters = c->esdf_read_counters;
+  hipStream_t st = c->stream;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->esdf_read_in, segments + 6 * off, 6 * m * sizeof(float), hipMemcpyHostToDevice, st));
+    W.n = m;
+    esdf_sweep_launch(c, W);
+    if (status) HIPCHK(c, hipMemcpyAsync(status + off, W.status, m, hipMemcpyDeviceToHost, st));
+    if (t_stop) HIPCHK(c, hipMemcpyAsync(t_stop + off, W.t_stop, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (min_clearance) HIPCHK(c, hipMemcpyAsync(min_clearance + off, W.min_clearance, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (t_min) HIPCHK(c, hipMemcpyAsync(t_min + off, W.t_min, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (the staging is reused by the next chunk)
+  }
+  HIPCHK(c, hipGetLastError());
+  return stats ? esdf_sweep_stats(c, stats) : KS_OK;
 }
 
 // ---- view rendering ("View rendering"; ks_k_render.h) -------------------------------------------

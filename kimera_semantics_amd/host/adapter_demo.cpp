@@ -309,6 +309,58 @@ int main(int argc, char** argv) {
                 (unsigned long long)es.voxels_observed, (unsigned long long)es.voxels_fixed);
   }
 
+  // KS_DEMO_ESDF_SAMPLE=<file>: what a planner reads of the ESDF, on the device without any layer sync — updateEsdf (min_distance_m
+  // 0.1, max_distance_m 0.4), then sampleEsdf on a 13^3 lattice around the last frame's position and sweepEsdf (default options) from
+  // that position to every seventh lattice point, written as { u32 points, u32 segments; points x f32[3]; f32 distance[points];
+  // f32 gradient[points][3]; u8 status[points], label[points], flags[points]; segments x f32[6]; u8 status[segments];
+  // f32 t_stop[segments], min_clearance[segments], t_min[segments] }
+  if (const char* sample_path = std::getenv("KS_DEMO_ESDF_SAMPLE")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    hip->updateEsdf(eo, &esdf);
+    const vxb::Point o(last_T[4], last_T[5], last_T[6]);
+    vxb::Pointcloud pts;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfSegment> segs;
+    for (int k = -6; k <= 6; ++k)
+      for (int j = -6; j <= 6; ++j)
+        for (int i = -6; i <= 6; ++i) {
+          pts.push_back(vxb::Point(o.x() + 0.31f * (float)i, o.y() + 0.27f * (float)j, o.z() + 0.13f * (float)k));
+          if (pts.size() % 7 == 0) segs.push_back({o, pts.back()});
+        }
+    kimera::HipSemanticTsdfIntegrator::EsdfSamples sm;
+    kimera::HipSemanticTsdfIntegrator::EsdfSweeps sw;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->sampleEsdf(pts, &sm);
+    hip->sweepEsdf(segs, kimera::HipSemanticTsdfIntegrator::SweepOptions(), &sw);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* sf = std::fopen(sample_path, "wb");
+    if (!sf) return 9;
+    const uint32_t np = pts.size(), ns = segs.size();
+    std::fwrite(&np, 4, 1, sf);
+    std::fwrite(&ns, 4, 1, sf);
+    std::fwrite(pts.data(), 12, np, sf);
+    std::fwrite(sm.distance.data(), 4, np, sf);
+    std::fwrite(sm.gradient.data(), 12, np, sf);
+    std::fwrite(sm.status.data(), 1, np, sf);
+    std::fwrite(sm.label.data(), 1, np, sf);
+    std::fwrite(sm.flags.data(), 1, np, sf);
+    std::fwrite(segs.data(), 24, ns, sf);
+    std::fwrite(sw.status.data(), 1, ns, sf);
+    std::fwrite(sw.t_stop.data(), 4, ns, sf);
+    std::fwrite(sw.min_clearance.data(), 4, ns, sf);
+    std::fwrite(sw.t_min.data(), 4, ns, sf);
+    std::fclose(sf);
+    const ks_esdf_sample_stats& ss = hip->lastEsdfSampleStats();
+    const ks_esdf_sweep_stats& ws = hip->lastEsdfSweepStats();
+    std::printf("adapter_demo: sampleEsdf + sweepEsdf %.3f ms, %u points (%llu interpolated, %llu nearest), %u segments (%llu free, %llu collision, %llu samples)\n",
+                ms, np, (unsigned long long)ss.points_interpolated, (unsigned long long)ss.points_nearest, ns, (unsigned long long)ws.segments_free,
+                (unsigned long long)ws.segments_collision, (unsigned long long)ws.samples);
+  }
+
   // KS_DEMO_OBJECTS=<file>: the object instances of the map, made on the device without any layer sync (extractObjects,
   // default options), written as { u32 objects; per object: u32 label, u32 n_voxels, i64 first_voxel[3], i64 bb_min[3],
   // i64 bb_max[3], f32 centroid[3] }

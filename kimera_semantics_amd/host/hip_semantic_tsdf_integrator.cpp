@@ -375,6 +375,42 @@ bool HipSemanticTsdfIntegrator::refreshEsdf(std::vector<EsdfBlock>* changed) {
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::sampleEsdf(const vxb::Pointcloud& points_G, EsdfSamples* out) {
+  CHECK_NOTNULL(out);
+  static_assert(sizeof(vxb::Point) == 12, "point layout");
+  const size_t n = points_G.size();
+  out->distance.assign(n, 0.0f);
+  out->gradient.assign(n, vxb::Point(0.0f, 0.0f, 0.0f));
+  out->status.assign(n, 0);
+  out->label.assign(n, 0);
+  out->flags.assign(n, 0);
+  check(ks_esdf_sample(ctx_, n ? reinterpret_cast<const float*>(points_G.data()) : nullptr, n, out->distance.data(),
+                       reinterpret_cast<float*>(out->gradient.data()), out->status.data(), out->label.data(), out->flags.data(),
+                       &last_esdf_sample_stats_),
+        "ks_esdf_sample");
+  return last_esdf_sample_stats_.points_interpolated + last_esdf_sample_stats_.points_nearest != 0;
+}
+
+bool HipSemanticTsdfIntegrator::sweepEsdf(const std::vector<EsdfSegment>& segments, const SweepOptions& options, EsdfSweeps* out) {
+  CHECK_NOTNULL(out);
+  static_assert(sizeof(EsdfSegment) == 24, "segment layout");
+  ks_esdf_sweep_config sc;
+  ks_esdf_sweep_default_config(&sc);
+  sc.radius_m = options.radius_m;
+  sc.min_step_m = options.min_step_m;
+  sc.unknown_is_free = options.unknown_is_free ? 1 : 0;
+  sc.max_samples = options.max_samples;
+  const size_t n = segments.size();
+  out->status.assign(n, 0);
+  out->t_stop.assign(n, 0.0f);
+  out->min_clearance.assign(n, 0.0f);
+  out->t_min.assign(n, 0.0f);
+  check(ks_esdf_sweep(ctx_, n ? reinterpret_cast<const float*>(segments.data()) : nullptr, n, &sc, out->status.data(), out->t_stop.data(),
+                      out->min_clearance.data(), out->t_min.data(), &last_esdf_sweep_stats_),
+        "ks_esdf_sweep");
+  return last_esdf_sweep_stats_.segments_free == n;
+}
+
 void HipSemanticTsdfIntegrator::downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out) {
   const size_t n = idx.size() / 3, vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
   std::vector<EsdfVoxel> all(n * nv);

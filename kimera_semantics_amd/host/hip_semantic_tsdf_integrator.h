@@ -179,6 +179,35 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// records of every other block are what they were.  Returns true when `changed` is not empty.
   bool refreshEsdf(std::vector<EsdfBlock>* changed);
   const ks_esdf_refresh_stats& lastEsdfRefreshStats() const { return last_esdf_refresh_stats_; }
+  /// Distance and gradient of the STORED ESDF at world points (ks_esdf_sample; the contract is DESIGN.md, "ESDF reads"): the
+  /// trilinear interpolant where all eight corner voxels are observed (status 2), the nearest voxel's distance with a zero
+  /// gradient where only the point's own voxel is (status 1), NaN otherwise (status 0).  What a planner asked of Voxblox's
+  /// EsdfMap::getDistanceAndGradientAtPosition, ON THE DEVICE: no ESDF layer travels.  The store is read as it is — call
+  /// updateEsdf() / refreshEsdf() first.  Returns true when at least one point is not unknown.
+  struct EsdfSamples {
+    std::vector<float> distance;
+    std::vector<vxb::Point> gradient;
+    std::vector<uint8_t> status, label, flags;   ///< KS_ESDF_*; nearest-surface label; observed | fixed << 1
+  };
+  bool sampleEsdf(const vxb::Pointcloud& points_G, EsdfSamples* out);
+  const ks_esdf_sample_stats& lastEsdfSampleStats() const { return last_esdf_sample_stats_; }
+  /// Segments against a sphere of radius_m over the STORED ESDF (ks_esdf_sweep): how a sampling planner validates an edge.
+  /// status is KS_SWEEP_FREE / COLLISION / UNKNOWN / INVALID; t_stop the arc length where the walk ended, min_clearance the
+  /// smallest distance - radius seen on the way and t_min where.  Returns true when every segment is FREE.
+  struct SweepOptions {
+    float radius_m = 0.3f, min_step_m = 0.0f;   ///< min_step_m 0: half a voxel
+    bool unknown_is_free = false;
+    int max_samples = 4096;
+  };
+  struct EsdfSegment {
+    vxb::Point a, b;
+  };
+  struct EsdfSweeps {
+    std::vector<uint8_t> status;
+    std::vector<float> t_stop, min_clearance, t_min;
+  };
+  bool sweepEsdf(const std::vector<EsdfSegment>& segments, const SweepOptions& options, EsdfSweeps* out);
+  const ks_esdf_sweep_stats& lastEsdfSweepStats() const { return last_esdf_sweep_stats_; }
   /// What the map looks like from a camera pose (ks_render_view; the contract is DESIGN.md, "View rendering"): one ray per
   /// pixel through the resident tiles ON THE DEVICE, as the map is after the frames in flight.  Needs NO syncLayers(): the
   /// voxels stay in HBM, only the images travel.  depth is z-depth in the camera frame, NaN where the ray found no surface
@@ -256,6 +285,8 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_frame_stats last_stats_{};
   ks_mesh_stats last_mesh_stats_{};
   ks_esdf_stats last_esdf_stats_{};
+  ks_esdf_sample_stats last_esdf_sample_stats_{};
+  ks_esdf_sweep_stats last_esdf_sweep_stats_{};
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};

@@ -54,6 +54,9 @@ def main():
                     "(block_indices (N, 3), distance / flags / label (N, vps^3) in host block layout, voxel_size, voxels_per_side)")
     ap.add_argument("--esdf-every", type=int, default=0, metavar="N", help="keep an ESDF up to date on the device: ks_esdf_update at the first tick, "
                     "ks_esdf_refresh every N frames after it (with --esdf the file holds the refreshed ESDF)")
+    ap.add_argument("--esdf-slice", metavar="OUT.npz", help="write distance, status and label images of the final ESDF over the map's bounding box "
+                    "at z = --slice-level, one pixel per voxel, made on the device (ks_esdf_slice: trilinear, NaN where unknown)")
+    ap.add_argument("--slice-level", type=float, default=0.0, metavar="Z", help="the reference's slice_level")
     ap.add_argument("--esdf-max-distance", type=float, default=2.0, metavar="M")
     ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
     ap.add_argument("--render-every", type=int, default=0, metavar="N", help="render the map on the device from the frame's own pose and intrinsics "
@@ -244,6 +247,24 @@ def main():
         how = f"{st['tiles_recomputed']} of {st['tiles_total']} tiles recomputed" if esdf_ticks else f"box {st['box_voxels']}"
         print(f"esdf: {st['voxels_observed']} observed voxels ({st['voxels_fixed']} in the band, {st['voxels_clamped']} at +-{a.esdf_max_distance} m), "
               f"{how}, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_esdf * 1e3:.2f} ms ({'refresh' if esdf_ticks else 'update'} + download) -> {a.esdf}")
+    if a.esdf_slice:
+        if a.esdf or esdf_ticks:   # an ESDF is stored: bring it up to date (nothing is recomputed when it is)
+            integ.esdf_refresh()
+        else:
+            integ.esdf_update(**esdf_cfg)
+        idx = integ.block_indices()
+        side = integ.vps * a.voxel_size
+        lo, hi = idx.min(axis=0) * side, (idx.max(axis=0) + 1) * side
+        w, h = int(round((hi[0] - lo[0]) / a.voxel_size)), int(round((hi[1] - lo[1]) / a.voxel_size))
+        origin = [lo[0] + 0.5 * a.voxel_size, lo[1] + 0.5 * a.voxel_size, a.slice_level]   # pixel (i, j) at the centre of voxel column (i, j)
+        t1 = time.perf_counter()
+        img = integ.esdf_slice(origin, [a.voxel_size, 0, 0], [0, a.voxel_size, 0], w, h, outputs=("distance", "status", "label"))
+        t_slice = time.perf_counter() - t1
+        np.savez_compressed(a.esdf_slice, distance=img["distance"], status=img["status"], label=img["label"], origin=np.float32(origin),
+                            voxel_size=np.float32(a.voxel_size), slice_level=np.float32(a.slice_level))
+        st = img["stats"]
+        print(f"esdf slice at z = {a.slice_level} m: {w} x {h} pixels, {st['points_interpolated']} interpolated, {st['points_nearest']} nearest, "
+              f"{st['points_unknown']} unknown, {t_slice * 1e3:.2f} ms (slice + download) -> {a.esdf_slice}")
     if a.objects:
         t1 = time.perf_counter()
         rec, st = integ.objects(min_voxels=a.objects_min_voxels)
