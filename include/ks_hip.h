@@ -66,7 +66,7 @@ enum { KS_EARLY_OUT_EXACT = 1 };                             /* value of ks_conf
  * fill both from one dict. */
 typedef struct ks_config {
   float voxel_size;
-  int32_t voxels_per_side;          /* host Layer block edge (8, 16 or 32); device tiles are always 8^3 */
+  int32_t voxels_per_side;          /* host Layer block edge (8, 16, 32 or 64); device tiles are always 8^3 */
   float truncation_distance;
   float max_weight;
   float min_ray_length_m;

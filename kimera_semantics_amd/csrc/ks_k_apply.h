@@ -9,7 +9,7 @@ namespace ksk {
 //   updateTsdfVoxel  (Voxblox; called at [K:fast.cpp:128], [K:merged.cpp:317-319])
 //   updateSemanticVoxel: priors += L*freq, argmax, colour  ([K:src/semantic_integrator_base.cpp:136-194])
 // One read-modify-write of the voxel per frame however many rays crossed it.
-//   k_apply      : one lane per short run (< kLongRun updates); long runs are queued
+//   k_apply      : one lane per short run; runs of more than kLongRun (32) updates are queued
 //   k_apply_long : one wavefront per long run (voxels near the sensor collect thousands of
 //                  updates): lanes fetch 64 updates at once and pre-compute the voxel-state-
 //                  independent part (sdf, updated weight); the state recurrence is then walked

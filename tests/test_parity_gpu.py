@@ -524,7 +524,7 @@ def test_degenerate_inputs_exact(method):
 
 @pytest.mark.parametrize("color_mode", [1, 0])
 def test_long_bundles_edge_cases_exact(color_mode):
-    """`merged`, bundles of >= 32 points (one workgroup each, 64 points per step): bundles of exactly 64 / 128 / 192 points (the
+    """`merged`, bundles of more than kLongRun (32) points (one workgroup each, 64 points per step): bundles of exactly 64 / 128 / 192 points (the
     bundle ends on a step boundary), of 33 and 65, zero-weight points (|z| <= 1e-6 after the pose) inside a long bundle, points
     whose coordinate is exactly 0 (the exponent window of the division), and long bundles of points beyond the ray-length limit
     (clearing rays: the first usable point only)."""
