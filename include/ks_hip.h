@@ -432,6 +432,70 @@ int ks_esdf_sweep(ks_ctx* ctx, const float* segments /* host, n x {ax ay az bx b
 int ks_esdf_sweep_device(ks_ctx* ctx, const float* d_segments, size_t n, const ks_esdf_sweep_config* cfg, uint8_t* d_status,
                          float* d_t_stop, float* d_min_clearance, float* d_t_min, ks_esdf_sweep_stats* stats);
 
+/* ---- navigation field: cost-to-go and paths over the stored ESDF (new: the reference hands the ESDF layer to Voxblox's planners
+ * on the host; here reachability, travel cost and paths are computed where the records are) ----
+ * The contract is DESIGN.md, section "Navigation field".  In short: the input is the STORE the ESDF reads above describe, as it
+ * is.  A voxel is TRAVERSABLE iff bit 0 of its flags is set and distance >= radius_m (an f32 compare: a NaN is not); unobserved
+ * space never is (no unknown_is_free variant).  Two traversable voxels are adjacent iff their indices differ by at most 1 on every
+ * axis (26-connectivity, across tile seams); a step costs KS_NAV_COST_FACE / _EDGE / _CORNER, about cost * voxel_size / 10 metres;
+ * no corner-cutting rule (the radius has inflated the obstacles).  A goal's voxel is the one ks_esdf_query takes for the point; a
+ * goal with a non-finite coordinate, outside the packed range or in a voxel that is not traversable counts in goals_blocked and is
+ * otherwise ignored, the others (goals_used, once per point) have cost 0; all goals blocked is no error.
+ * FIELD: one uint32_t per voxel of the store's tiles: KS_NAV_BLOCKED where not traversable, else the smallest sum of step costs to
+ * a goal voxel, KS_NAV_UNREACHED if there is no path or that sum exceeds the cap max_cost (0: KS_NAV_MAX_COST).  It depends on the
+ * store, the radius, the cap and the SET of goal voxels alone — not on slots, on the order of goals or of uploads, or on the
+ * schedule of the relaxation: two calls give the same bytes.
+ * ks_nav_update   completes the frames in flight (their statistics stay owed), computes the field and stores it beside the tiles
+ *                 (4 B per voxel).  It only READS everything else.  The field is a SNAPSHOT of the ESDF store: later integrate,
+ *                 upload, merge and fuse calls leave it, tiles that join later read KS_NAV_BLOCKED; a successful ks_esdf_update or
+ *                 ks_esdf_refresh, a ks_remove_blocks* call that takes tiles out, ks_clear and ks_clear_voxels drop it, and so does
+ *                 a ks_nav_update that fails.  Without a field the reads return KS_ERR_INVALID_ARG.
+ * ks_nav_query    the cost of the voxel that contains each point; KS_NAV_BLOCKED outside the packed range, for non-finite points
+ *                 and for tiles not in the field.
+ * ks_nav_download_blocks   vps^3 words per host-layout block, x + vps * (y + vps * z); absent blocks read KS_NAV_BLOCKED.
+ * ks_nav_paths    per start: v = its voxel, cost = field[v] (also when blocked or unreached).  KS_NAV_BLOCKED: PATH_BLOCKED;
+ *                 unreached: PATH_UNREACHABLE; both with n_waypoints 0.  Else waypoint 0 is the centre of v,
+ *                 ((float)v_k + 0.5f) * voxel_size per axis, and while field[v] > 0 the next waypoint is the FIRST neighbour u in
+ *                 the order o = 0..26, o != 13, offset (o % 3 - 1, (o / 3) % 3 - 1, o / 9 - 1), with field[u] <= KS_NAV_MAX_COST and
+ *                 field[u] + w(o) == field[v].  Cost 0: PATH_REACHED.  More than max_waypoints waypoints: PATH_TRUNCATED with
+ *                 n_waypoints = max_waypoints.  No such neighbour (not on a field this library made): PATH_INVALID with the
+ *                 waypoints so far; never looped on.  waypoints is [n][max_waypoints][3]; rows from n_waypoints on are not
+ *                 written.  Any output may be NULL, not all.
+ * The *_device calls take DEVICE pointers on ks_stream(ctx); the host waits only when stats is non-NULL (ks_nav_query_device has
+ * none and never waits).  The host-pointer reads complete the frames in flight and stage large n in chunks.  n = 0 is no error.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; NULL goals or n_goals outside 1..65536; radius_m negative or not finite; max_cost
+ * above KS_NAV_MAX_COST; max_waypoints outside 1..65536; NULL input with n > 0; every output NULL with n > 0; no stored ESDF, or
+ * no stored field; a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact; the
+ * relaxation still active after max_rounds rounds: nothing is stored), KS_ERR_HIP. */
+#define KS_NAV_BLOCKED 0xffffffffu
+#define KS_NAV_UNREACHED 0xfffffffeu
+#define KS_NAV_MAX_COST 0xffffff00u
+enum { KS_NAV_COST_FACE = 10, KS_NAV_COST_EDGE = 14, KS_NAV_COST_CORNER = 17 };
+enum { KS_NAV_PATH_REACHED = 0, KS_NAV_PATH_UNREACHABLE = 1, KS_NAV_PATH_BLOCKED = 2, KS_NAV_PATH_TRUNCATED = 3, KS_NAV_PATH_INVALID = 4 };
+typedef struct ks_nav_config {
+  float radius_m;      /* 0.3; >= 0, finite */
+  uint32_t max_cost;   /* 0: KS_NAV_MAX_COST */
+  uint32_t max_rounds; /* 0: 1 << 20 */
+  uint32_t pad;
+} ks_nav_config;       /* 16 bytes */
+typedef struct ks_nav_stats {
+  uint64_t voxels_traversable, voxels_reached, goals_used, goals_blocked, largest_cost; /* follow from the contract */
+  uint64_t rounds, tile_relaxations; /* diagnostics of the schedule: they may differ from run to run */
+  uint64_t workspace_bytes;          /* the field, two lists and a flag word per tile, the goals */
+} ks_nav_stats;        /* 64 bytes */
+typedef struct ks_nav_path_stats { uint64_t paths_reached, paths_unreachable, paths_blocked, paths_truncated, waypoints; } ks_nav_path_stats; /* 40 bytes */
+int ks_nav_default_config(ks_nav_config* cfg);
+int ks_nav_update(ks_ctx* ctx, const float* goals_xyz /* host, world frame */, size_t n_goals, const ks_nav_config* cfg,
+                  ks_nav_stats* stats /* may be NULL */);
+int ks_nav_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* cost);
+int ks_nav_query_device(ks_ctx* ctx, const float* d_xyz, size_t n, uint32_t* d_cost);
+int ks_nav_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, uint32_t* out /* n * vps^3, host block layout */);
+int ks_nav_paths(ks_ctx* ctx, const float* starts_xyz /* host, world frame */, size_t n, uint32_t max_waypoints, uint8_t* status,
+                 uint32_t* cost, uint32_t* n_waypoints, float* waypoints /* any may be NULL, not all */,
+                 ks_nav_path_stats* stats /* may be NULL */);
+int ks_nav_paths_device(ks_ctx* ctx, const float* d_starts_xyz, size_t n, uint32_t max_waypoints, uint8_t* d_status, uint32_t* d_cost,
+                        uint32_t* d_n_waypoints, float* d_waypoints, ks_nav_path_stats* stats);
+
 /* ---- view rendering: what the map looks like from a camera pose (new: the reference has no such product; a caller of it
  * downloads the layers and ray-casts on the host) ----
  * The contract is DESIGN.md, section "View rendering"; every operation is f32 in the order written there.  In short, for

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "ks_remove_blocks", "ks_remove_distant_blocks", "ks_removed_blocks",
     "ks_fuse_default_config", "ks_fuse_map",
     "ks_mesh_index", "ks_mesh_index_size", "ks_mesh_index_download",
+    "ks_nav_default_config", "ks_nav_update", "ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks", "ks_nav_paths", "ks_nav_paths_device",
 ]
 
 
@@ -136,6 +137,25 @@ KS_ESDF_UNKNOWN, KS_ESDF_NEAREST, KS_ESDF_INTERPOLATED = 0, 1, 2
 KS_SWEEP_FREE, KS_SWEEP_COLLISION, KS_SWEEP_UNKNOWN, KS_SWEEP_INVALID = 0, 1, 2, 3
 
 
+class KsNavConfig(C.Structure):
+    _fields_ = [("radius_m", C.c_float), ("max_cost", C.c_uint32), ("max_rounds", C.c_uint32), ("pad", C.c_uint32)]
+
+
+class KsNavStats(C.Structure):
+    _fields_ = [("voxels_traversable", C.c_uint64), ("voxels_reached", C.c_uint64), ("goals_used", C.c_uint64), ("goals_blocked", C.c_uint64),
+                ("largest_cost", C.c_uint64), ("rounds", C.c_uint64), ("tile_relaxations", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
+class KsNavPathStats(C.Structure):
+    _fields_ = [("paths_reached", C.c_uint64), ("paths_unreachable", C.c_uint64), ("paths_blocked", C.c_uint64),
+                ("paths_truncated", C.c_uint64), ("waypoints", C.c_uint64)]
+
+
+KS_NAV_BLOCKED, KS_NAV_UNREACHED, KS_NAV_MAX_COST = 0xffffffff, 0xfffffffe, 0xffffff00
+KS_NAV_COST_FACE, KS_NAV_COST_EDGE, KS_NAV_COST_CORNER = 10, 14, 17
+KS_NAV_PATH_REACHED, KS_NAV_PATH_UNREACHABLE, KS_NAV_PATH_BLOCKED, KS_NAV_PATH_TRUNCATED, KS_NAV_PATH_INVALID = 0, 1, 2, 3, 4
+
+
 class KsRenderConfig(C.Structure):
     _fields_ = [("min_weight", C.c_float), ("min_range_m", C.c_float), ("max_range_m", C.c_float)]
 
@@ -208,7 +228,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -315,6 +335,12 @@ def lib():
         L.ks_mesh_index.argtypes = [vp, C.POINTER(KsMeshIndexStats)]
         L.ks_mesh_index_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.ks_mesh_index_download.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]
+        L.ks_nav_default_config.argtypes = [C.POINTER(KsNavConfig)]
+        L.ks_nav_update.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsNavConfig), C.POINTER(KsNavStats)]
+        for name in ("ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks"):
+            getattr(L, name).argtypes = [vp, vp, C.c_size_t, vp]
+        for name in ("ks_nav_paths", "ks_nav_paths_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp, C.POINTER(KsNavPathStats)]
         _lib = L
     return _lib
 
@@ -773,6 +799,73 @@ class HipIntegrator:
         out = np.zeros(len(xyz), dtype=np.uint32)
         self._chk(lib().ks_objects_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
         return out
+
+    # ---- navigation field over the stored ESDF (DESIGN.md, section "Navigation field") ----
+    def nav_config(self, **cfg) -> KsNavConfig:
+        nc = KsNavConfig()
+        lib().ks_nav_default_config(C.byref(nc))
+        for k, v in cfg.items():
+            if k not in ("radius_m", "max_cost", "max_rounds"):
+                raise AttributeError(k)
+            if v is not None:
+                setattr(nc, k, v)
+        return nc
+
+    def nav_update(self, goals, radius_m=None, max_cost=None, max_rounds=None) -> dict:
+        """ks_nav_update: the cost-to-go field of the STORED ESDF to the nearest of the world points goals (n, 3), through the voxels
+        a sphere of radius_m may occupy.  Returns the statistics; the field stays on the device for nav_query / nav_blocks /
+        nav_paths until the ESDF store or the map changes."""
+        goals = np.ascontiguousarray(goals, dtype=np.float32).reshape(-1, 3)
+        nc, st = self.nav_config(radius_m=radius_m, max_cost=max_cost, max_rounds=max_rounds), KsNavStats()
+        self._chk(lib().ks_nav_update(self._h, _ptr(goals), len(goals), C.byref(nc), C.byref(st)))
+        return self._stats_dict(st)
+
+    def nav_query(self, xyz) -> np.ndarray:
+        """(n,) u32: the cost of the voxel that contains each world point; KS_NAV_BLOCKED / KS_NAV_UNREACHED as in the field."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.full(len(xyz), 0xeeeeeeee, dtype=np.uint32)
+        self._chk(lib().ks_nav_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
+        return out
+
+    def nav_query_device(self, d_xyz: int, n: int, d_cost: int) -> None:
+        """ks_nav_query_device: raw device addresses (e.g. torch.Tensor.data_ptr()); enqueued on self.stream, the host does not wait."""
+        self._chk(lib().ks_nav_query_device(self._h, d_xyz or None, int(n), d_cost or None))
+
+    def nav_blocks(self, block_idx) -> np.ndarray:
+        """(n, vps^3) u32: the field of host-layout blocks; KS_NAV_BLOCKED where a block or tile is not in the field."""
+        indices = np.ascontiguousarray(block_idx, dtype=np.int32).reshape(-1, 3)
+        out = np.full((len(indices), self.vps ** 3), 0xeeeeeeee, dtype=np.uint32)
+        self._chk(lib().ks_nav_download_blocks(self._h, _ptr(indices), len(indices), _ptr(out)))
+        return out
+
+    _NAV_PATH_OUTPUTS = ("status", "cost", "n_waypoints", "waypoints")
+    NAV_WAYPOINT_FILL = -7.0   # rows of `waypoints` from n_waypoints on keep this pattern: the library does not write them
+
+    def nav_paths(self, starts, max_waypoints, outputs=("status", "cost", "n_waypoints", "waypoints"), stats=True) -> dict:
+        """ks_nav_paths: a path per world point of starts (n, 3) by steepest descent of the stored field.  Returns a dict of status
+        (n,) u8 (KS_NAV_PATH_*), cost (n,) u32, n_waypoints (n,) u32, waypoints (n, max_waypoints, 3) f32, plus "stats"."""
+        starts = np.ascontiguousarray(starts, dtype=np.float32).reshape(-1, 3)
+        n, mw = len(starts), max(int(max_waypoints), 0)
+        for k in outputs:
+            if k not in self._NAV_PATH_OUTPUTS:
+                raise AttributeError(k)
+        make = {"status": lambda: np.full(n, 0xee, np.uint8), "cost": lambda: np.full(n, 0xeeeeeeee, np.uint32),
+                "n_waypoints": lambda: np.full(n, 0xeeeeeeee, np.uint32),
+                "waypoints": lambda: np.full((n, min(mw, 65536), 3), self.NAV_WAYPOINT_FILL, np.float32)}
+        out = {k: make[k]() for k in outputs}
+        st = KsNavPathStats()
+        self._chk(lib().ks_nav_paths(self._h, _ptr(starts), n, int(max_waypoints) & 0xffffffff, *[_ptr(out.get(k)) for k in self._NAV_PATH_OUTPUTS],
+                                     C.byref(st) if stats else None))
+        out["stats"] = self._stats_dict(st) if stats else None
+        return out
+
+    def nav_paths_device(self, d_starts: int, n: int, max_waypoints: int, d_status: int = 0, d_cost: int = 0, d_n_waypoints: int = 0,
+                         d_waypoints: int = 0, stats=True):
+        """ks_nav_paths_device: as esdf_sample_device."""
+        st = KsNavPathStats()
+        self._chk(lib().ks_nav_paths_device(self._h, d_starts or None, int(n), int(max_waypoints) & 0xffffffff, d_status or None, d_cost or None,
+                                            d_n_waypoints or None, d_waypoints or None, C.byref(st) if stats else None))
+        return self._stats_dict(st) if stats else None
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----
     TILE_BYTES = 65536

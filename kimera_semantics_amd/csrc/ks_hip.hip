@@ -73,6 +73,7 @@ using namespace ksd;
 #include "ks_k_render.h"
 #include "ks_k_align.h"
 #include "ks_k_objects.h"
+#include "ks_k_nav.h"
 #include "ks_k_remove.h"
 #include "ks_k_fuse.h"
 
@@ -564,6 +565,20 @@ struct ks_ctx {
   bool obj_valid = false;                  // an update has run since the map was last cleared
   uint32_t obj_tiles = 0;                  // tiles that were resident at that update
   size_t obj_count = 0;                    // records stored
+  // ks_nav_update (ks_k_nav.h).  The field holds 512 words per tile slot of the ESDF store it was made from: a snapshot that the
+  // next ESDF update or refresh, a removal or a clear drops; the buffers grow only.
+  DevBuf<uint32_t> nav_cost;               // [nav_tiles][512]
+  DevBuf<uint32_t> nav_lists;              // [2][nav_tiles]: the active tiles of this round and of the next
+  DevBuf<uint32_t> nav_queued;             // [nav_tiles] the tile waits on a list, then the three rotating list counts
+  DevBuf<NavCounters> nav_counters;
+  DevBuf<unsigned long long> nav_path_counters;
+  DevBuf<float> nav_in, nav_wp;            // goals, or the starts of a chunk; the waypoints of a chunk
+  DevBuf<uint32_t> nav_u32;                // staging of query, download and paths (cost | n_waypoints)
+  DevBuf<uint8_t> nav_u8;                  // ... the path statuses
+  DevBuf<int32_t> nav_idx;
+  bool nav_valid = false;
+  uint32_t nav_tiles = 0;
+  size_t nav_chunk = size_t(1) << 20;      // points or starts staged at a time
   // ks_remove_blocks / ks_remove_distant_blocks (ks_k_remove.h).  What the stored products still have to hear of a removal:
   std::vector<int32_t> removed_blocks;     // the blocks the LAST removal call took out, ascending (ks_removed_blocks)
   std::vector<uint64_t> mesh_removed;      // block words removed since the last ks_mesh_update, ascending: it reports them as
@@ -2903,6 +2918,8 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   if (const char* e = dbg_env("KS_SEED_CAP_ITEMS")) c->seed_cap_items = std::max<size_t>(1, (size_t)atoll(e));
   // (tests: a host-pointer ESDF read of about a thousand points that crosses several chunk boundaries)
   if (const char* e = dbg_env("KS_ESDF_READ_CHUNK")) c->esdf_read_chunk = std::max<size_t>(1, (size_t)atoll(e));
+  // (tests: host-pointer reads of the navigation field that cross several chunk boundaries)
+  if (const char* e = dbg_env("KS_NAV_CHUNK")) c->nav_chunk = std::max<size_t>(1, (size_t)atoll(e));
   if (eo_marks_first > eo_marks0) c->eo_want_marks.store(eo_marks_first, std::memory_order_relaxed);
   if (ensure_points(c, cfg->max_points) != KS_OK || ensure_exact_slots(c, eo_marks0, eo_x0) != KS_OK) {
     g_create_error = c->err;
@@ -3655,6 +3672,7 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
   }
   // 2) the store: default records for every resident tile
   c->esdf_valid = false;   // (a failure below leaves no half-written snapshot readable)
+  c->nav_valid = false;    // the navigation field is a snapshot of the store this call replaces
   if ((rc = c->esdf_store.reserve(c, (size_t)nt * kTileVoxels, ((size_t)nt + nt / 2 + 64) * kTileVoxels))) return rc;
   if ((rc = c->esdf_counters.reserve(c, 3, 3))) return rc;
   HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
@@ -3820,6 +3838,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
   }
   if (L.n_stale == 0 && !tiles_left) {   // nothing to do: the totals of the store as it is
     c->esdf_changed.clear();
+    c->nav_valid = false;   // the navigation field does not outlive a successful refresh, whatever it recomputed
     return KS_OK;
   }
   if (workspace > max_workspace_bytes) {
@@ -3841,6 +3860,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
       (rc = c->esdf_counters.reserve(c, 3, 3)))
     return rc;
   c->esdf_valid = false;   // (a failure below leaves no half-written store readable)
+  c->nav_valid = false;    // the navigation field is a snapshot of the store as it was
   if (grown.get()) {
     if (nt_old) HIPCHK(c, hipMemcpyAsync(grown.get(), c->esdf_store.get(), (size_t)nt_old * kTileVoxels * sizeof(EsdfRecord), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -4599,6 +4619,253 @@ int ks_objects_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* id) {
   return KS_OK;
 }
 
+// ---- navigation field over the stored ESDF ("Navigation field"; ks_k_nav.h) ---------------------
+constexpr uint32_t kNavRoundsPerRead = 16;   // rounds enqueued between two host reads of the next list's count
+
+int ks_nav_default_config(ks_nav_config* n) {
+  if (!n) return KS_ERR_INVALID_ARG;
+  n->radius_m = 0.3f;
+  n->max_cost = 0;
+  n->max_rounds = 0;
+  n->pad = 0;
+  return KS_OK;
+}
+
+static int nav_refuse(ks_ctx* c, const char* who, const char* why) {
+  c->err = std::string(who) + ": " + why;
+  return KS_ERR_INVALID_ARG;
+}
+// what every call asks of the context, then the frames in flight are completed (their statistics stay owed)
+static int nav_begin(ks_ctx* c, const char* who) {
+  if (int rc = holds_voxels(c, who)) return rc;
+  if (c->fatal) return nav_refuse(c, who, "context is in a failed state (earlier pool/index error)");
+  return KS_OK;
+}
+static int nav_read_begin(ks_ctx* c, const char* who) {
+  if (int rc = nav_begin(c, who)) return rc;
+  if (!c->nav_valid) return nav_refuse(c, who, "no stored field (ks_nav_update has not run since the ESDF store or the map last changed)");
+  return quiesce(c);
+}
+static NavField nav_view(ks_ctx* c) { return NavField{c->nav_cost.get(), c->nav_tiles}; }
+
+int ks_nav_update(ks_ctx* c, const float* goals, size_t n_goals, const ks_nav_config* n, ks_nav_stats* stats) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_nav_update";
+  if (!goals || n_goals < 1 || n_goals > 65536) return nav_refuse(c, who, "goals is NULL or n_goals lies outside 1..65536");
+  if (!std::isfinite(n->radius_m) || n->radius_m < 0.0f) return nav_refuse(c, who, "radius_m must be finite and not negative");
+  if (n->max_cost > KS_NAV_MAX_COST) return nav_refuse(c, who, "max_cost lies above KS_NAV_MAX_COST");
+  if (int rc = nav_begin(c, who)) return rc;
+  if (int rc = esdf_ready(c, who)) return rc;
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->esdf_tiles;
+  const size_t nvox = (size_t)nt * kTileVoxels;
+  const uint32_t max_cost = n->max_cost ? n->max_cost : KS_NAV_MAX_COST, max_rounds = n->max_rounds ? n->max_rounds : 1u << 20;
+  int rc;
+  c->nav_valid = false;   // (a failure below leaves no field stored)
+  if ((rc = c->nav_cost.reserve(c, nvox, ((size_t)nt + nt / 2 + 64) * kTileVoxels)) || (rc = c->nav_lists.reserve(c, 2 * (size_t)nt, 3 * (size_t)nt + 128)) ||
+      (rc = c->nav_queued.reserve(c, (size_t)nt + 3, (size_t)nt + nt / 2 + 64)) || (rc = c->nav_counters.reserve(c, 1, 1)) ||
+      (rc = c->nav_in.reserve(c, 3 * n_goals, 3 * n_goals)))
+    return rc;
+  uint32_t* counts = c->nav_queued.get() + nt;
+  HIPCHK(c, hipMemsetAsync(c->nav_counters, 0, sizeof(NavCounters), st));
+  HIPCHK(c, hipMemsetAsync(c->nav_queued, 0, ((size_t)nt + 3) * sizeof(uint32_t), st));
+  HIPCHK(c, hipMemcpyAsync(c->nav_in, goals, 3 * n_goals * sizeof(float), hipMemcpyHostToDevice, st));
+  const NavField F{c->nav_cost.get(), nt};
+  if (nt)
+    hipLaunchKernelGGL(k_nav_init, dim3((uint32_t)((nvox + 255) / 256)), dim3(256), 0, st, (const EsdfRecord*)c->esdf_store.get(), nvox, n->radius_m,
+                       c->nav_cost.get(), c->nav_counters.get());
+  hipLaunchKernelGGL(k_nav_seed, dim3((uint32_t)((n_goals + 255) / 256)), dim3(256), 0, st, c->table, F, (const float*)c->nav_in.get(), (uint32_t)n_goals,
+                     c->voxel_size_inv, c->nav_queued.get(), c->nav_lists.get(), counts, c->nav_counters.get());
+  // rounds in groups: the host reads the count of the list the next round would take, once per group
+  uint32_t round = 0, active = 0;
+  for (;;) {
+    HIPCHK(c, hipMemcpyAsync(&active, counts + round % 3u, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (active == 0 || round >= max_rounds) break;
+    const uint32_t group = std::min(kNavRoundsPerRead, max_rounds - round);
+    for (uint32_t k = 0; k < group; ++k, ++round)
+      hipLaunchKernelGGL(k_nav_relax, dim3(nt), dim3(512), 0, st, c->table, F, c->nav_queued.get(), c->nav_lists.get(), counts, round, max_cost,
+                         c->nav_counters.get());
+  }
+  HIPCHK(c, hipGetLastError());
+  if (active) {   // a field that has not converged depends on the schedule: none is stored
+    c->err = std::string(who) + ": the relaxation is still active after max_rounds = " + std::to_string(max_rounds) + " rounds";
+    return KS_ERR_UNSUPPORTED;
+  }
+  if (nt) hipLaunchKernelGGL(k_nav_count, dim3((uint32_t)((nvox + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->nav_cost.get(), nvox, c->nav_counters.get());
+  NavCounters counters{};
+  HIPCHK(c, hipMemcpyAsync(&counters, c->nav_counters, sizeof(counters), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->nav_valid = true;
+  c->nav_tiles = nt;
+  if (stats) {
+    stats->voxels_traversable = counters.traversable;
+    stats->voxels_reached = counters.reached;
+    stats->goals_used = counters.goals_used;
+    stats->goals_blocked = counters.goals_blocked;
+    stats->largest_cost = counters.largest;
+    stats->rounds = counters.rounds;
+    stats->tile_relaxations = counters.relaxations;
+    stats->workspace_bytes = (uint64_t)nvox * 4 + (uint64_t)nt * 12 + (uint64_t)n_goals * 12;
+  }
+  return KS_OK;
+}
+
+// the field is one word per voxel with all-ones for "nothing here": the readers of the id store (ks_k_nav.h)
+static void nav_query_launch(ks_ctx* c, const float* d_xyz, size_t n, uint32_t* d_cost) {
+  const size_t per = size_t(1) << 30;
+  for (size_t off = 0; off < n; off += per) {
+    const size_t m = std::min(per, n - off);
+    hipLaunchKernelGGL(k_obj_query, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, (const uint32_t*)c->nav_cost.get(), c->nav_tiles,
+                       d_xyz + 3 * off, m, c->voxel_size_inv, d_cost + off);
+  }
+}
+
+int ks_nav_query_device(ks_ctx* c, const float* d_xyz, size_t n, uint32_t* d_cost) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_nav_query_device";
+  if (n && (!d_xyz || !d_cost)) return nav_refuse(c, who, "xyz or cost is NULL");
+  if (int rc = nav_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  nav_query_launch(c, d_xyz, n, d_cost);
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_nav_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* cost) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_nav_query";
+  if (n && (!xyz || !cost)) return nav_refuse(c, who, "xyz or cost is NULL");
+  if (int rc = nav_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  const size_t m_max = std::min(c->nav_chunk, n);
+  int rc;
+  if ((rc = c->nav_in.reserve(c, 3 * m_max, 3 * m_max)) || (rc = c->nav_u32.reserve(c, m_max, m_max))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->nav_in, xyz + 3 * off, 3 * m * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    nav_query_launch(c, c->nav_in, m, c->nav_u32);
+    HIPCHK(c, hipMemcpyAsync(cost + off, c->nav_u32, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the staging is reused by the next chunk)
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_nav_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, uint32_t* out) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_nav_download_blocks";
+  if (n && (!idx || !out)) return nav_refuse(c, who, "idx_xyz or out is NULL");
+  if (int rc = nav_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  const int vps = c->cfg.voxels_per_side;
+  const size_t nv = (size_t)vps * vps * vps;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(64) << 20) / (nv * sizeof(uint32_t))), 65535);   // <= 64 MiB staged at a time
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->nav_u32.reserve(c, m_max * nv, m_max * nv)) || (rc = c->nav_idx.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->nav_idx, idx + 3 * off, m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_download, dim3((uint32_t)((nv + 255) / 256), (uint32_t)m), dim3(256), 0, c->stream, c->table,
+                       (const uint32_t*)c->nav_cost.get(), c->nav_tiles, (const int32_t*)c->nav_idx.get(), vps, c->nav_u32.get());
+    HIPCHK(c, hipMemcpyAsync(out + off * nv, c->nav_u32, m * nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+// the checks of both path calls, then the frames in flight are completed and the five counters cleared
+static int nav_paths_begin(ks_ctx* c, const char* who, const float* starts, size_t n, uint32_t max_waypoints, bool any_output, ks_nav_path_stats* stats) {
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  if (max_waypoints < 1 || max_waypoints > 65536) return nav_refuse(c, who, "max_waypoints must lie in 1..65536");
+  if (n && !starts) return nav_refuse(c, who, "starts is NULL");
+  if (n && !any_output) return nav_refuse(c, who, "all four outputs are NULL");
+  if ((uint64_t)n >= (1ull << 32)) return nav_refuse(c, who, "2^32 starts or more in one call");
+  if (int rc = nav_read_begin(c, who)) return rc;
+  if (int rc = c->nav_path_counters.reserve(c, 8, 8)) return rc;
+  HIPCHK(c, hipMemsetAsync(c->nav_path_counters, 0, 8 * sizeof(unsigned long long), c->stream));
+  return KS_OK;
+}
+// k_nav_paths over P.n starts at a DEVICE address (a launch takes at most 2^30 of them)
+static void nav_paths_launch(ks_ctx* c, const NavPaths& P) {
+  const size_t per = size_t(1) << 30;
+  for (size_t off = 0; off < P.n; off += per) {
+    NavPaths Q = P;
+    Q.n = std::min(per, P.n - off);
+    Q.starts += 3 * off;
+    if (Q.status) Q.status += off;
+    if (Q.cost) Q.cost += off;
+    if (Q.n_waypoints) Q.n_waypoints += off;
+    if (Q.waypoints) Q.waypoints += off * (size_t)P.max_waypoints * 3;
+    hipLaunchKernelGGL(k_nav_paths, dim3((uint32_t)((Q.n + 255) / 256)), dim3(256), 0, c->stream, c->table, nav_view(c), Q);
+  }
+}
+// waits for the stream and reads the five sums
+static int nav_paths_stats(ks_ctx* c, ks_nav_path_stats* stats) {
+  unsigned long long v[5] = {0, 0, 0, 0, 0};
+  HIPCHK(c, hipMemcpyAsync(v, c->nav_path_counters, sizeof(v), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  stats->paths_reached = v[0];
+  stats->paths_unreachable = v[1];
+  stats->paths_blocked = v[2];
+  stats->paths_truncated = v[3];
+  stats->waypoints = v[4];
+  return KS_OK;
+}
+
+int ks_nav_paths_device(ks_ctx* c, const float* d_starts, size_t n, uint32_t max_waypoints, uint8_t* d_status, uint32_t* d_cost, uint32_t* d_n_waypoints,
+                        float* d_waypoints, ks_nav_path_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = nav_paths_begin(c, "ks_nav_paths_device", d_starts, n, max_waypoints, d_status || d_cost || d_n_waypoints || d_waypoints, stats)) return rc;
+  if (n == 0) return KS_OK;
+  nav_paths_launch(c, NavPaths{d_starts, n, max_waypoints, c->cfg.voxel_size, c->voxel_size_inv, d_status, d_cost, d_n_waypoints, d_waypoints,
+                               c->nav_path_counters.get()});
+  HIPCHK(c, hipGetLastError());
+  return stats ? nav_paths_stats(c, stats) : KS_OK;
+}
+
+int ks_nav_paths(ks_ctx* c, const float* starts, size_t n, uint32_t max_waypoints, uint8_t* status, uint32_t* cost, uint32_t* n_waypoints, float* waypoints,
+                 ks_nav_path_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = nav_paths_begin(c, "ks_nav_paths", starts, n, max_waypoints, status || cost || n_waypoints || waypoints, stats)) return rc;
+  if (n == 0) return KS_OK;
+  // a chunk's waypoints stay within 64 MiB; only the rows a path has written reach the caller's array
+  const size_t row = (size_t)max_waypoints * 3;
+  const size_t m_max = std::min(n, waypoints ? std::min(c->nav_chunk, std::max<size_t>(1, (size_t(64) << 20) / (row * sizeof(float)))) : c->nav_chunk);
+  const bool counts = n_waypoints || waypoints;
+  int rc;
+  if ((rc = c->nav_in.reserve(c, 3 * m_max, 3 * m_max)) || (rc = c->nav_u32.reserve(c, 2 * m_max, 2 * m_max)) || (rc = c->nav_u8.reserve(c, m_max, m_max)) ||
+      (waypoints && (rc = c->nav_wp.reserve(c, m_max * row, m_max * row))))
+    return rc;
+  NavPaths P{c->nav_in.get(), 0, max_waypoints, c->cfg.voxel_size, c->voxel_size_inv, status ? c->nav_u8.get() : nullptr, cost ? c->nav_u32.get() : nullptr,
+             counts ? c->nav_u32.get() + m_max : nullptr, waypoints ? c->nav_wp.get() : nullptr, c->nav_path_counters.get()};
+  std::vector<uint32_t> nw(counts ? m_max : 0);
+  std::vector<float> wp(waypoints ? m_max * row : 0);
+  hipStream_t st = c->stream;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->nav_in, starts + 3 * off, 3 * m * sizeof(float), hipMemcpyHostToDevice, st));
+    P.n = m;
+    nav_paths_launch(c, P);
+    if (status) HIPCHK(c, hipMemcpyAsync(status + off, P.status, m, hipMemcpyDeviceToHost, st));
+    if (cost) HIPCHK(c, hipMemcpyAsync(cost + off, P.cost, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (counts) HIPCHK(c, hipMemcpyAsync(nw.data(), P.n_waypoints, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (waypoints) HIPCHK(c, hipMemcpyAsync(wp.data(), P.waypoints, m * row * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (the staging is reused by the next chunk)
+    for (size_t i = 0; i < m; ++i) {
+      if (n_waypoints) n_waypoints[off + i] = nw[i];
+      if (waypoints && nw[i]) std::memcpy(waypoints + (off + i) * row, wp.data() + i * row, (size_t)nw[i] * 3 * sizeof(float));
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return stats ? nav_paths_stats(c, stats) : KS_OK;
+}
+
 // ---- voxel-level host sync -------------------------------------------------------------------------------
 // Device-side address of a host allocation the GPU can write (hipHostMalloc'ed: ks_host_alloc), else nullptr.
 static void* device_view_of_pinned(void* p) {
@@ -5344,6 +5611,8 @@ static void mesh_reset(ks_ctx* c) {
   c->obj_valid = false;    // ... and the stored objects
   c->obj_tiles = 0;
   c->obj_count = 0;
+  c->nav_valid = false;    // ... and the navigation field
+  c->nav_tiles = 0;
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {
@@ -5436,6 +5705,7 @@ static int remove_tiles(ks_ctx* c, ks_remove_stats* stats) {
     stats->pool_capacity_tiles = c->cfg.max_tiles;
   }
   if (n_removed == 0) return KS_OK;
+  c->nav_valid = false;   // slots move below and the navigation field does not follow
   if ((rc = snap.fetch_keys(c))) return rc;
   // 1) what leaves: tile positions and blocks, ascending
   std::vector<uint64_t> gone_tiles;

@@ -361,6 +361,58 @@ int main(int argc, char** argv) {
                 (unsigned long long)ws.segments_collision, (unsigned long long)ws.samples);
   }
 
+  // KS_DEMO_NAV=<file>: where the robot can go and how, on the device without any layer sync — updateEsdf (min_distance_m 0.1,
+  // max_distance_m 0.4), updateNavField (radius 0.2 m) with the last frame's position and a point 0.6 m beside it as goals, then
+  // planPaths (at most 96 waypoints) from a 13^3 lattice around that position, written as { u32 goals, u32 starts, u32 max_waypoints;
+  // goals x f32[3]; starts x f32[3]; u8 status[starts]; u32 cost[starts]; u32 n_waypoints[starts]; the waypoints of every start
+  // in turn, n_waypoints x f32[3] each }
+  if (const char* nav_path = std::getenv("KS_DEMO_NAV")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    hip->updateEsdf(eo, &esdf);
+    const vxb::Point o(last_T[4], last_T[5], last_T[6]);
+    vxb::Pointcloud goals, starts;
+    goals.push_back(o);
+    goals.push_back(vxb::Point(o.x() + 0.6f, o.y(), o.z()));
+    for (int k = -6; k <= 6; ++k)
+      for (int j = -6; j <= 6; ++j)
+        for (int i = -6; i <= 6; ++i) starts.push_back(vxb::Point(o.x() + 0.31f * (float)i, o.y() + 0.27f * (float)j, o.z() + 0.13f * (float)k));
+    kimera::HipSemanticTsdfIntegrator::NavOptions no;
+    no.radius_m = 0.2f;
+    kimera::HipSemanticTsdfIntegrator::NavPaths paths;
+    const uint32_t max_waypoints = 96;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->updateNavField(goals, no);
+    hip->planPaths(starts, max_waypoints, &paths);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* nf = std::fopen(nav_path, "wb");
+    if (!nf) return 9;
+    const uint32_t ng = goals.size(), ns = starts.size();
+    std::fwrite(&ng, 4, 1, nf);
+    std::fwrite(&ns, 4, 1, nf);
+    std::fwrite(&max_waypoints, 4, 1, nf);
+    std::fwrite(goals.data(), 12, ng, nf);
+    std::fwrite(starts.data(), 12, ns, nf);
+    std::fwrite(paths.status.data(), 1, ns, nf);
+    std::fwrite(paths.cost.data(), 4, ns, nf);
+    for (const auto& w : paths.waypoints) {
+      const uint32_t nw = w.size();
+      std::fwrite(&nw, 4, 1, nf);
+    }
+    for (const auto& w : paths.waypoints) std::fwrite(w.data(), 12, w.size(), nf);
+    std::fclose(nf);
+    const ks_nav_stats& st = hip->lastNavStats();
+    const ks_nav_path_stats& ps = hip->lastNavPathStats();
+    std::printf("adapter_demo: updateNavField + planPaths %.3f ms, %llu of %llu traversable voxels reached in %llu rounds, %u starts (%llu reached, %llu unreachable, %llu blocked, %llu waypoints)\n",
+                ms, (unsigned long long)st.voxels_reached, (unsigned long long)st.voxels_traversable, (unsigned long long)st.rounds, ns,
+                (unsigned long long)ps.paths_reached, (unsigned long long)ps.paths_unreachable, (unsigned long long)ps.paths_blocked,
+                (unsigned long long)ps.waypoints);
+  }
+
   // KS_DEMO_OBJECTS=<file>: the object instances of the map, made on the device without any layer sync (extractObjects,
   // default options), written as { u32 objects; per object: u32 label, u32 n_voxels, i64 first_voxel[3], i64 bb_min[3],
   // i64 bb_max[3], f32 centroid[3] }

@@ -411,6 +411,49 @@ bool HipSemanticTsdfIntegrator::sweepEsdf(const std::vector<EsdfSegment>& segmen
   return last_esdf_sweep_stats_.segments_free == n;
 }
 
+bool HipSemanticTsdfIntegrator::updateNavField(const vxb::Pointcloud& goals_G, const NavOptions& options) {
+  static_assert(sizeof(vxb::Point) == 12, "point layout");
+  ks_nav_config nc;
+  ks_nav_default_config(&nc);
+  nc.radius_m = options.radius_m;
+  nc.max_cost = options.max_cost;
+  nc.max_rounds = options.max_rounds;
+  const size_t n = goals_G.size();
+  check(ks_nav_update(ctx_, n ? reinterpret_cast<const float*>(goals_G.data()) : nullptr, n, &nc, &last_nav_stats_), "ks_nav_update");
+  return last_nav_stats_.goals_used != 0;
+}
+
+bool HipSemanticTsdfIntegrator::planPaths(const vxb::Pointcloud& starts_G, uint32_t max_waypoints, NavPaths* out) {
+  CHECK_NOTNULL(out);
+  const size_t n = starts_G.size();
+  out->status.assign(n, 0);
+  out->cost.assign(n, 0);
+  out->waypoints.assign(n, vxb::Pointcloud());
+  last_nav_path_stats_ = ks_nav_path_stats{};
+  // chunks of starts whose rows of max_waypoints stay within 16 MiB (max_waypoints is checked by the library)
+  const size_t row = std::max<size_t>(1, (size_t)max_waypoints * 3);
+  const size_t chunk = std::max<size_t>(1, (size_t(16) << 20) / (row * sizeof(float)));
+  std::vector<float> wp(std::min(chunk, n) * row);
+  std::vector<uint32_t> count(std::min(chunk, n));
+  const float* starts = n ? reinterpret_cast<const float*>(starts_G.data()) : nullptr;
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = std::min(chunk, n - off);
+    ks_nav_path_stats st{};
+    check(ks_nav_paths(ctx_, starts + 3 * off, m, max_waypoints, out->status.data() + off, out->cost.data() + off, count.data(), wp.data(), &st),
+          "ks_nav_paths");
+    last_nav_path_stats_.paths_reached += st.paths_reached;
+    last_nav_path_stats_.paths_unreachable += st.paths_unreachable;
+    last_nav_path_stats_.paths_blocked += st.paths_blocked;
+    last_nav_path_stats_.paths_truncated += st.paths_truncated;
+    last_nav_path_stats_.waypoints += st.waypoints;
+    for (size_t i = 0; i < m; ++i) {
+      const float* p = wp.data() + i * row;
+      for (uint32_t k = 0; k < count[i]; ++k) out->waypoints[off + i].push_back(vxb::Point(p[3 * k], p[3 * k + 1], p[3 * k + 2]));
+    }
+  }
+  return last_nav_path_stats_.paths_reached == n;
+}
+
 void HipSemanticTsdfIntegrator::downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out) {
   const size_t n = idx.size() / 3, vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
   std::vector<EsdfVoxel> all(n * nv);

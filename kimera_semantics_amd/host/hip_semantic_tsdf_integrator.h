@@ -208,6 +208,27 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   };
   bool sweepEsdf(const std::vector<EsdfSegment>& segments, const SweepOptions& options, EsdfSweeps* out);
   const ks_esdf_sweep_stats& lastEsdfSweepStats() const { return last_esdf_sweep_stats_; }
+  /// The cost-to-go field of the STORED ESDF to the nearest of `goals_G`, through the voxels a sphere of radius_m may occupy
+  /// (ks_nav_update; the contract is DESIGN.md, "Navigation field"): what a planner computed by Dijkstra on a downloaded ESDF
+  /// layer, ON THE DEVICE.  The field stays there for planPaths() until the next updateEsdf() / refreshEsdf(), removal or clear.
+  /// Call updateEsdf() / refreshEsdf() first.  Returns true when at least one goal is usable.
+  struct NavOptions {
+    float radius_m = 0.3f;
+    uint32_t max_cost = 0;     ///< 0: KS_NAV_MAX_COST
+    uint32_t max_rounds = 0;   ///< 0: 1 << 20
+  };
+  bool updateNavField(const vxb::Pointcloud& goals_G, const NavOptions& options);
+  const ks_nav_stats& lastNavStats() const { return last_nav_stats_; }
+  /// A path per start by steepest descent of that field (ks_nav_paths): waypoints are voxel centres, the last one a goal's.
+  /// status is KS_NAV_PATH_*; cost the start voxel's field value (about cost * voxel_size / 10 metres when reached).
+  /// Returns true when every start reached a goal.
+  struct NavPaths {
+    std::vector<uint8_t> status;
+    std::vector<uint32_t> cost;
+    std::vector<vxb::Pointcloud> waypoints;
+  };
+  bool planPaths(const vxb::Pointcloud& starts_G, uint32_t max_waypoints, NavPaths* out);
+  const ks_nav_path_stats& lastNavPathStats() const { return last_nav_path_stats_; }
   /// What the map looks like from a camera pose (ks_render_view; the contract is DESIGN.md, "View rendering"): one ray per
   /// pixel through the resident tiles ON THE DEVICE, as the map is after the frames in flight.  Needs NO syncLayers(): the
   /// voxels stay in HBM, only the images travel.  depth is z-depth in the camera frame, NaN where the ray found no surface
@@ -287,6 +308,8 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_esdf_stats last_esdf_stats_{};
   ks_esdf_sample_stats last_esdf_sample_stats_{};
   ks_esdf_sweep_stats last_esdf_sweep_stats_{};
+  ks_nav_stats last_nav_stats_{};
+  ks_nav_path_stats last_nav_path_stats_{};
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};

@@ -13,9 +13,11 @@ of the replay (ks_objects_update) and writes their records, centroids in metres 
 map around the sensor position after every frame (ks_remove_distant_blocks: what voxblox::TsdfServer does with
 max_block_distance_from_body; completes the frames in flight), so that a long replay runs in a bounded pool; --submap-frames N
 maps like a submap mapper: every N frames go into a second context in the frame of their first camera pose, which is then fused
-into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and merged) and cleared; map saving stays on the host side of the drop-in boundary (out of scope).
+into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and merged) and cleared; --nav-goal X,Y,Z --nav-out
+writes the cost-to-go field of the final ESDF to that goal for a robot of --nav-radius, made on the device (ks_nav_update), with the
+path from the last camera position; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
+      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
@@ -59,6 +61,10 @@ def main():
     ap.add_argument("--slice-level", type=float, default=0.0, metavar="Z", help="the reference's slice_level")
     ap.add_argument("--esdf-max-distance", type=float, default=2.0, metavar="M")
     ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
+    ap.add_argument("--nav-goal", metavar="X,Y,Z", help="with --nav-out: the goal of the navigation field, a world point in metres")
+    ap.add_argument("--nav-radius", type=float, default=0.3, metavar="R", help="the robot radius the field is made for")
+    ap.add_argument("--nav-out", metavar="OUT.npz", help="compute the cost-to-go field of the final ESDF to --nav-goal on the device (ks_nav_update) and "
+                    "write it per block with the path from the last camera position (ks_nav_paths); needs --esdf, --esdf-every or --esdf-slice")
     ap.add_argument("--render-every", type=int, default=0, metavar="N", help="render the map on the device from the frame's own pose and intrinsics "
                     "every N frames (ks_render_view; completes the frames in flight)")
     ap.add_argument("--render-out", metavar="DIR", help="where --render-every writes view_<frame>.npz (depth, labels, rgba, normals, T_G_C, K)")
@@ -80,6 +86,16 @@ def main():
     a = ap.parse_args()
     if a.render_every and not a.render_out:
         ap.error("--render-every needs --render-out")
+    if bool(a.nav_out) != bool(a.nav_goal):
+        ap.error("--nav-out and --nav-goal go together")
+    if a.nav_out and not (a.esdf or a.esdf_every or a.esdf_slice):
+        ap.error("--nav-out plans over the stored ESDF: give --esdf, --esdf-every or --esdf-slice as well")
+    if a.nav_goal:
+        try:
+            nav_goal = np.array([float(v) for v in a.nav_goal.split(",")], np.float32)
+            assert nav_goal.shape == (3,)
+        except (ValueError, AssertionError):
+            ap.error("--nav-goal takes X,Y,Z")
     if a.bag:
         seq = FS.read_rosbag(a.bag, a.depth_topic, a.semantic_topic, a.camera_info_topic, a.sensor_frame, a.base_link_frame, a.world_frame)
     else:
@@ -141,10 +157,12 @@ def main():
         os.makedirs(a.render_out, exist_ok=True)
 
     prune_s, prunes = 0.0, []
+    last_position = None
 
     def acc(fr, T, st):
-        nonlocal upd, refresh_s, n_seen, esdf_s, render_s, prune_s
+        nonlocal upd, refresh_s, n_seen, esdf_s, render_s, prune_s, last_position
         upd += st.n_voxel_updates
+        last_position = np.asarray(T, np.float32)[4:7].copy()
         n_seen += 1
         if a.max_block_distance is not None:   # first: what the later ticks of this frame see is the pruned map
             t1 = time.perf_counter()
@@ -265,6 +283,25 @@ def main():
         st = img["stats"]
         print(f"esdf slice at z = {a.slice_level} m: {w} x {h} pixels, {st['points_interpolated']} interpolated, {st['points_nearest']} nearest, "
               f"{st['points_unknown']} unknown, {t_slice * 1e3:.2f} ms (slice + download) -> {a.esdf_slice}")
+    if a.nav_out:   # (after the ESDF outputs: the store is up to date)
+        if not (a.esdf or a.esdf_slice):
+            integ.esdf_refresh()   # (--esdf-every alone: the last ticks' frames)
+        t1 = time.perf_counter()
+        st = integ.nav_update(nav_goal[None], radius_m=a.nav_radius)
+        idx = integ.block_indices()
+        field = integ.nav_blocks(idx)
+        path = integ.nav_paths(last_position[None], 65536, outputs=("status", "cost", "n_waypoints", "waypoints"))
+        t_nav = time.perf_counter() - t1
+        n_wp = int(path["n_waypoints"][0])
+        np.savez_compressed(a.nav_out, block_indices=idx, cost=field, goal=nav_goal, radius_m=np.float32(a.nav_radius), start=last_position,
+                            path_status=path["status"][0], path_cost=path["cost"][0], path=path["waypoints"][0, :n_wp],
+                            voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+        what = {B.KS_NAV_PATH_REACHED: "reaches the goal", B.KS_NAV_PATH_UNREACHABLE: "cannot reach the goal", B.KS_NAV_PATH_BLOCKED: "starts in a voxel "
+                "that is not traversable", B.KS_NAV_PATH_TRUNCATED: "was cut at 65536 waypoints"}.get(int(path["status"][0]), "is invalid")
+        print(f"nav: {st['voxels_reached']} of {st['voxels_traversable']} traversable voxels reached for radius {a.nav_radius} m ({st['goals_used']} of 1 goals "
+              f"usable), largest cost {st['largest_cost']}, {st['rounds']} rounds, {st['tile_relaxations']} tile relaxations; the path from the last camera "
+              f"position {what}: {n_wp} waypoints, about {int(path['cost'][0]) * a.voxel_size / 10 if n_wp else 0:.2f} m; {t_nav * 1e3:.2f} ms "
+              f"(field + download + path) -> {a.nav_out}")
     if a.objects:
         t1 = time.perf_counter()
         rec, st = integ.objects(min_voxels=a.objects_min_voxels)
