@@ -21,18 +21,19 @@ def cfg_of(spec):
     return dict(min_distance_m=MIN_DISTANCE, max_distance_m=spec.get("max_distance_m", 0.4))
 
 
-def random_field(idx, vps, seed):
-    """Not geometric: distances per voxel from {+-0.03, +-0.07 (sites, about 3 %), +-0.3}, labels 0..20, 10 % weight 0."""
+def random_field(idx, vps, seed, near=0.03, unobserved=0.10):
+    """Not geometric: distances per voxel from {+-0.03, +-0.07 (sites, about 3 %), +-0.3}, labels 0..20, 10 % weight 0.
+    near, unobserved: the two fractions (the draws are the same whatever they are)."""
     from kimera_semantics_amd import binding as B
     from kimera_semantics_amd import synth
     rng = np.random.default_rng(seed)
     idx = np.asarray(idx, np.int32).reshape(-1, 3)
     shape = (len(idx), vps ** 3)
     t, s = np.zeros(shape, B.TSDF_DTYPE), np.zeros(shape, B.SEM_DTYPE)
-    near = rng.random(shape) < 0.03
+    near = rng.random(shape) < near
     mag = np.where(near, rng.choice(np.array([0.03, 0.07], np.float32), shape), np.float32(0.3))
     t["distance"] = np.where(rng.random(shape) < 0.5, -mag, mag).astype(np.float32)
-    t["weight"] = np.where(rng.random(shape) < 0.10, 0.0, 1.0).astype(np.float32)
+    t["weight"] = np.where(rng.random(shape) < unobserved, 0.0, 1.0).astype(np.float32)
     label = rng.integers(0, 21, shape).astype(np.uint8)
     lut = synth.default_label_colors()
     t["color"] = lut[label]
@@ -216,6 +217,7 @@ def case_query(spec):
 
 def case_errors(spec):
     from kimera_semantics_amd import binding as B
+    from tests import esdf_model as M
     g = _uploaded("sphere", 8)
     idx = g.block_indices()
 
@@ -238,6 +240,11 @@ def case_errors(spec):
     assert e.stats["workspace_bytes"] > 4096 and "use_region" in str(e) and str(e.stats["workspace_bytes"]) in str(e), e
     st = g.esdf_update(min_distance_m=MIN_DISTANCE, max_distance_m=255 * VOXEL)   # R = 255 is served
     assert st["voxels_observed"] > 0 and st["voxels_clamped"] == 0
+    far = dict(min_distance_m=MIN_DISTANCE, max_distance_m=255 * VOXEL)   # ... and equals the model at that window
+    assert M.reach(far["max_distance_m"], VOXEL) == 255
+    model = M.model_of(g, far)
+    M.assert_same(g.esdf_blocks(idx), model.blocks(idx), "R = 255")
+    _check_stats(st, model, "R = 255")
     g.close()
     # a marcher context of the exact multi-GPU mode holds no voxel data
     marcher, owner = (mesh_case._integrator(1, 64, 48) for _ in range(2))

@@ -143,18 +143,29 @@ def esdf_from_blocks(indices, tsdf, labels, vps, voxel_size, form="separable", k
     return Model(origin, rec, stats, vps, keys=(planes, best, far, neg) if keep_keys else None)
 
 
-def tied_voxels(model, R):
+def tied_voxels(model, R, form="brute"):
     """Observed voxels outside the band whose minimum-d2 sites (two or more) differ in (|distance|, label): where the
-    secondary keys decide.  From the brute-force form: the largest low part among the sites at the minimum d2, against the
-    smallest."""
+    secondary keys decide.  The largest low part among the sites at the minimum d2, against the smallest: the minimum of the
+    keys with their low parts flipped.  That minimum separates like the key's own: adding o^2 << 40 keeps the order of a
+    flipped low part just as it keeps that of the low part, so form "separable" takes it for larger windows
+    (tests/test_esdf_cpu.py shows the two forms agree)."""
     planes, best, far, neg = model.keys
     flipped = np.where(planes < NONE, (planes & ~LOW) | (~planes & LOW), NONE)
-    other = window_min_brute(flipped, R)
+    other = (window_min_brute if form == "brute" else window_min_separable)(flipped, R)
     k = np.where(neg, best[1], best[0])
     o = np.where(neg, other[1], other[0])
     found = far & (k < NONE)
     assert ((k >> U(40)) == (o >> U(40)))[found].all()
     return int((found & ((k & LOW) != (~o & LOW))).sum())
+
+
+def found_d2(model):
+    """(found, d2) over the dense box: the observed voxels outside the band that have a site in their window, and the squared
+    offset, in voxels, of the site that won (0 where none did)."""
+    planes, best, far, neg = model.keys
+    k = np.where(neg, best[1], best[0])
+    found = far & (k < NONE)
+    return found, np.where(found, k >> U(40), U(0)).astype(np.int64)
 
 
 def model_of(g, cfg=None, form="separable", **kw):

@@ -31,6 +31,19 @@ def test_separable_model_equals_brute_force_model(kind, vps, max_distance_m):
     assert (a.dense["flags"] == 1).sum() > 5000 and (a.dense["flags"] == 0).sum() > 1000
 
 
+def test_separable_tie_count_equals_brute_force_tie_count():
+    """tied_voxels in both forms on the random field of the ties case: the separable form counts the rods and plates of
+    tests/esdf_far_case.py, whose windows the brute form cannot walk."""
+    idx, t, s = esdf_case.make_field("random", 8)
+    m = esdf_model.esdf_from_blocks(idx, t, s["label"], 8, esdf_case.VOXEL, form="brute", keep_keys=True,
+                                    min_distance_m=esdf_case.MIN_DISTANCE, max_distance_m=0.4)
+    R = esdf_model.reach(0.4, esdf_case.VOXEL)
+    brute, separable = esdf_model.tied_voxels(m, R), esdf_model.tied_voxels(m, R, form="separable")
+    assert R == 8 and brute == separable >= 1000, (brute, separable)
+    found, d2 = esdf_model.found_d2(m)
+    assert found.sum() > 5000 and d2[found].min() >= 1 and d2[found].max() <= 3 * R * R and (d2[~found] == 0).all()
+
+
 def test_model_on_an_analytic_sphere_is_the_distance_to_the_sphere():
     vps = 8
     idx, t, s = esdf_case.make_field("sphere", vps)
