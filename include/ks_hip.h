@@ -629,6 +629,71 @@ int ks_objects_download(ks_ctx* ctx, ks_object* out, size_t cap, size_t* n);
 int ks_objects_download_blocks(ks_ctx* ctx, const int32_t* idx_xyz, size_t n, uint32_t* out /* n * vps^3 ids, host block layout */);
 int ks_objects_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* id);
 
+/* ---- exploration frontiers over the stored ESDF: the free voxels a robot can stand in that border space nobody has observed,
+ * clustered (new: every exploration planner on such a map starts from this set, computed on the host from downloaded layers) ----
+ * The contract is DESIGN.md, section "Exploration frontiers"; it is this library's own.  The input is the ESDF STORE exactly as
+ * ks_nav_update reads it, with nothing refreshed: a voxel is OBSERVED iff bit 0 of its flags is set; every voxel outside the
+ * store's tiles (a tile that is not resident, one that joined after the store was made, indices beyond the tile range) reads the
+ * default record and so is not observed; a voxel is TRAVERSABLE iff it is observed and distance >= radius_m (an f32 compare: a NaN
+ * is not traversable; ks_nav_update's rule).  A traversable voxel is a FRONTIER VOXEL iff at least one of its SIX face neighbours
+ * is not observed (faces only); its unknown_faces is the number of such neighbours, 1..6.  With use_bounds, a voxel whose global
+ * index (8 * tile + local) lies outside the inclusive box bounds_min..bounds_max is no frontier voxel; that it is unobserved still
+ * makes its neighbours frontier voxels.  Frontier voxels are adjacent iff their global indices differ by at most 1 on every axis
+ * (26-connectivity, across tile seams); a COMPONENT is a class of the closure, a FRONTIER a component of at least min_voxels voxels.
+ * Everything in a record is an integer; centroid_k = ((double)sum_k / n_voxels + 0.5) * voxel_size is the host's one division.
+ * JOIN with the navigation field: if a field is stored when ks_frontiers_update runs (it is a snapshot of this same store),
+ * nav_cost is the minimum of field[v] over the frontier's voxels with field[v] <= KS_NAV_MAX_COST and nav_voxel, among the voxels
+ * attaining it, the smallest in (x, y, z) order; if no voxel has such a cost, or no field is stored (no error), nav_cost =
+ * KS_NAV_UNREACHED and nav_voxel = first_voxel.  The centre of nav_voxel, ((float)v + 0.5f) * voxel_size, is a valid start for
+ * ks_nav_paths.  The field is read at the call: a later ks_nav_update leaves the records as they were.
+ * Order (part of the ABI): frontiers ascend by pack_coord3(first_voxel).  Two calls give the same bytes, and so do the same voxels
+ * uploaded in another block order (nothing depends on slots).
+ * ks_frontiers_update   completes the frames in flight (their statistics stay owed) and stores the records and, beside the store's
+ *                       tiles, one uint32 per voxel: the index of its frontier, or KS_FRONTIER_NONE.  The result is a snapshot of
+ *                       the ESDF store, like the navigation field: later integrate, upload, merge and fuse calls leave it; a
+ *                       successful ks_esdf_update or ks_esdf_refresh, a ks_remove_blocks* call that takes tiles out, ks_clear,
+ *                       ks_clear_voxels and a ks_frontiers_update that fails drop it.  It only READS: the map, the `updated` and
+ *                       `dirty` flags, both stale bits, the stored mesh and its index, the ESDF, the objects and the navigation
+ *                       field stay as they were.  stats: voxels_traversable (of the store, whatever the bounds), voxels_frontier,
+ *                       components (before the min_voxels filter), frontiers, voxels_in_frontiers, largest_frontier_voxels,
+ *                       unknown_faces (over all frontier voxels), nav_field_used (0 | 1), workspace_bytes.
+ * ks_frontiers_size / ks_frontiers_download   the number of records / the records (cap >= that number).
+ * ks_frontiers_download_blocks   vps^3 ids per host-layout block in x + vps * (y + vps * z) order; absent blocks read as none.
+ * ks_frontiers_query    the id of the voxel that contains each point (the point-to-voxel rule of ks_esdf_query).
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; radius_m negative or not finite; min_voxels < 1; use_bounds with a bounds_min above
+ * its bounds_max; no stored ESDF; size, download or query without a stored result; capacity too small; NULL input or output with
+ * n > 0; a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact; a store of 2^23 tiles or
+ * more), KS_ERR_HIP (nothing stays stored).  A store without a frontier is no error: zero records; reads with n = 0 are no error.
+ * Multi-GPU: each context works over the tiles it holds; tiles of another owner read as unknown, seams between owners are not joined. */
+typedef struct ks_frontier_config {
+  float radius_m;       /* 0.3 */
+  uint32_t min_voxels;  /* 8 */
+  int32_t use_bounds;   /* 0 */
+  int32_t bounds_min[3], bounds_max[3]; /* inclusive, global voxel indices; read only with use_bounds */
+  uint32_t pad;
+} ks_frontier_config; /* 40 bytes */
+typedef struct ks_frontier_stats {
+  uint64_t voxels_traversable, voxels_frontier, components, frontiers, voxels_in_frontiers, largest_frontier_voxels, unknown_faces,
+      nav_field_used, workspace_bytes;
+} ks_frontier_stats; /* 72 bytes */
+typedef struct ks_frontier {
+  int32_t first_voxel[3]; /* the frontier's smallest global voxel index in (x, y, z) order: its identity */
+  uint32_t n_voxels;
+  int32_t bb_min[3], bb_max[3]; /* inclusive, global voxel indices */
+  int64_t sum[3];               /* sums of the voxels' global indices */
+  uint32_t unknown_faces;       /* sum over its voxels: proportional to the area that borders unknown space */
+  uint32_t nav_cost;            /* smallest cost-to-go of its voxels, or KS_NAV_UNREACHED */
+  int32_t nav_voxel[3];         /* the smallest voxel in (x, y, z) order at that cost, or first_voxel */
+  uint32_t pad;                 /* 0 */
+} ks_frontier; /* 88 bytes */
+#define KS_FRONTIER_NONE 0xffffffffu
+int ks_frontiers_default_config(ks_frontier_config* cfg);
+int ks_frontiers_update(ks_ctx* ctx, const ks_frontier_config* cfg, ks_frontier_stats* stats /* may be NULL */);
+int ks_frontiers_size(ks_ctx* ctx, size_t* n);
+int ks_frontiers_download(ks_ctx* ctx, ks_frontier* out, size_t cap, size_t* n);
+int ks_frontiers_download_blocks(ks_ctx* ctx, const int32_t* block_idx_xyz, size_t n, uint32_t* out /* n * vps^3 ids, host block layout */);
+int ks_frontiers_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* id);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

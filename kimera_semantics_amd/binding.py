@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "ks_fuse_default_config", "ks_fuse_map",
     "ks_mesh_index", "ks_mesh_index_size", "ks_mesh_index_download",
     "ks_nav_default_config", "ks_nav_update", "ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks", "ks_nav_paths", "ks_nav_paths_device",
+    "ks_frontiers_default_config", "ks_frontiers_update", "ks_frontiers_size", "ks_frontiers_download", "ks_frontiers_download_blocks", "ks_frontiers_query",
 ]
 
 
@@ -214,6 +215,42 @@ def object_centroids(records, voxel_size) -> np.ndarray:
     return (r["sum"].astype(np.float64) / np.maximum(r["n_voxels"], 1)[:, None].astype(np.float64) + 0.5) * float(voxel_size)
 
 
+class KsFrontierConfig(C.Structure):
+    _fields_ = [("radius_m", C.c_float), ("min_voxels", C.c_uint32), ("use_bounds", C.c_int32), ("bounds_min", C.c_int32 * 3),
+                ("bounds_max", C.c_int32 * 3), ("pad", C.c_uint32)]
+
+
+class KsFrontierStats(C.Structure):
+    _fields_ = [("voxels_traversable", C.c_uint64), ("voxels_frontier", C.c_uint64), ("components", C.c_uint64), ("frontiers", C.c_uint64),
+                ("voxels_in_frontiers", C.c_uint64), ("largest_frontier_voxels", C.c_uint64), ("unknown_faces", C.c_uint64),
+                ("nav_field_used", C.c_uint64), ("workspace_bytes", C.c_uint64)]
+
+
+# ks_frontier: 88 bytes; centroid as for ks_object (frontier_centroids), the start of a path to it: frontier_targets
+FRONTIER_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
+                           ("sum", "<i8", (3,)), ("unknown_faces", "<u4"), ("nav_cost", "<u4"), ("nav_voxel", "<i4", (3,)), ("pad", "<u4")])
+KS_FRONTIER_NONE = 0xffffffff
+
+
+def frontier_centroids(records, voxel_size) -> np.ndarray:
+    """Centroids in metres, (n, 3) f64, of ks_frontier records: the host's one division."""
+    return object_centroids(records, voxel_size)
+
+
+def frontier_targets(records, voxel_size) -> np.ndarray:
+    """(n, 3) f32: the centres of the records' nav_voxel, ((float)v + 0.5f) * voxel_size — valid starts for nav_paths."""
+    v = np.asarray(records)["nav_voxel"].astype(np.float32)
+    return (v + np.float32(0.5)) * np.float32(voxel_size)
+
+
+def frontier_bounds(box_min_m, box_max_m, voxel_size):
+    """(bounds_min, bounds_max) int32 (3,): the voxels that contain the two corners of a metric box, by ks_esdf_query's
+    point-to-voxel rule floor(p * (1 / voxel_size) + 1e-6) in f32."""
+    inv = np.float32(1.0 / np.float64(np.float32(voxel_size)))
+    lo, hi = (np.floor(np.asarray(p, np.float32).reshape(3) * inv + np.float32(1e-6)).astype(np.int32) for p in (box_min_m, box_max_m))
+    return lo, hi
+
+
 KS_ALIGN_CONVERGED, KS_ALIGN_ITERATION_LIMIT, KS_ALIGN_TOO_FEW_INLIERS, KS_ALIGN_DEGENERATE = 0, 1, 2, 3
 
 
@@ -228,7 +265,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -335,6 +372,12 @@ def lib():
         L.ks_mesh_index.argtypes = [vp, C.POINTER(KsMeshIndexStats)]
         L.ks_mesh_index_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
         L.ks_mesh_index_download.argtypes = [vp, vp, vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t]
+        L.ks_frontiers_default_config.argtypes = [C.POINTER(KsFrontierConfig)]
+        L.ks_frontiers_update.argtypes = [vp, C.POINTER(KsFrontierConfig), C.POINTER(KsFrontierStats)]
+        L.ks_frontiers_size.argtypes = [vp, C.POINTER(C.c_size_t)]
+        L.ks_frontiers_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_frontiers_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_frontiers_query.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_nav_default_config.argtypes = [C.POINTER(KsNavConfig)]
         L.ks_nav_update.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsNavConfig), C.POINTER(KsNavStats)]
         for name in ("ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks"):
@@ -798,6 +841,52 @@ class HipIntegrator:
         xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(len(xyz), dtype=np.uint32)
         self._chk(lib().ks_objects_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
+        return out
+
+    # ---- exploration frontiers over the stored ESDF (DESIGN.md, section "Exploration frontiers") ----
+    def frontier_config(self, **cfg) -> KsFrontierConfig:
+        fc = KsFrontierConfig()
+        lib().ks_frontiers_default_config(C.byref(fc))
+        for k, v in cfg.items():
+            if k not in ("radius_m", "min_voxels", "use_bounds", "bounds_min", "bounds_max"):
+                raise AttributeError(k)
+            if v is None:
+                continue
+            if k in ("bounds_min", "bounds_max"):
+                v = (C.c_int32 * 3)(*[int(a) for a in v])
+            setattr(fc, k, v)
+        return fc
+
+    def frontiers(self, **cfg):
+        """ks_frontiers_update + ks_frontiers_download: the traversable voxels of the STORED ESDF with an unobserved face neighbour,
+        clustered into 26-connected components and joined with the stored navigation field, if there is one.  Returns (records (n,)
+        FRONTIER_DTYPE ascending by first_voxel, stats dict).  cfg are the fields of KsFrontierConfig.  The contract is DESIGN.md,
+        section "Exploration frontiers"; frontier_ids() / frontier_query() read the per-voxel ids it stores."""
+        fc, st = self.frontier_config(**cfg), KsFrontierStats()
+        self._chk(lib().ks_frontiers_update(self._h, C.byref(fc), C.byref(st)))
+        return self.frontier_records(), {k: int(getattr(st, k)) for k, _ in KsFrontierStats._fields_}
+
+    def frontier_records(self) -> np.ndarray:
+        """The records of the last frontiers() call."""
+        n = C.c_size_t()
+        self._chk(lib().ks_frontiers_size(self._h, C.byref(n)))
+        out = np.zeros(n.value, dtype=FRONTIER_DTYPE)
+        self._chk(lib().ks_frontiers_download(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def frontier_ids(self, block_idx) -> np.ndarray:
+        """(N, vps^3) u32 in host block layout: the index of each voxel's frontier in the records of the last frontiers() call, or
+        KS_FRONTIER_NONE."""
+        indices = np.ascontiguousarray(block_idx, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((len(indices), self.vps ** 3), dtype=np.uint32)
+        self._chk(lib().ks_frontiers_download_blocks(self._h, _ptr(indices), len(indices), _ptr(out)))
+        return out
+
+    def frontier_query(self, xyz) -> np.ndarray:
+        """(n,) u32: the frontier id of the voxel that contains each world point, or KS_FRONTIER_NONE."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(xyz), dtype=np.uint32)
+        self._chk(lib().ks_frontiers_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
         return out
 
     # ---- navigation field over the stored ESDF (DESIGN.md, section "Navigation field") ----

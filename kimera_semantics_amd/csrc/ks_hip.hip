@@ -74,6 +74,7 @@ using namespace ksd;
 #include "ks_k_align.h"
 #include "ks_k_objects.h"
 #include "ks_k_nav.h"
+#include "ks_k_frontier.h"
 #include "ks_k_remove.h"
 #include "ks_k_fuse.h"
 
@@ -579,6 +580,25 @@ struct ks_ctx {
   bool nav_valid = false;
   uint32_t nav_tiles = 0;
   size_t nav_chunk = size_t(1) << 20;      // points or starts staged at a time
+  // ks_frontiers_update (ks_k_frontier.h).  The id store holds 512 words per tile slot of the ESDF store it was made from: a
+  // snapshot with the lifetime of the navigation field (drop_frontiers); the buffers grow only.
+  DevBuf<uint32_t> fr_ids;                 // [fr_tiles][512] (during an update: the provisional numbers of the roots)
+  DevBuf<uint32_t> fr_parent;              // the union-find forest of an update, then the voxels' provisional numbers
+  DevBuf<uint8_t> fr_cls, fr_faces;        // the class byte and the unknown-face count of every voxel
+  DevBuf<unsigned long long> fr_planes;    // [fr_tiles][8][observed | candidate]: 128 B per tile
+  DevBuf<ObjCounters> fr_numbered;         // k_obj_number's component count
+  DevBuf<FrCounters> fr_counters;
+  DevBuf<FrAcc> fr_acc;                    // per provisional component
+  DevBuf<uint64_t> fr_keys[2];             // the sort's key and payload buffers
+  DevBuf<uint32_t> fr_vals[2];
+  DevBuf<uint32_t> fr_final;               // provisional number -> frontier index
+  DevBuf<ks_frontier> fr_records;
+  DevBuf<uint32_t> fr_out;                 // staging of download and query
+  DevBuf<int32_t> fr_idx;
+  DevBuf<float> fr_xyz;
+  bool fr_valid = false;
+  uint32_t fr_tiles = 0;
+  size_t fr_count = 0;
   // ks_remove_blocks / ks_remove_distant_blocks (ks_k_remove.h).  What the stored products still have to hear of a removal:
   std::vector<int32_t> removed_blocks;     // the blocks the LAST removal call took out, ascending (ks_removed_blocks)
   std::vector<uint64_t> mesh_removed;      // block words removed since the last ks_mesh_update, ascending: it reports them as
@@ -605,6 +625,12 @@ struct ks_ctx {
       return KS_ERR_HIP;                                                                          \
     }                                                                                             \
   } while (0)
+
+// the stored frontiers are a snapshot of the ESDF store: they go wherever the navigation field goes
+static void drop_frontiers(ks_ctx* c) {
+  c->fr_valid = false;
+  c->fr_count = 0;
+}
 
 int ks_hip_failed(ks_ctx* ctx, const char* what, hipError_t e) {
   ctx->err = std::string(what) + ": " + hipGetErrorString(e);
@@ -3673,6 +3699,7 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
   // 2) the store: default records for every resident tile
   c->esdf_valid = false;   // (a failure below leaves no half-written snapshot readable)
   c->nav_valid = false;    // the navigation field is a snapshot of the store this call replaces
+  drop_frontiers(c);       // ... and so are the frontiers (§21)
   if ((rc = c->esdf_store.reserve(c, (size_t)nt * kTileVoxels, ((size_t)nt + nt / 2 + 64) * kTileVoxels))) return rc;
   if ((rc = c->esdf_counters.reserve(c, 3, 3))) return rc;
   HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
@@ -3839,6 +3866,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
   if (L.n_stale == 0 && !tiles_left) {   // nothing to do: the totals of the store as it is
     c->esdf_changed.clear();
     c->nav_valid = false;   // the navigation field does not outlive a successful refresh, whatever it recomputed
+    drop_frontiers(c);      // ... nor do the frontiers (§21)
     return KS_OK;
   }
   if (workspace > max_workspace_bytes) {
@@ -3861,6 +3889,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     return rc;
   c->esdf_valid = false;   // (a failure below leaves no half-written store readable)
   c->nav_valid = false;    // the navigation field is a snapshot of the store as it was
+  drop_frontiers(c);       // ... and so are the frontiers (§21)
   if (grown.get()) {
     if (nt_old) HIPCHK(c, hipMemcpyAsync(grown.get(), c->esdf_store.get(), (size_t)nt_old * kTileVoxels * sizeof(EsdfRecord), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -4866,6 +4895,185 @@ int ks_nav_paths(ks_ctx* c, const float* starts, size_t n, uint32_t max_waypoint
   return stats ? nav_paths_stats(c, stats) : KS_OK;
 }
 
+// ---- exploration frontiers over the stored ESDF ("Exploration frontiers"; ks_k_frontier.h) -------
+int ks_frontiers_default_config(ks_frontier_config* f) {
+  if (!f) return KS_ERR_INVALID_ARG;
+  std::memset(f, 0, sizeof(*f));
+  f->radius_m = 0.3f;
+  f->min_voxels = 8;
+  return KS_OK;
+}
+
+// the work space of an update over nt tiles that finds nc components: per voxel the forest, the ids, the class
+// byte and the face count; per tile the two bit planes; per component the accumulator, the record, two keys and three words
+static uint64_t frontiers_workspace(uint64_t nt, uint64_t nc) {
+  return nt * kTileVoxels * 10 + nt * 128 + sizeof(ObjCounters) + sizeof(FrCounters) + nc * (sizeof(FrAcc) + sizeof(ks_frontier) + 2 * 8 + 3 * 4);
+}
+
+int ks_frontiers_update(ks_ctx* c, const ks_frontier_config* f, ks_frontier_stats* stats) {
+  if (!c || !f) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_frontiers_update";
+  if (!std::isfinite(f->radius_m) || f->radius_m < 0.0f) return nav_refuse(c, who, "radius_m must be finite and not negative");
+  if (f->min_voxels < 1) return nav_refuse(c, who, "min_voxels must be at least 1");
+  if (f->use_bounds)
+    for (int k = 0; k < 3; ++k)
+      if (f->bounds_min[k] > f->bounds_max[k]) return nav_refuse(c, who, "a bounds_min lies above its bounds_max");
+  if (int rc = nav_begin(c, who)) return rc;
+  if (int rc = esdf_ready(c, who)) return rc;
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->esdf_tiles;
+  if (nt >= (1u << 23)) {   // (a voxel's id is slot * 512 + local in 32 bits, all-ones = none)
+    c->err = std::string(who) + ": too many tiles for one call";
+    return KS_ERR_UNSUPPORTED;
+  }
+  const size_t nvox = (size_t)nt * kTileVoxels;
+  const bool with_field = c->nav_valid && c->nav_tiles == nt;   // (a stored field is a snapshot of this same store)
+  int rc;
+  drop_frontiers(c);   // (a failure below leaves nothing stored)
+  if ((rc = c->fr_ids.reserve(c, nvox, ((size_t)nt + nt / 2 + 64) * kTileVoxels)) || (rc = c->fr_parent.reserve(c, nvox, nvox + nvox / 2)) ||
+      (rc = c->fr_cls.reserve(c, nvox, nvox + nvox / 2)) || (rc = c->fr_faces.reserve(c, nvox, nvox + nvox / 2)) ||
+      (rc = c->fr_planes.reserve(c, (size_t)nt * 16, ((size_t)nt + nt / 2) * 16)) || (rc = c->fr_numbered.reserve(c, 1, 1)) ||
+      (rc = c->fr_counters.reserve(c, 1, 1)))
+    return rc;
+  HIPCHK(c, hipMemsetAsync(c->fr_numbered, 0, sizeof(ObjCounters), st));
+  HIPCHK(c, hipMemsetAsync(c->fr_counters, 0, sizeof(FrCounters), st));
+  FrParams F{};
+  F.radius = f->radius_m;
+  F.min_voxels = f->min_voxels;
+  F.use_bounds = f->use_bounds ? 1 : 0;
+  for (int k = 0; k < 3; ++k) F.bmin[k] = f->bounds_min[k], F.bmax[k] = f->bounds_max[k];
+  F.nt = nt;
+  ObjParams O{};   // (k_obj_seams reads the tile count alone)
+  O.nt = nt;
+  ObjCounters numbered{};
+  FrCounters counts{};
+  if (nt) {
+    // 1) the bit planes, the classes and the in-tile forest; seams, flat forest and provisional numbers as the objects do
+    hipLaunchKernelGGL(k_fr_planes, dim3(nt * 2), dim3(256), 0, st, c->table, F, (const EsdfRecord*)c->esdf_store.get(), c->fr_planes.get(),
+                       c->fr_counters.get());
+    hipLaunchKernelGGL(k_fr_classify, dim3(nt), dim3(512), 0, st, c->table, F, (const unsigned long long*)c->fr_planes.get(), c->fr_cls.get(),
+                       c->fr_faces.get(), c->fr_parent.get(), c->fr_counters.get());
+    hipLaunchKernelGGL(k_obj_seams, dim3(nt), dim3(512), 0, st, c->table, O, (const uint8_t*)c->fr_cls.get(), c->fr_parent.get());
+    hipLaunchKernelGGL(k_obj_number, dim3(nt * 2), dim3(256), 0, st, c->fr_parent.get(), c->fr_ids.get(), c->fr_numbered.get());
+    HIPCHK(c, hipMemcpyAsync(&numbered, c->fr_numbered, sizeof(numbered), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the one read that sizes what follows
+    const uint32_t nc = numbered.n_components;
+    if (nc) {
+      // 2) reduce, join with the field, filter, order, assign
+      const size_t cap = (size_t)nc + nc / 2;
+      if ((rc = c->fr_acc.reserve(c, nc, cap)) || (rc = c->fr_final.reserve(c, nc, cap)) || (rc = c->fr_records.reserve(c, nc, cap))) return rc;
+      for (int k = 0; k < 2; ++k)
+        if ((rc = c->fr_keys[k].reserve(c, nc, cap)) || (rc = c->fr_vals[k].reserve(c, nc, cap))) return rc;
+      const dim3 per_comp((nc + 255) / 256);
+      const uint32_t* field = with_field ? (const uint32_t*)c->nav_cost.get() : nullptr;
+      hipLaunchKernelGGL(k_fr_acc_init, per_comp, dim3(256), 0, st, c->fr_acc.get(), nc);
+      hipLaunchKernelGGL(k_fr_reduce, dim3(nt * 2), dim3(256), 0, st, c->table, (const uint8_t*)c->fr_faces.get(), field, c->fr_parent.get(),
+                         (const uint32_t*)c->fr_ids.get(), c->fr_acc.get());
+      if (field)
+        hipLaunchKernelGGL(k_fr_nav_pick, dim3(nt * 2), dim3(256), 0, st, c->table, field, (const uint32_t*)c->fr_parent.get(), c->fr_acc.get());
+      hipLaunchKernelGGL(k_fr_keys, per_comp, dim3(256), 0, st, (const FrAcc*)c->fr_acc.get(), nc, F.min_voxels, c->fr_keys[0].get(),
+                         c->fr_vals[0].get(), c->fr_counters.get());
+      uint64_t* keys = nullptr;
+      uint32_t* vals = nullptr;
+      if ((rc = sort_pairs(c, c->fr_keys[0].get(), c->fr_keys[1].get(), c->fr_vals[0].get(), c->fr_vals[1].get(), nc, 64, &keys, &vals))) return rc;
+      hipLaunchKernelGGL(k_fr_records, per_comp, dim3(256), 0, st, (const FrAcc*)c->fr_acc.get(), nc, (const uint64_t*)keys, (const uint32_t*)vals,
+                         c->fr_records.get(), c->fr_final.get());
+    }
+    hipLaunchKernelGGL(k_obj_ids, dim3((uint32_t)((nvox + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->fr_parent.get(),
+                       (const uint32_t*)c->fr_final.get(), c->fr_ids.get(), nvox);
+    HIPCHK(c, hipMemcpyAsync(&counts, c->fr_counters, sizeof(counts), hipMemcpyDeviceToHost, st));
+  }
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->fr_valid = true;
+  c->fr_tiles = nt;
+  c->fr_count = counts.n_frontiers;
+  if (stats) {
+    stats->voxels_traversable = counts.traversable;
+    stats->voxels_frontier = counts.frontier_voxels;
+    stats->components = numbered.n_components;
+    stats->frontiers = counts.n_frontiers;
+    stats->voxels_in_frontiers = counts.voxels_in_frontiers;
+    stats->largest_frontier_voxels = counts.largest;
+    stats->unknown_faces = counts.unknown_faces;
+    stats->nav_field_used = with_field ? 1 : 0;
+    stats->workspace_bytes = frontiers_workspace(nt, numbered.n_components);
+  }
+  return KS_OK;
+}
+
+static int frontiers_read_begin(ks_ctx* c, const char* who) {
+  if (int rc = nav_begin(c, who)) return rc;
+  if (!c->fr_valid)
+    return nav_refuse(c, who, "no frontiers are stored (ks_frontiers_update has not run since the ESDF store or the map last changed)");
+  return KS_OK;
+}
+
+int ks_frontiers_size(ks_ctx* c, size_t* n) {
+  if (!c || !n) return KS_ERR_INVALID_ARG;
+  if (int rc = frontiers_read_begin(c, "ks_frontiers_size")) return rc;
+  *n = c->fr_count;
+  return KS_OK;
+}
+
+int ks_frontiers_download(ks_ctx* c, ks_frontier* out, size_t cap, size_t* n) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = frontiers_read_begin(c, "ks_frontiers_download")) return rc;
+  if (n) *n = c->fr_count;
+  if (cap < c->fr_count || (c->fr_count && !out)) return nav_refuse(c, "ks_frontiers_download", "output buffer too small");
+  if (c->fr_count) HIPCHK(c, hipMemcpy(out, c->fr_records.get(), c->fr_count * sizeof(ks_frontier), hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+
+int ks_frontiers_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, uint32_t* out) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_frontiers_download_blocks";
+  if (n && (!idx || !out)) return nav_refuse(c, who, "block_idx_xyz or out is NULL");
+  if (int rc = frontiers_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const int vps = c->cfg.voxels_per_side;
+  const size_t nv = (size_t)vps * vps * vps;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(64) << 20) / (nv * sizeof(uint32_t))), 65535);   // <= 64 MiB staged at a time
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->fr_out.reserve(c, m_max * nv, m_max * nv)) || (rc = c->fr_idx.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->fr_idx, idx + 3 * off, m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_download, dim3((uint32_t)((nv + 255) / 256), (uint32_t)m), dim3(256), 0, c->stream, c->table,
+                       (const uint32_t*)c->fr_ids.get(), c->fr_tiles, (const int32_t*)c->fr_idx.get(), vps, c->fr_out.get());
+    HIPCHK(c, hipMemcpyAsync(out + off * nv, c->fr_out, m * nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_frontiers_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* id) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_frontiers_query";
+  if (n && (!xyz || !id)) return nav_refuse(c, who, "xyz or id is NULL");
+  if (int rc = frontiers_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const size_t m_max = std::min(size_t(1) << 22, n);
+  int rc;
+  if ((rc = c->fr_out.reserve(c, m_max, m_max)) || (rc = c->fr_xyz.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->fr_xyz, xyz + 3 * off, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_query, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, (const uint32_t*)c->fr_ids.get(),
+                       c->fr_tiles, (const float*)c->fr_xyz.get(), m, c->voxel_size_inv, c->fr_out.get());
+    HIPCHK(c, hipMemcpyAsync(id + off, c->fr_out, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
 // ---- voxel-level host sync -------------------------------------------------------------------------------
 // Device-side address of a host allocation the GPU can write (hipHostMalloc'ed: ks_host_alloc), else nullptr.
 static void* device_view_of_pinned(void* p) {
@@ -5613,6 +5821,8 @@ static void mesh_reset(ks_ctx* c) {
   c->obj_count = 0;
   c->nav_valid = false;    // ... and the navigation field
   c->nav_tiles = 0;
+  drop_frontiers(c);       // ... and the frontiers
+  c->fr_tiles = 0;
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {
@@ -5706,6 +5916,7 @@ static int remove_tiles(ks_ctx* c, ks_remove_stats* stats) {
   }
   if (n_removed == 0) return KS_OK;
   c->nav_valid = false;   // slots move below and the navigation field does not follow
+  drop_frontiers(c);      // ... nor do the frontier ids (§21)
   if ((rc = snap.fetch_keys(c))) return rc;
   // 1) what leaves: tile positions and blocks, ascending
   std::vector<uint64_t> gone_tiles;

@@ -413,6 +413,48 @@ int main(int argc, char** argv) {
                 (unsigned long long)ps.waypoints);
   }
 
+  // KS_DEMO_FRONTIERS=<file>: where an explorer may go next, on the device without any layer sync — updateEsdf (min_distance_m 0.1,
+  // max_distance_m 0.4), updateNavField (radius 0.2 m) with the last frame's position as the one goal, then extractFrontiers (radius
+  // 0.2 m, the other options default), written as { u32 frontiers; f32 goal[3]; u64 stats[9] (ks_frontier_stats); the 88-byte
+  // records; per frontier f32 centroid[3], f32 target[3] }
+  if (const char* frontiers_path = std::getenv("KS_DEMO_FRONTIERS")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    hip->updateEsdf(eo, &esdf);
+    vxb::Pointcloud goals;
+    goals.push_back(vxb::Point(last_T[4], last_T[5], last_T[6]));
+    kimera::HipSemanticTsdfIntegrator::NavOptions no;
+    no.radius_m = 0.2f;
+    hip->updateNavField(goals, no);
+    kimera::HipSemanticTsdfIntegrator::FrontierOptions fo;
+    fo.radius_m = 0.2f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::Frontier> frontiers;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->extractFrontiers(fo, &frontiers);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* ff = std::fopen(frontiers_path, "wb");
+    if (!ff) return 9;
+    const uint32_t n_frontiers = frontiers.size();
+    const ks_frontier_stats& fs = hip->lastFrontierStats();
+    std::fwrite(&n_frontiers, 4, 1, ff);
+    std::fwrite(goals.data(), 12, 1, ff);
+    std::fwrite(&fs, sizeof(fs), 1, ff);
+    for (const auto& f : frontiers) std::fwrite(&f.record, sizeof(ks_frontier), 1, ff);
+    uint32_t reached = 0;
+    for (const auto& f : frontiers) {
+      const float m[6] = {f.centroid.x(), f.centroid.y(), f.centroid.z(), f.target.x(), f.target.y(), f.target.z()};
+      std::fwrite(m, 4, 6, ff);
+      reached += f.record.nav_cost <= KS_NAV_MAX_COST;
+    }
+    std::fclose(ff);
+    std::printf("adapter_demo: extractFrontiers %.3f ms, %u frontiers of %llu components, %llu of %llu frontier voxels in them, %u reached by the field\n", ms,
+                n_frontiers, (unsigned long long)fs.components, (unsigned long long)fs.voxels_in_frontiers, (unsigned long long)fs.voxels_frontier, reached);
+  }
+
   // KS_DEMO_OBJECTS=<file>: the object instances of the map, made on the device without any layer sync (extractObjects,
   // default options), written as { u32 objects; per object: u32 label, u32 n_voxels, i64 first_voxel[3], i64 bb_min[3],
   // i64 bb_max[3], f32 centroid[3] }

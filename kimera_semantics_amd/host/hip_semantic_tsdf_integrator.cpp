@@ -559,6 +559,37 @@ bool HipSemanticTsdfIntegrator::extractObjects(const ObjectOptions& options, std
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::extractFrontiers(const FrontierOptions& options, std::vector<Frontier>* out) {
+  CHECK_NOTNULL(out);
+  out->clear();
+  ks_frontier_config fc;
+  ks_frontiers_default_config(&fc);
+  fc.radius_m = options.radius_m;
+  fc.min_voxels = options.min_voxels;
+  fc.use_bounds = options.use_bounds ? 1 : 0;
+  for (int k = 0; k < 3; ++k) {
+    fc.bounds_min[k] = static_cast<int32_t>(options.bounds_min[k]);
+    fc.bounds_max[k] = static_cast<int32_t>(options.bounds_max[k]);
+  }
+  check(ks_frontiers_update(ctx_, &fc, &last_frontier_stats_), "ks_frontiers_update");
+  size_t n = 0;
+  check(ks_frontiers_size(ctx_, &n), "ks_frontiers_size");
+  if (n == 0) return false;
+  std::vector<ks_frontier> rec(n);
+  check(ks_frontiers_download(ctx_, rec.data(), n, &n), "ks_frontiers_download");
+  const float voxel_size = semantic_layer_ptr_->voxel_size();
+  out->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    Frontier& f = (*out)[i];
+    f.record = rec[i];
+    for (int k = 0; k < 3; ++k) {
+      f.centroid[k] = static_cast<float>((static_cast<double>(rec[i].sum[k]) / static_cast<double>(rec[i].n_voxels) + 0.5) * static_cast<double>(voxel_size));
+      f.target[k] = (static_cast<float>(rec[i].nav_voxel[k]) + 0.5f) * voxel_size;
+    }
+  }
+  return true;
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

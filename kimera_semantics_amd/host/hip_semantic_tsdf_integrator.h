@@ -279,6 +279,24 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// Returns true when `out` is not empty.
   bool extractObjects(const ObjectOptions& options, std::vector<ObjectInstance>* out);
   const ks_objects_stats& lastObjectsStats() const { return last_objects_stats_; }
+  /// Where an explorer may go next (ks_frontiers_update; the contract is DESIGN.md, "Exploration frontiers"): the voxels of the
+  /// STORED ESDF a sphere of radius_m may occupy that border space nobody has observed, clustered into 26-connected components ON THE
+  /// DEVICE and joined with the navigation field, if updateNavField() has stored one.  Call updateEsdf() / refreshEsdf() first.
+  /// Frontiers ascend by their smallest voxel (x, y, z).  The bounds are inclusive global voxel indices.
+  struct FrontierOptions {
+    float radius_m = 0.3f;
+    uint32_t min_voxels = 8;
+    bool use_bounds = false;
+    vxb::GlobalIndex bounds_min = vxb::GlobalIndex(0, 0, 0), bounds_max = vxb::GlobalIndex(0, 0, 0);
+  };
+  struct Frontier {
+    vxb::Point centroid;   ///< metres, world frame
+    vxb::Point target;     ///< metres: the centre of record.nav_voxel, a valid start for planPaths()
+    ks_frontier record;    ///< nav_cost is KS_NAV_UNREACHED when the field does not reach it, or none is stored
+  };
+  /// Returns true when `out` is not empty.
+  bool extractFrontiers(const FrontierOptions& options, std::vector<Frontier>* out);
+  const ks_frontier_stats& lastFrontierStats() const { return last_frontier_stats_; }
   /// Fuses the map of another integrator into this one at a rigid pose ON THE DEVICE (ks_fuse_map; the contract is DESIGN.md,
   /// section 17): the submap's TSDF and semantics are resampled under T_G_S (submap frame -> this map's frame) into this map's grid and
   /// folded in by the layer-merge rule — what a server does with a layer it receives on Voxblox's tsdf_map_in
@@ -314,6 +332,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};
   ks_objects_stats last_objects_stats_{};
+  ks_frontier_stats last_frontier_stats_{};
   ks_remove_stats last_remove_stats_{};
   ks_fuse_stats last_fuse_stats_{};
   vxb::FloatingPoint prune_distance_ = std::numeric_limits<vxb::FloatingPoint>::max();

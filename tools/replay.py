@@ -17,7 +17,7 @@ into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and 
 writes the cost-to-go field of the final ESDF to that goal for a robot of --nav-radius, made on the device (ks_nav_update), with the
 path from the last camera position; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] \\
+      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
@@ -78,6 +78,10 @@ def main():
     ap.add_argument("--objects", metavar="OUT.npz", help="cluster the surface voxels of every label into object instances at the end of the replay and "
                     "write them (records (n,) of 72 bytes ascending by first_voxel, centroids_m (n, 3), label_names (n,), voxel_size)")
     ap.add_argument("--objects-min-voxels", type=int, default=8, metavar="N")
+    ap.add_argument("--frontiers", metavar="OUT.npz", help="extract the exploration frontiers of the final ESDF on the device (ks_frontiers_update) for a "
+                    "robot of --nav-radius and write them (records (n,) of 88 bytes ascending by first_voxel, centroids_m, targets_m, stats, "
+                    "block_indices and the per-block ids); needs --esdf; with --nav-goal the records carry the cost-to-go from that goal")
+    ap.add_argument("--frontiers-min-voxels", type=int, default=8, metavar="N")
     ap.add_argument("--max-block-distance", type=float, default=None, metavar="M", help="after every frame remove the blocks whose origin is further "
                     "than M metres from the sensor position (ks_remove_distant_blocks; completes the frames in flight)")
     ap.add_argument("--submap-frames", type=int, default=0, metavar="N", help="integrate every N frames into a second context, in the frame of "
@@ -90,6 +94,8 @@ def main():
         ap.error("--nav-out and --nav-goal go together")
     if a.nav_out and not (a.esdf or a.esdf_every or a.esdf_slice):
         ap.error("--nav-out plans over the stored ESDF: give --esdf, --esdf-every or --esdf-slice as well")
+    if a.frontiers and not a.esdf:
+        ap.error("--frontiers reads the stored ESDF: give --esdf as well")
     if a.nav_goal:
         try:
             nav_goal = np.array([float(v) for v in a.nav_goal.split(",")], np.float32)
@@ -302,6 +308,20 @@ def main():
               f"usable), largest cost {st['largest_cost']}, {st['rounds']} rounds, {st['tile_relaxations']} tile relaxations; the path from the last camera "
               f"position {what}: {n_wp} waypoints, about {int(path['cost'][0]) * a.voxel_size / 10 if n_wp else 0:.2f} m; {t_nav * 1e3:.2f} ms "
               f"(field + download + path) -> {a.nav_out}")
+    if a.frontiers:   # (after --nav-out: a stored field fills the join)
+        t1 = time.perf_counter()
+        rec, st = integ.frontiers(radius_m=a.nav_radius, min_voxels=a.frontiers_min_voxels)
+        idx = integ.block_indices()
+        ids = integ.frontier_ids(idx)
+        t_fr = time.perf_counter() - t1
+        np.savez_compressed(a.frontiers, records=rec, centroids_m=B.frontier_centroids(rec, integ.cfg.voxel_size),
+                            targets_m=B.frontier_targets(rec, integ.cfg.voxel_size), stats_names=np.array(list(st)), stats=np.array(list(st.values()), np.uint64),
+                            block_indices=idx, ids=ids, radius_m=np.float32(a.nav_radius), voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+        reached = int((rec["nav_cost"] <= B.KS_NAV_MAX_COST).sum())
+        print(f"frontiers: {st['frontiers']} frontiers of {st['components']} components over {st['voxels_frontier']} frontier voxels "
+              f"({st['voxels_in_frontiers']} in frontiers, the largest {st['largest_frontier_voxels']}), {st['unknown_faces']} unknown faces, "
+              f"{reached} reached by the field" + ("" if st["nav_field_used"] else " (no field stored: give --nav-goal)") +
+              f", work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_fr * 1e3:.2f} ms (update + records + ids) -> {a.frontiers}")
     if a.objects:
         t1 = time.perf_counter()
         rec, st = integ.objects(min_voxels=a.objects_min_voxels)
