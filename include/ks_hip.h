@@ -694,6 +694,57 @@ int ks_frontiers_download(ks_ctx* ctx, ks_frontier* out, size_t cap, size_t* n);
 int ks_frontiers_download_blocks(ks_ctx* ctx, const int32_t* block_idx_xyz, size_t n, uint32_t* out /* n * vps^3 ids, host block layout */);
 int ks_frontiers_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* id);
 
+/* ---- view information gain over the stored ESDF: how much unobserved space each of n candidate camera poses would see (new: the
+ * hot loop of a next-best-view explorer, a ray caster on the host over a downloaded layer) ----
+ * The contract is DESIGN.md, section "View information gain"; it is this library's own.  The input is the ESDF STORE exactly as
+ * ks_nav_update reads it, with nothing refreshed; a voxel outside the store's tiles reads the default record.  A voxel is UNKNOWN
+ * iff bit 0 of its flags is clear, OCCUPIED iff observed and !(distance > stop_distance_m) (a NaN distance stops a ray), FREE
+ * otherwise.  One ray per pixel of a width x height pinhole image with K = {fx, fy, cx, cy}, its origin and direction by the rule of
+ * ks_render_view; samples at t_k = min_range_m + (float)k * step for k = 0 .. N - 1, N = (uint32_t)floorf((max_range_m -
+ * min_range_m) / step) + 1, step = step_m or the context's voxel_size; the voxel of a sample by the point-to-voxel rule of
+ * ks_esdf_query.  A ray ends OPEN before a sample that is not finite or outside the packed range, and after sample N - 1; it ends
+ * as a HIT at the first sample whose voxel is occupied (that sample counts).  Unknown voxels never stop a ray.
+ * A record counts the DISTINCT voxels the samples of a view's rays visit, by state (a voxel ten rays cross counts once); label_voxels
+ * those occupied ones whose nearest_label equals cfg.label (0 with label = 255); samples every counted sample.  flags bit 0: the
+ * view is valid.  A view whose T_G_C has a non-finite component, or whose rays leave the ball of max_range_m around its origin (a
+ * quaternion that is not of unit length), is data, not an error: an all-zero record.  Views are independent; two calls give the
+ * same bytes, and so do the same voxels uploaded in another block order.
+ * ks_view_gain          poses and records on the host.  ks_view_gain_device: DEVICE pointers, enqueued on ks_stream(ctx); the host
+ *                       is waited for only when stats is not NULL.  Both complete the frames in flight (their statistics stay
+ *                       owed) and only READ: nothing is stored, nothing of the context changes.  n = 0 is no error.
+ * stats: views_valid, views_invalid, the sums of the seven counters over the views, workspace_bytes and views_in_lds (DESIGN.md
+ * §22.2 gives the rule for both).
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; NULL poses or output with n > 0; no stored ESDF; width or height outside 1..1024 or
+ * width * height > 65536; K not finite or fx, fy not positive; a range or step that is negative or not finite; min_range_m >
+ * max_range_m; N > 4096; label > 255; n >= 2^24; a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of
+ * ks_integrate_round_exact; the work space of one view in flight exceeds max_workspace_bytes: stats->workspace_bytes says what that
+ * is, nothing else is done), KS_ERR_HIP.  Multi-GPU: each context sees the tiles it holds. */
+typedef struct ks_view_gain_config {
+  float min_range_m;     /* 0 */
+  float max_range_m;     /* 5 */
+  float step_m;          /* 0: the context's voxel_size */
+  float stop_distance_m; /* 0 */
+  uint32_t width;        /* 32 */
+  uint32_t height;       /* 24 */
+  float K[4];            /* fx, fy, cx, cy: no default, the caller sets it */
+  uint32_t label;        /* 255: none */
+  uint32_t pad;
+  uint64_t max_workspace_bytes; /* 1 GiB */
+} ks_view_gain_config; /* 56 bytes */
+typedef struct ks_view_gain_record {
+  uint32_t unknown_voxels, free_voxels, surface_voxels, label_voxels, rays_hit, rays_open, samples, flags;
+} ks_view_gain_record; /* 32 bytes */
+#define KS_VIEW_GAIN_VALID 1u
+typedef struct ks_view_gain_stats {
+  uint64_t views_valid, views_invalid, unknown_voxels, free_voxels, surface_voxels, label_voxels, rays_hit, rays_open, samples,
+      workspace_bytes, views_in_lds;
+} ks_view_gain_stats; /* 88 bytes */
+int ks_view_gain_default_config(ks_view_gain_config* cfg);
+int ks_view_gain(ks_ctx* ctx, const float* T_G_C /* host, n x 7 */, size_t n, const ks_view_gain_config* cfg,
+                 ks_view_gain_record* out /* host, n */, ks_view_gain_stats* stats /* may be NULL */);
+int ks_view_gain_device(ks_ctx* ctx, const float* d_T_G_C, size_t n, const ks_view_gain_config* cfg, ks_view_gain_record* d_out,
+                        ks_view_gain_stats* stats /* may be NULL */);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "ks_mesh_index", "ks_mesh_index_size", "ks_mesh_index_download",
     "ks_nav_default_config", "ks_nav_update", "ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks", "ks_nav_paths", "ks_nav_paths_device",
     "ks_frontiers_default_config", "ks_frontiers_update", "ks_frontiers_size", "ks_frontiers_download", "ks_frontiers_download_blocks", "ks_frontiers_query",
+    "ks_view_gain_default_config", "ks_view_gain", "ks_view_gain_device",
 ]
 
 
@@ -251,6 +252,38 @@ def frontier_bounds(box_min_m, box_max_m, voxel_size):
     return lo, hi
 
 
+class KsViewGainConfig(C.Structure):
+    _fields_ = [("min_range_m", C.c_float), ("max_range_m", C.c_float), ("step_m", C.c_float), ("stop_distance_m", C.c_float),
+                ("width", C.c_uint32), ("height", C.c_uint32), ("K", C.c_float * 4), ("label", C.c_uint32), ("pad", C.c_uint32),
+                ("max_workspace_bytes", C.c_uint64)]
+
+
+class KsViewGainStats(C.Structure):
+    _fields_ = [("views_valid", C.c_uint64), ("views_invalid", C.c_uint64), ("unknown_voxels", C.c_uint64), ("free_voxels", C.c_uint64),
+                ("surface_voxels", C.c_uint64), ("label_voxels", C.c_uint64), ("rays_hit", C.c_uint64), ("rays_open", C.c_uint64),
+                ("samples", C.c_uint64), ("workspace_bytes", C.c_uint64), ("views_in_lds", C.c_uint64)]
+
+
+# ks_view_gain_record: 32 bytes, one per candidate pose
+VIEW_GAIN_DTYPE = np.dtype([(k, "<u4") for k in ("unknown_voxels", "free_voxels", "surface_voxels", "label_voxels", "rays_hit", "rays_open",
+                                                  "samples", "flags")])
+KS_VIEW_GAIN_VALID = 1
+
+
+def view_gain_yaw_poses(xyz, n_yaws=8) -> np.ndarray:
+    """(n * n_yaws, 7) f32 candidate poses T_G_C for view_gain: at every position of xyz (n, 3) a level camera (optical axis
+    horizontal, image y pointing down the world's -z) turned about the world's z axis in n_yaws equal steps from +x."""
+    xyz = np.asarray(xyz, np.float64).reshape(-1, 3)
+    half = np.pi * np.arange(n_yaws) / n_yaws
+    cz, sz = np.cos(half), np.sin(half)
+    w0, x0, y0, z0 = 0.5, -0.5, 0.5, -0.5                       # camera z -> world x, camera x -> world -y, camera y -> world -z
+    q = np.stack([cz * w0 - sz * z0, cz * x0 - sz * y0, cz * y0 + sz * x0, cz * z0 + sz * w0], axis=1)   # (cz, 0, 0, sz) * q0
+    out = np.zeros((len(xyz), n_yaws, 7), np.float32)
+    out[:, :, :4] = q[None, :, :]
+    out[:, :, 4:] = xyz[:, None, :]
+    return out.reshape(-1, 7)
+
+
 KS_ALIGN_CONVERGED, KS_ALIGN_ITERATION_LIMIT, KS_ALIGN_TOO_FEW_INLIERS, KS_ALIGN_DEGENERATE = 0, 1, 2, 3
 
 
@@ -265,7 +298,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_view_gain.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -378,6 +411,9 @@ def lib():
         L.ks_frontiers_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ks_frontiers_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_frontiers_query.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_view_gain_default_config.argtypes = [C.POINTER(KsViewGainConfig)]
+        for name in ("ks_view_gain", "ks_view_gain_device"):
+            getattr(L, name).argtypes = [vp, vp, C.c_size_t, C.POINTER(KsViewGainConfig), vp, C.POINTER(KsViewGainStats)]
         L.ks_nav_default_config.argtypes = [C.POINTER(KsNavConfig)]
         L.ks_nav_update.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsNavConfig), C.POINTER(KsNavStats)]
         for name in ("ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks"):
@@ -888,6 +924,36 @@ class HipIntegrator:
         out = np.zeros(len(xyz), dtype=np.uint32)
         self._chk(lib().ks_frontiers_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
         return out
+
+    # ---- view information gain over the stored ESDF (DESIGN.md, section "View information gain") ----
+    def view_gain_config(self, K, width=None, height=None, **cfg) -> KsViewGainConfig:
+        vc = KsViewGainConfig()
+        lib().ks_view_gain_default_config(C.byref(vc))
+        vc.K = (C.c_float * 4)(*[float(a) for a in K])
+        for k, v in dict(cfg, width=width, height=height).items():
+            if k not in ("min_range_m", "max_range_m", "step_m", "stop_distance_m", "width", "height", "label", "max_workspace_bytes"):
+                raise AttributeError(k)
+            if v is not None:
+                setattr(vc, k, v)
+        return vc
+
+    def view_gain(self, poses, K, width=None, height=None, **cfg):
+        """ks_view_gain: for each candidate camera pose T_G_C (n, 7) the distinct unknown, free and surface voxels of the STORED ESDF
+        that the rays of a width x height pinhole image with K = (fx, fy, cx, cy) visit before a surface stops them.  Returns
+        (records (n,) VIEW_GAIN_DTYPE, stats dict).  cfg are the fields of KsViewGainConfig.  The contract is DESIGN.md, section
+        "View information gain"."""
+        T = np.ascontiguousarray(poses, dtype=np.float32).reshape(-1, 7)
+        vc, st = self.view_gain_config(K, width, height, **cfg), KsViewGainStats()
+        out = np.zeros(len(T), dtype=VIEW_GAIN_DTYPE)
+        self._chk(lib().ks_view_gain(self._h, _ptr(T), len(T), C.byref(vc), _ptr(out), C.byref(st)))
+        return out, {k: int(getattr(st, k)) for k, _ in KsViewGainStats._fields_}
+
+    def view_gain_device(self, d_poses: int, n: int, K, width=None, height=None, d_out: int = 0, stats=True, **cfg):
+        """ks_view_gain_device: raw device addresses (e.g. torch.Tensor.data_ptr()) of n x 7 floats and n 32-byte records.  The
+        kernels are enqueued on self.stream; with stats=False the host does not wait for them and None is returned."""
+        vc, st = self.view_gain_config(K, width, height, **cfg), KsViewGainStats()
+        self._chk(lib().ks_view_gain_device(self._h, d_poses or None, int(n), C.byref(vc), d_out or None, C.byref(st) if stats else None))
+        return {k: int(getattr(st, k)) for k, _ in KsViewGainStats._fields_} if stats else None
 
     # ---- navigation field over the stored ESDF (DESIGN.md, section "Navigation field") ----
     def nav_config(self, **cfg) -> KsNavConfig:

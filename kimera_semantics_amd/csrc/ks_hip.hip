@@ -75,6 +75,7 @@ using namespace ksd;
 #include "ks_k_objects.h"
 #include "ks_k_nav.h"
 #include "ks_k_frontier.h"
+#include "ks_k_view_gain.h"
 #include "ks_k_remove.h"
 #include "ks_k_fuse.h"
 
@@ -599,6 +600,14 @@ struct ks_ctx {
   bool fr_valid = false;
   uint32_t fr_tiles = 0;
   size_t fr_count = 0;
+  // ks_view_gain (ks_k_view_gain.h): nothing is stored between calls; the buffers grow only
+  DevBuf<unsigned long long> vg_planes;    // [esdf_tiles][8][observed | occupied | labelled | 0]: 256 B per tile
+  DevBuf<uint32_t> vg_slabs;               // [groups][slab_words]: the visited bitmaps of the views that do not fit the LDS
+  DevBuf<VgCounters> vg_counters;
+  DevBuf<float> vg_poses;                  // staging of the host entry
+  DevBuf<ks_view_gain_record> vg_records;
+  uint32_t vg_lds_bits = kVgLdsBits;       // KS_DEBUG=1 KS_VG_LDS_BITS=<n> (tests): the LDS budget in bits; 0: every view through global memory
+  uint32_t vg_groups = kVgMaxGroups;       // KS_DEBUG=1 KS_VG_GROUPS=<n> (tests): workgroups in flight
   // ks_remove_blocks / ks_remove_distant_blocks (ks_k_remove.h).  What the stored products still have to hear of a removal:
   std::vector<int32_t> removed_blocks;     // the blocks the LAST removal call took out, ascending (ks_removed_blocks)
   std::vector<uint64_t> mesh_removed;      // block words removed since the last ks_mesh_update, ascending: it reports them as
@@ -2946,6 +2955,9 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   if (const char* e = dbg_env("KS_ESDF_READ_CHUNK")) c->esdf_read_chunk = std::max<size_t>(1, (size_t)atoll(e));
   // (tests: host-pointer reads of the navigation field that cross several chunk boundaries)
   if (const char* e = dbg_env("KS_NAV_CHUNK")) c->nav_chunk = std::max<size_t>(1, (size_t)atoll(e));
+  // (tests: views of a few thousand voxels on the global path, a box just below and above the budget; one bitmap reused by every view)
+  if (const char* e = dbg_env("KS_VG_LDS_BITS")) c->vg_lds_bits = (uint32_t)std::min<long long>(std::max<long long>(0, atoll(e)), (long long)kVgLdsBits);
+  if (const char* e = dbg_env("KS_VG_GROUPS")) c->vg_groups = (uint32_t)std::min<long long>(std::max<long long>(1, atoll(e)), (long long)kVgMaxGroups);
   if (eo_marks_first > eo_marks0) c->eo_want_marks.store(eo_marks_first, std::memory_order_relaxed);
   if (ensure_points(c, cfg->max_points) != KS_OK || ensure_exact_slots(c, eo_marks0, eo_x0) != KS_OK) {
     g_create_error = c->err;
@@ -5071,6 +5083,134 @@ int ks_frontiers_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* id) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
   }
   HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+// ---- view information gain over the stored ESDF ("View information gain"; ks_k_view_gain.h) -------
+int ks_view_gain_default_config(ks_view_gain_config* g) {
+  if (!g) return KS_ERR_INVALID_ARG;
+  std::memset(g, 0, sizeof(*g));
+  g->max_range_m = 5.0f;
+  g->width = 32;
+  g->height = 24;
+  g->label = 255;
+  g->max_workspace_bytes = uint64_t(1) << 30;
+  return KS_OK;
+}
+
+// the checks of both calls and the sizing rule of DESIGN.md §22.2, then both kernels on the context's stream: DEVICE records out;
+// the poses are DEVICE memory, or with `staged` host memory that goes through the context's staging (the records then land in
+// c->vg_records).  The host is not waited for here.  *launched = false: nothing to do (n = 0).
+static int view_gain_enqueue(ks_ctx* c, const char* who, const float* poses, bool staged, size_t n, const ks_view_gain_config* g,
+                             ks_view_gain_record* d_out, ks_view_gain_stats* stats, bool* launched) {
+  *launched = false;
+  if (n && (!poses || !d_out)) return nav_refuse(c, who, "T_G_C or out is NULL");
+  if (g->width < 1 || g->width > 1024 || g->height < 1 || g->height > 1024 || g->width * g->height > 65536)
+    return nav_refuse(c, who, "width and height must lie in 1..1024 and width * height in 1..65536");
+  for (int k = 0; k < 4; ++k)
+    if (!std::isfinite(g->K[k])) return nav_refuse(c, who, "K must be finite");
+  if (!(g->K[0] > 0.0f) || !(g->K[1] > 0.0f)) return nav_refuse(c, who, "fx and fy must be positive");
+  const float par[4] = {g->min_range_m, g->max_range_m, g->step_m, g->stop_distance_m};
+  for (float v : par)
+    if (!std::isfinite(v) || v < 0.0f) return nav_refuse(c, who, "min_range_m, max_range_m, step_m and stop_distance_m must be finite and not negative");
+  if (g->min_range_m > g->max_range_m) return nav_refuse(c, who, "min_range_m lies above max_range_m");
+  if (g->label > 255) return nav_refuse(c, who, "label lies above 255");
+  if (n >= (size_t(1) << 24)) return nav_refuse(c, who, "n must lie below 2^24");
+  const float step = g->step_m > 0.0f ? g->step_m : c->cfg.voxel_size;
+  const float n_steps = floorf((g->max_range_m - g->min_range_m) / step);
+  if (!(n_steps < 4096.0f)) return nav_refuse(c, who, "more than 4096 samples per ray");
+  if (int rc = nav_begin(c, who)) return rc;
+  if (int rc = esdf_ready(c, who)) return rc;
+  if (int rc = quiesce(c)) return rc;
+  if (n == 0) return KS_OK;
+  // the sizing rule: planes, counters, and one slab of the ball bound per workgroup in flight
+  const uint32_t nt = c->esdf_tiles;
+  const uint64_t side = 2 * (uint64_t)std::ceil((double)g->max_range_m / (double)c->cfg.voxel_size) + 3;
+  const uint64_t ball_bits = side * side * side;
+  const uint64_t slab_words = ((ball_bits + 31) / 32 + 63) / 64 * 64;   // (256-byte steps)
+  const uint64_t fixed = (uint64_t)nt * kVgTileWords * 8 + sizeof(VgCounters), slab_bytes = slab_words * 4;
+  if (g->max_workspace_bytes < fixed + slab_bytes) {
+    if (stats) stats->workspace_bytes = fixed + slab_bytes;
+    c->err = std::string(who) + ": one view in flight needs " + std::to_string(fixed + slab_bytes) + " bytes of work space, above max_workspace_bytes";
+    return KS_ERR_UNSUPPORTED;
+  }
+  const uint64_t groups = std::min<uint64_t>(std::min<uint64_t>(n, c->vg_groups), (g->max_workspace_bytes - fixed) / slab_bytes);
+  if (stats) stats->workspace_bytes = fixed + groups * slab_bytes;
+  int rc;
+  if ((rc = c->vg_planes.reserve(c, (size_t)nt * kVgTileWords, ((size_t)nt + nt / 2 + 64) * kVgTileWords)) || (rc = c->vg_counters.reserve(c, 1, 1)) ||
+      (rc = c->vg_slabs.reserve(c, (size_t)(groups * slab_words), (size_t)(groups * slab_words))))
+    return rc;
+  hipStream_t st = c->stream;
+  if (staged) {   // (the staging is idle: every earlier call waited for its read-back)
+    if ((rc = c->vg_poses.reserve(c, 7 * n, 7 * n)) || (rc = c->vg_records.reserve(c, n, n))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->vg_poses, poses, 7 * n * sizeof(float), hipMemcpyHostToDevice, st));
+    poses = c->vg_poses.get();
+    d_out = c->vg_records.get();
+  }
+  VgParams V{};
+  V.cx = g->K[2];
+  V.cy = g->K[3];
+  V.constant_x = (float)(1.0 / (double)g->K[0]);   // as ks_render_view
+  V.constant_y = (float)(1.0 / (double)g->K[1]);
+  V.width = (int)g->width;
+  V.height = (int)g->height;
+  V.voxel_size_inv = c->voxel_size_inv;
+  V.min_range = g->min_range_m;
+  V.step = step;
+  V.stop_distance = g->stop_distance_m;
+  V.n_samples = (uint32_t)n_steps + 1u;
+  V.label = g->label;
+  V.n_tiles = nt;
+  V.n_views = (uint32_t)n;
+  V.lds_bits = c->vg_lds_bits;
+  V.ball_bits = ball_bits;
+  V.slab_words = slab_words;
+  HIPCHK(c, hipMemsetAsync(c->vg_counters, 0, sizeof(VgCounters), st));
+  if (nt)
+    hipLaunchKernelGGL(k_vg_planes, dim3(nt * 2), dim3(256), 0, st, (const EsdfRecord*)c->esdf_store.get(), V.stop_distance, V.label, c->vg_planes.get());
+  hipLaunchKernelGGL(k_vg_walk, dim3((uint32_t)groups), dim3(kVgThreads), 0, st, c->table, V, poses, (const unsigned long long*)c->vg_planes.get(),
+                     c->vg_slabs.get(), d_out, c->vg_counters.get());
+  HIPCHK(c, hipGetLastError());
+  *launched = true;
+  return KS_OK;
+}
+
+// waits for the stream and reads the counters
+static int view_gain_stats(ks_ctx* c, ks_view_gain_stats* stats) {
+  VgCounters k{};
+  HIPCHK(c, hipMemcpyAsync(&k, c->vg_counters, sizeof(k), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  stats->views_valid = k.views_valid;
+  stats->views_invalid = k.views_invalid;
+  stats->unknown_voxels = k.unknown;
+  stats->free_voxels = k.free_;
+  stats->surface_voxels = k.surface;
+  stats->label_voxels = k.label;
+  stats->rays_hit = k.hit;
+  stats->rays_open = k.open;
+  stats->samples = k.samples;
+  stats->views_in_lds = k.views_in_lds;
+  return KS_OK;
+}
+
+int ks_view_gain_device(ks_ctx* c, const float* d_T, size_t n, const ks_view_gain_config* g, ks_view_gain_record* d_out, ks_view_gain_stats* stats) {
+  if (!c || !g) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  bool launched = false;
+  if (int rc = view_gain_enqueue(c, "ks_view_gain_device", d_T, false, n, g, d_out, stats, &launched)) return rc;
+  return stats && launched ? view_gain_stats(c, stats) : KS_OK;
+}
+
+int ks_view_gain(ks_ctx* c, const float* T, size_t n, const ks_view_gain_config* g, ks_view_gain_record* out, ks_view_gain_stats* stats) {
+  if (!c || !g) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  bool launched = false;
+  if (int rc = view_gain_enqueue(c, "ks_view_gain", T, true, n, g, out, stats, &launched)) return rc;
+  hipStream_t st = c->stream;
+  if (!launched) return KS_OK;
+  HIPCHK(c, hipMemcpyAsync(out, c->vg_records, n * sizeof(ks_view_gain_record), hipMemcpyDeviceToHost, st));
+  if (stats) return view_gain_stats(c, stats);
+  HIPCHK(c, hipStreamSynchronize(st));
   return KS_OK;
 }
 

@@ -455,6 +455,65 @@ int main(int argc, char** argv) {
                 n_frontiers, (unsigned long long)fs.components, (unsigned long long)fs.voxels_in_frontiers, (unsigned long long)fs.voxels_frontier, reached);
   }
 
+  // KS_DEMO_VIEW_GAIN=<file>: how much unobserved space candidate views would see, on the device without any layer sync — updateEsdf
+  // (min_distance_m 0.1, max_distance_m 0.4), then scoreViews for the last frame's pose turned about the world's z axis in 8 steps of
+  // 45 degrees: 16 x 12 rays of a 90-degree image, 3 m range, label 4 counted; written as { u32 views, width, height, label; f32 K[4];
+  // f32 max_range_m; u32 0; u64 stats[11] (ks_view_gain_stats); the poses (7 f32 each); the 32-byte records }
+  if (const char* gain_path = std::getenv("KS_DEMO_VIEW_GAIN")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    hip->updateEsdf(eo, &esdf);
+    kimera::HipSemanticTsdfIntegrator::ViewGainOptions vo;
+    vo.max_range_m = 3.0f;
+    vo.width = 16;
+    vo.height = 12;
+    vo.fx = vo.fy = 8.0f;
+    vo.cx = 7.5f;
+    vo.cy = 5.5f;
+    vo.label = 4;
+    std::vector<vxb::Transformation> views;
+    std::vector<float> poses;
+    for (int k = 0; k < 8; ++k) {
+      const double half = 0.5 * k * 0.78539816339744831, cz = std::cos(half), sz = std::sin(half);
+      const double q[4] = {last_T[0], last_T[1], last_T[2], last_T[3]};
+      // (cz, 0, 0, sz) * q: the camera's orientation turned about the world's z axis
+      const float p[7] = {static_cast<float>(cz * q[0] - sz * q[3]), static_cast<float>(cz * q[1] - sz * q[2]), static_cast<float>(cz * q[2] + sz * q[1]),
+                          static_cast<float>(cz * q[3] + sz * q[0]), last_T[4], last_T[5], last_T[6]};
+      views.push_back(vxb::Transformation(p[0], p[1], p[2], p[3], vxb::Point(p[4], p[5], p[6])));
+      const vxb::Transformation& T = views.back();   // (what scoreViews reads)
+      const float back[7] = {T.qw(), T.qvec().x(), T.qvec().y(), T.qvec().z(), T.getPosition().x(), T.getPosition().y(), T.getPosition().z()};
+      poses.insert(poses.end(), back, back + 7);
+    }
+    std::vector<ks_view_gain_record> records;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->scoreViews(views, vo, &records);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* gf = std::fopen(gain_path, "wb");
+    if (!gf) return 9;
+    const uint32_t head[4] = {static_cast<uint32_t>(views.size()), vo.width, vo.height, vo.label};
+    const float K[4] = {vo.fx, vo.fy, vo.cx, vo.cy};
+    const uint32_t zero = 0;
+    const ks_view_gain_stats& gs = hip->lastViewGainStats();
+    std::fwrite(head, 4, 4, gf);
+    std::fwrite(K, 4, 4, gf);
+    std::fwrite(&vo.max_range_m, 4, 1, gf);
+    std::fwrite(&zero, 4, 1, gf);
+    std::fwrite(&gs, sizeof(gs), 1, gf);
+    std::fwrite(poses.data(), 4, poses.size(), gf);
+    std::fwrite(records.data(), sizeof(ks_view_gain_record), records.size(), gf);
+    std::fclose(gf);
+    size_t best = 0;
+    for (size_t i = 1; i < records.size(); ++i)
+      if (records[i].unknown_voxels > records[best].unknown_voxels) best = i;
+    std::printf("adapter_demo: scoreViews %.3f ms, %zu views, %llu unknown / %llu free / %llu surface voxels in all, the best view (%zu) sees %u unknown voxels\n", ms,
+                records.size(), (unsigned long long)gs.unknown_voxels, (unsigned long long)gs.free_voxels, (unsigned long long)gs.surface_voxels, best,
+                records.empty() ? 0u : records[best].unknown_voxels);
+  }
+
   // KS_DEMO_OBJECTS=<file>: the object instances of the map, made on the device without any layer sync (extractObjects,
   // default options), written as { u32 objects; per object: u32 label, u32 n_voxels, i64 first_voxel[3], i64 bb_min[3],
   // i64 bb_max[3], f32 centroid[3] }

@@ -590,6 +590,33 @@ bool HipSemanticTsdfIntegrator::extractFrontiers(const FrontierOptions& options,
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::scoreViews(const std::vector<vxb::Transformation>& T_G_C, const ViewGainOptions& options,
+                                           std::vector<ks_view_gain_record>* out) {
+  CHECK_NOTNULL(out);
+  ks_view_gain_config vc;
+  ks_view_gain_default_config(&vc);
+  vc.min_range_m = options.min_range_m;
+  vc.max_range_m = options.max_range_m;
+  vc.step_m = options.step_m;
+  vc.stop_distance_m = options.stop_distance_m;
+  vc.width = options.width;
+  vc.height = options.height;
+  vc.K[0] = options.fx;
+  vc.K[1] = options.fy;
+  vc.K[2] = options.cx;
+  vc.K[3] = options.cy;
+  vc.label = options.label;
+  std::vector<float> poses(7 * T_G_C.size());
+  for (size_t i = 0; i < T_G_C.size(); ++i) {
+    const vxb::Transformation& T = T_G_C[i];
+    const float p[7] = {T.qw(), T.qvec().x(), T.qvec().y(), T.qvec().z(), T.getPosition().x(), T.getPosition().y(), T.getPosition().z()};
+    std::copy(p, p + 7, poses.begin() + 7 * i);
+  }
+  out->assign(T_G_C.size(), ks_view_gain_record{});
+  check(ks_view_gain(ctx_, poses.data(), T_G_C.size(), &vc, out->data(), &last_view_gain_stats_), "ks_view_gain");
+  return !out->empty();
+}
+
 HipSemanticTsdfIntegrator::Workers::~Workers() {
   {
     std::lock_guard<std::mutex> lk(mu_);

@@ -297,6 +297,21 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// Returns true when `out` is not empty.
   bool extractFrontiers(const FrontierOptions& options, std::vector<Frontier>* out);
   const ks_frontier_stats& lastFrontierStats() const { return last_frontier_stats_; }
+  /// How much unobserved space each candidate camera pose would see (ks_view_gain; the contract is DESIGN.md, "View information
+  /// gain"): the distinct unknown, free and surface voxels of the STORED ESDF that the rays of a small pinhole image visit before a
+  /// surface stops them, counted ON THE DEVICE.  Call updateEsdf() / refreshEsdf() first.  One record per pose, in the order of the poses;
+  /// a pose with a non-finite component gets an all-zero record.
+  struct ViewGainOptions {
+    float min_range_m = 0.0f, max_range_m = 5.0f;
+    float step_m = 0.0f;            ///< 0: the voxel size
+    float stop_distance_m = 0.0f;
+    uint32_t width = 32, height = 24;
+    float fx = 0.0f, fy = 0.0f, cx = 0.0f, cy = 0.0f;   ///< no default: the caller sets them
+    uint32_t label = 255;           ///< 255: no label is counted
+  };
+  /// Returns true when `out` is not empty.
+  bool scoreViews(const std::vector<vxb::Transformation>& T_G_C, const ViewGainOptions& options, std::vector<ks_view_gain_record>* out);
+  const ks_view_gain_stats& lastViewGainStats() const { return last_view_gain_stats_; }
   /// Fuses the map of another integrator into this one at a rigid pose ON THE DEVICE (ks_fuse_map; the contract is DESIGN.md,
   /// section 17): the submap's TSDF and semantics are resampled under T_G_S (submap frame -> this map's frame) into this map's grid and
   /// folded in by the layer-merge rule — what a server does with a layer it receives on Voxblox's tsdf_map_in
@@ -333,6 +348,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_align_stats last_align_stats_{};
   ks_objects_stats last_objects_stats_{};
   ks_frontier_stats last_frontier_stats_{};
+  ks_view_gain_stats last_view_gain_stats_{};
   ks_remove_stats last_remove_stats_{};
   ks_fuse_stats last_fuse_stats_{};
   vxb::FloatingPoint prune_distance_ = std::numeric_limits<vxb::FloatingPoint>::max();

@@ -17,7 +17,7 @@ into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and 
 writes the cost-to-go field of the final ESDF to that goal for a robot of --nav-radius, made on the device (ks_nav_update), with the
 path from the last camera position; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] \\
+      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] [--view-gain out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
@@ -82,6 +82,12 @@ def main():
                     "robot of --nav-radius and write them (records (n,) of 88 bytes ascending by first_voxel, centroids_m, targets_m, stats, "
                     "block_indices and the per-block ids); needs --esdf; with --nav-goal the records carry the cost-to-go from that goal")
     ap.add_argument("--frontiers-min-voxels", type=int, default=8, metavar="N")
+    ap.add_argument("--view-gain", metavar="OUT.npz", help="score candidate camera poses by the unknown voxels of the final ESDF they would see, on the "
+                    "device (ks_view_gain): the centres of the frontiers' nav_voxel (the frontiers as --frontiers makes them), each at 8 yaws, "
+                    "--view-gain-size rays of a 90-degree image, --view-gain-range metres; writes poses (n, 7), records (n,) of 32 bytes, stats; "
+                    "needs --esdf")
+    ap.add_argument("--view-gain-size", default="32x24", metavar="WxH")
+    ap.add_argument("--view-gain-range", type=float, default=5.0, metavar="M")
     ap.add_argument("--max-block-distance", type=float, default=None, metavar="M", help="after every frame remove the blocks whose origin is further "
                     "than M metres from the sensor position (ks_remove_distant_blocks; completes the frames in flight)")
     ap.add_argument("--submap-frames", type=int, default=0, metavar="N", help="integrate every N frames into a second context, in the frame of "
@@ -96,6 +102,8 @@ def main():
         ap.error("--nav-out plans over the stored ESDF: give --esdf, --esdf-every or --esdf-slice as well")
     if a.frontiers and not a.esdf:
         ap.error("--frontiers reads the stored ESDF: give --esdf as well")
+    if a.view_gain and not a.esdf:
+        ap.error("--view-gain reads the stored ESDF: give --esdf as well")
     if a.nav_goal:
         try:
             nav_goal = np.array([float(v) for v in a.nav_goal.split(",")], np.float32)
@@ -322,6 +330,22 @@ def main():
               f"({st['voxels_in_frontiers']} in frontiers, the largest {st['largest_frontier_voxels']}), {st['unknown_faces']} unknown faces, "
               f"{reached} reached by the field" + ("" if st["nav_field_used"] else " (no field stored: give --nav-goal)") +
               f", work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_fr * 1e3:.2f} ms (update + records + ids) -> {a.frontiers}")
+    if a.view_gain:   # (after --frontiers: the candidates stand where the frontiers are best reached)
+        vw, vh = (int(v) for v in a.view_gain_size.lower().split("x"))
+        frec, _ = integ.frontiers(radius_m=a.nav_radius, min_voxels=a.frontiers_min_voxels)
+        poses = B.view_gain_yaw_poses(B.frontier_targets(frec, integ.cfg.voxel_size), 8)
+        vK = (0.5 * vw, 0.5 * vw, (vw - 1) / 2, (vh - 1) / 2)
+        t1 = time.perf_counter()
+        rec, st = integ.view_gain(poses, vK, vw, vh, max_range_m=a.view_gain_range)
+        t_vg = time.perf_counter() - t1
+        np.savez_compressed(a.view_gain, poses=poses, records=rec, stats_names=np.array(list(st)), stats=np.array(list(st.values()), np.uint64),
+                            K=np.array(vK, np.float32), width=np.int32(vw), height=np.int32(vh), max_range_m=np.float32(a.view_gain_range),
+                            voxel_size=np.float32(a.voxel_size))
+        best = int(np.argmax(rec["unknown_voxels"])) if len(rec) else -1
+        print(f"view gain: {len(poses)} candidate views at {len(frec)} frontiers, {st['samples'] / max(len(poses), 1):.0f} samples per view, "
+              f"{st['views_in_lds']} with their visited bitmap in LDS" +
+              (f", the best (view {best}, at {poses[best, 4:7].round(2).tolist()}) sees {int(rec['unknown_voxels'][best])} unknown voxels" if best >= 0 else "") +
+              f", work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_vg * 1e3:.2f} ms -> {a.view_gain}")
     if a.objects:
         t1 = time.perf_counter()
         rec, st = integ.objects(min_voxels=a.objects_min_voxels)
