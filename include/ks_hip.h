@@ -745,6 +745,54 @@ int ks_view_gain(ks_ctx* ctx, const float* T_G_C /* host, n x 7 */, size_t n, co
 int ks_view_gain_device(ks_ctx* ctx, const float* d_T_G_C, size_t n, const ks_view_gain_config* cfg, ks_view_gain_record* d_out,
                         ks_view_gain_stats* stats /* may be NULL */);
 
+/* ---- path shortening: a polyline pulled taut by line of sight over the stored ESDF (new: what every consumer of ks_nav_paths
+ * did on the host over downloaded waypoints, or with one ks_esdf_sweep_device call per greedy round) ----
+ * The contract is DESIGN.md, section "Path shortening"; every operation is f32 in the order written there, without FMA
+ * contraction.  SW(a, b) is the sweep of ks_esdf_sweep with this call's radius_m, min_step_m, unknown_is_free and max_samples;
+ * L(a, b) is the length that sweep computes.  The input is n paths in the layout ks_nav_paths writes; path i is P[0 .. m - 1], m =
+ * n_waypoints_in[i].  It need not come from ks_nav_paths: the call reads the ESDF store alone, as a snapshot, exactly as
+ * ks_esdf_sweep does, with or without a stored navigation field.
+ * Per path: KS_SHORTEN_INVALID when m == 0, m > max_waypoints or any of the 3 m coordinates is not finite: n_out = 0, length = 0,
+ * min_clearance = +inf, no sweep is taken and no row is written.  Otherwise Q[0] = P[0], a = 0, length = 0, min_clearance = +inf,
+ * the status KS_SHORTEN_OK, and while a < m - 1: hi = min(a + lookahead, m - 1); the candidates j in [a + 1, hi] are taken in
+ * CHUNKS OF 64 FROM THE FAR END, chunk c holding max(a + 1, hi - 64 c - 63) <= j <= hi - 64 c, and EVERY candidate of a chunk is
+ * swept with SW(P[a], P[j]) (it counts in sweeps, its samples in samples); the first chunk with a FREE candidate ends the search
+ * and j* is the largest FREE j of that chunk (visibility is not monotone: a free far candidate beats a blocked nearer one).  No
+ * chunk with a FREE candidate: j* = a + 1, the input's own segment is kept, the path becomes KS_SHORTEN_UNVERIFIED and the
+ * segment counts in segments_unverified; the call never invents geometry.  Then Q[k++] = P[j*] (the same bits), length = length
+ * + L(a, j*), min_clearance = min_c of SW(P[a], P[j*]) where that is smaller, a = j*.  n_out = k; Q[n_out - 1] is P[m - 1]; m ==
+ * 1 gives n_out = 1 without a sweep.  lookahead = 1 with every adjacent segment free returns the input.
+ * waypoints_out is [n][max_waypoints][3]; rows from n_out on are not written.  Any output may be NULL, not all.  waypoints_out
+ * may be THE SAME POINTER as waypoints_in (in place); any other overlap is the caller's error and is not detected.
+ * ks_path_shorten         host pointers: completes the frames in flight (their statistics stay owed) and stages chunks of paths.
+ * ks_path_shorten_device  DEVICE pointers on ks_stream(ctx).  It too completes the frames in flight first, which the host waits
+ *                         for (as ks_esdf_sweep_device does); the host waits for the KERNEL only when stats is non-NULL.
+ * Both only READ the context.  n = 0 is no error.  stats: integer sums; waypoints_in counts the valid paths only; sweeps and
+ * samples follow from the contract.
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; NULL input with n > 0; every output NULL with n > 0; max_waypoints outside
+ * 1..65536; lookahead outside 1..4096; radius_m or min_step_m negative or not finite; max_samples outside 2..65536; n >= 2^32; no
+ * stored ESDF; a context in a failed state), KS_ERR_UNSUPPORTED (a marcher context of ks_integrate_round_exact), KS_ERR_HIP. */
+enum { KS_SHORTEN_OK = 0, KS_SHORTEN_UNVERIFIED = 1, KS_SHORTEN_INVALID = 2 };
+typedef struct ks_path_shorten_config {
+  float radius_m;          /* 0.3 */
+  float min_step_m;        /* 0: half the context's voxel_size */
+  int32_t unknown_is_free; /* 0 */
+  int32_t max_samples;     /* 4096; 2..65536 */
+  uint32_t lookahead;      /* 64; 1..4096 */
+  uint32_t pad[3];
+} ks_path_shorten_config; /* 32 bytes */
+typedef struct ks_path_shorten_stats {
+  uint64_t paths_ok, paths_unverified, paths_invalid, waypoints_in, waypoints_out, segments_unverified, sweeps, samples;
+} ks_path_shorten_stats; /* 64 bytes */
+int ks_path_shorten_default_config(ks_path_shorten_config* cfg);
+int ks_path_shorten(ks_ctx* ctx, const float* waypoints_in /* host, [n][max_waypoints][3] */, const uint32_t* n_waypoints_in, size_t n,
+                    uint32_t max_waypoints, const ks_path_shorten_config* cfg, uint8_t* status, uint32_t* n_waypoints_out,
+                    float* waypoints_out, float* length, float* min_clearance /* any may be NULL, not all */,
+                    ks_path_shorten_stats* stats /* may be NULL */);
+int ks_path_shorten_device(ks_ctx* ctx, const float* d_waypoints_in, const uint32_t* d_n_waypoints_in, size_t n, uint32_t max_waypoints,
+                           const ks_path_shorten_config* cfg, uint8_t* d_status, uint32_t* d_n_waypoints_out, float* d_waypoints_out,
+                           float* d_length, float* d_min_clearance, ks_path_shorten_stats* stats);
+
 /* ---- multi-GPU exchange (new functionality: the reference is single-process) ----
  * The map is a set of 8^3-voxel tiles; a tile travels as its packed 63-bit key plus a raw
  * 64 KiB record block (512 voxels x 128 B).  ks_get_tile_keys lists the resident tiles in slot

@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "ks_nav_default_config", "ks_nav_update", "ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks", "ks_nav_paths", "ks_nav_paths_device",
     "ks_frontiers_default_config", "ks_frontiers_update", "ks_frontiers_size", "ks_frontiers_download", "ks_frontiers_download_blocks", "ks_frontiers_query",
     "ks_view_gain_default_config", "ks_view_gain", "ks_view_gain_device",
+    "ks_path_shorten_default_config", "ks_path_shorten", "ks_path_shorten_device",
 ]
 
 
@@ -156,6 +157,19 @@ class KsNavPathStats(C.Structure):
 KS_NAV_BLOCKED, KS_NAV_UNREACHED, KS_NAV_MAX_COST = 0xffffffff, 0xfffffffe, 0xffffff00
 KS_NAV_COST_FACE, KS_NAV_COST_EDGE, KS_NAV_COST_CORNER = 10, 14, 17
 KS_NAV_PATH_REACHED, KS_NAV_PATH_UNREACHABLE, KS_NAV_PATH_BLOCKED, KS_NAV_PATH_TRUNCATED, KS_NAV_PATH_INVALID = 0, 1, 2, 3, 4
+
+
+class KsPathShortenConfig(C.Structure):
+    _fields_ = [("radius_m", C.c_float), ("min_step_m", C.c_float), ("unknown_is_free", C.c_int32), ("max_samples", C.c_int32),
+                ("lookahead", C.c_uint32), ("pad", C.c_uint32 * 3)]
+
+
+class KsPathShortenStats(C.Structure):
+    _fields_ = [("paths_ok", C.c_uint64), ("paths_unverified", C.c_uint64), ("paths_invalid", C.c_uint64), ("waypoints_in", C.c_uint64),
+                ("waypoints_out", C.c_uint64), ("segments_unverified", C.c_uint64), ("sweeps", C.c_uint64), ("samples", C.c_uint64)]
+
+
+KS_SHORTEN_OK, KS_SHORTEN_UNVERIFIED, KS_SHORTEN_INVALID = 0, 1, 2
 
 
 class KsRenderConfig(C.Structure):
@@ -298,7 +312,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_view_gain.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_view_gain.h", "ks_k_path.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -414,6 +428,9 @@ def lib():
         L.ks_view_gain_default_config.argtypes = [C.POINTER(KsViewGainConfig)]
         for name in ("ks_view_gain", "ks_view_gain_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_size_t, C.POINTER(KsViewGainConfig), vp, C.POINTER(KsViewGainStats)]
+        L.ks_path_shorten_default_config.argtypes = [C.POINTER(KsPathShortenConfig)]
+        for name in ("ks_path_shorten", "ks_path_shorten_device"):
+            getattr(L, name).argtypes = [vp, vp, vp, C.c_size_t, C.c_uint32, C.POINTER(KsPathShortenConfig), vp, vp, vp, vp, vp, C.POINTER(KsPathShortenStats)]
         L.ks_nav_default_config.argtypes = [C.POINTER(KsNavConfig)]
         L.ks_nav_update.argtypes = [vp, vp, C.c_size_t, C.POINTER(KsNavConfig), C.POINTER(KsNavStats)]
         for name in ("ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks"):
@@ -1020,6 +1037,56 @@ class HipIntegrator:
         st = KsNavPathStats()
         self._chk(lib().ks_nav_paths_device(self._h, d_starts or None, int(n), int(max_waypoints) & 0xffffffff, d_status or None, d_cost or None,
                                             d_n_waypoints or None, d_waypoints or None, C.byref(st) if stats else None))
+        return self._stats_dict(st) if stats else None
+
+    def path_shorten_config(self, **cfg) -> KsPathShortenConfig:
+        pc = KsPathShortenConfig()
+        lib().ks_path_shorten_default_config(C.byref(pc))
+        for k, v in cfg.items():
+            if k not in ("radius_m", "min_step_m", "unknown_is_free", "max_samples", "lookahead"):
+                raise AttributeError(k)
+            if v is not None:
+                setattr(pc, k, v)
+        return pc
+
+    _SHORTEN_OUTPUTS = ("status", "n_waypoints", "waypoints", "length", "min_clearance")
+
+    def shorten_paths(self, waypoints, n_waypoints, outputs=("status", "n_waypoints", "waypoints", "length", "min_clearance"), stats=True,
+                      in_place=False, **cfg) -> dict:
+        """ks_path_shorten: each path of waypoints (n, max_waypoints, 3) f32 / n_waypoints (n,) u32 (the layout nav_paths returns)
+        pulled taut by line of sight over the STORED ESDF.  Returns a dict of status (n,) u8 (KS_SHORTEN_*), n_waypoints (n,) u32,
+        waypoints (n, max_waypoints, 3) f32 whose rows from n_waypoints on keep NAV_WAYPOINT_FILL, length / min_clearance (n,) f32,
+        plus "stats"; cfg are the fields of KsPathShortenConfig.  in_place: the library gets one array as input and output (a copy
+        of `waypoints`, returned as "waypoints": rows from n_waypoints on then keep the input)."""
+        wp = np.ascontiguousarray(waypoints, dtype=np.float32)
+        assert wp.ndim == 3 and wp.shape[2] == 3, wp.shape
+        nw = np.ascontiguousarray(n_waypoints, dtype=np.uint32).reshape(-1)
+        n, mw = len(nw), wp.shape[1]
+        assert wp.shape[0] == n
+        for k in outputs:
+            if k not in self._SHORTEN_OUTPUTS:
+                raise AttributeError(k)
+        if in_place:
+            assert "waypoints" in outputs
+            wp = wp.copy()
+        make = {"status": lambda: np.full(n, 0xee, np.uint8), "n_waypoints": lambda: np.full(n, 0xeeeeeeee, np.uint32),
+                "waypoints": lambda: wp if in_place else np.full((n, mw, 3), self.NAV_WAYPOINT_FILL, np.float32),
+                "length": lambda: np.full(n, -7.0, np.float32), "min_clearance": lambda: np.full(n, -7.0, np.float32)}
+        out = {k: make[k]() for k in outputs}
+        pc, st = self.path_shorten_config(**cfg), KsPathShortenStats()
+        self._chk(lib().ks_path_shorten(self._h, _ptr(wp), _ptr(nw), n, mw & 0xffffffff, C.byref(pc), *[_ptr(out.get(k)) for k in self._SHORTEN_OUTPUTS],
+                                        C.byref(st) if stats else None))
+        out["stats"] = self._stats_dict(st) if stats else None
+        return out
+
+    def shorten_paths_device(self, d_waypoints: int, d_n_waypoints: int, n: int, max_waypoints: int, d_status: int = 0, d_n_waypoints_out: int = 0,
+                             d_waypoints_out: int = 0, d_length: int = 0, d_min_clearance: int = 0, stats=True, **cfg):
+        """ks_path_shorten_device: raw device addresses (e.g. torch.Tensor.data_ptr()) on ks_stream; d_waypoints_out may equal
+        d_waypoints.  With stats the call has waited for the kernel; without, it returns None and waits for nothing."""
+        pc, st = self.path_shorten_config(**cfg), KsPathShortenStats()
+        self._chk(lib().ks_path_shorten_device(self._h, d_waypoints or None, d_n_waypoints or None, int(n), int(max_waypoints) & 0xffffffff, C.byref(pc),
+                                               d_status or None, d_n_waypoints_out or None, d_waypoints_out or None, d_length or None,
+                                               d_min_clearance or None, C.byref(st) if stats else None))
         return self._stats_dict(st) if stats else None
 
     # ---- multi-GPU exchange primitives (used by kimera_semantics_amd.parallel) ----

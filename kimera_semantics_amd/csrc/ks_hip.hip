@@ -76,6 +76,7 @@ using namespace ksd;
 #include "ks_k_nav.h"
 #include "ks_k_frontier.h"
 #include "ks_k_view_gain.h"
+#include "ks_k_path.h"
 #include "ks_k_remove.h"
 #include "ks_k_fuse.h"
 
@@ -608,6 +609,12 @@ struct ks_ctx {
   DevBuf<ks_view_gain_record> vg_records;
   uint32_t vg_lds_bits = kVgLdsBits;       // KS_DEBUG=1 KS_VG_LDS_BITS=<n> (tests): the LDS budget in bits; 0: every view through global memory
   uint32_t vg_groups = kVgMaxGroups;       // KS_DEBUG=1 KS_VG_GROUPS=<n> (tests): workgroups in flight
+  // ks_path_shorten (ks_k_path.h): nothing is stored between calls (the counters are esdf_read_counters); what the host entry stages
+  DevBuf<float> ps_in, ps_out, ps_f;       // the waypoints of a chunk of paths in and out; length | min_clearance
+  DevBuf<uint32_t> ps_u32;                 // n_waypoints in | out
+  DevBuf<uint8_t> ps_u8;                   // the statuses
+  size_t ps_chunk = size_t(1) << 20;       // KS_DEBUG=1 KS_SHORTEN_CHUNK=<paths> (tests): paths staged at a time
+  uint32_t ps_blocks = 4096;               // KS_DEBUG=1 KS_SHORTEN_GRID=<workgroups> (tests): the bound of k_path_shorten's grid
   // ks_remove_blocks / ks_remove_distant_blocks (ks_k_remove.h).  What the stored products still have to hear of a removal:
   std::vector<int32_t> removed_blocks;     // the blocks the LAST removal call took out, ascending (ks_removed_blocks)
   std::vector<uint64_t> mesh_removed;      // block words removed since the last ks_mesh_update, ascending: it reports them as
@@ -2958,6 +2965,9 @@ int ks_create(const ks_config* cfg, ks_ctx** out) {
   // (tests: views of a few thousand voxels on the global path, a box just below and above the budget; one bitmap reused by every view)
   if (const char* e = dbg_env("KS_VG_LDS_BITS")) c->vg_lds_bits = (uint32_t)std::min<long long>(std::max<long long>(0, atoll(e)), (long long)kVgLdsBits);
   if (const char* e = dbg_env("KS_VG_GROUPS")) c->vg_groups = (uint32_t)std::min<long long>(std::max<long long>(1, atoll(e)), (long long)kVgMaxGroups);
+  // (tests: a host-pointer call that crosses several chunk boundaries; more paths than the grid has wavefronts)
+  if (const char* e = dbg_env("KS_SHORTEN_CHUNK")) c->ps_chunk = std::max<size_t>(1, (size_t)atoll(e));
+  if (const char* e = dbg_env("KS_SHORTEN_GRID")) c->ps_blocks = (uint32_t)std::min<long long>(std::max<long long>(1, atoll(e)), 4096);
   if (eo_marks_first > eo_marks0) c->eo_want_marks.store(eo_marks_first, std::memory_order_relaxed);
   if (ensure_points(c, cfg->max_points) != KS_OK || ensure_exact_slots(c, eo_marks0, eo_x0) != KS_OK) {
     g_create_error = c->err;
@@ -5212,6 +5222,130 @@ int ks_view_gain(ks_ctx* c, const float* T, size_t n, const ks_view_gain_config*
   if (stats) return view_gain_stats(c, stats);
   HIPCHK(c, hipStreamSynchronize(st));
   return KS_OK;
+}
+
+// ---- path shortening over the stored ESDF ("Path shortening"; ks_k_path.h) ----------------------
+int ks_path_shorten_default_config(ks_path_shorten_config* p) {
+  if (!p) return KS_ERR_INVALID_ARG;
+  std::memset(p, 0, sizeof(*p));
+  p->radius_m = 0.3f;
+  p->min_step_m = 0.0f;
+  p->unknown_is_free = 0;
+  p->max_samples = 4096;
+  p->lookahead = 64;
+  return KS_OK;
+}
+
+// the checks of both calls and the kernel's parameters but for its pointers; then the frames in flight are completed and the
+// eight counters cleared
+static int path_shorten_begin(ks_ctx* c, const char* who, const float* in, const uint32_t* n_in, size_t n, uint32_t max_waypoints,
+                              const ks_path_shorten_config* p, bool any_output, PathShorten* W) {
+  if (!p) return esdf_read_refuse(c, who, "the configuration is NULL");
+  if (max_waypoints < 1 || max_waypoints > 65536) return esdf_read_refuse(c, who, "max_waypoints must lie in 1..65536");
+  if (p->lookahead < 1 || p->lookahead > 4096) return esdf_read_refuse(c, who, "lookahead must lie in 1..4096");
+  const ks_esdf_sweep_config s{p->radius_m, p->min_step_m, p->unknown_is_free, p->max_samples};
+  EsdfSweep rule{};
+  if (int rc = esdf_sweep_check(c, who, n, &s, &rule)) return rc;
+  if (n && (!in || !n_in)) return esdf_read_refuse(c, who, "waypoints_in or n_waypoints_in is NULL");
+  if (n && !any_output) return esdf_read_refuse(c, who, "all five outputs are NULL");
+  if (int rc = esdf_read_begin(c, who)) return rc;
+  W->n = n;
+  W->max_waypoints = max_waypoints;
+  W->lookahead = p->lookahead;
+  W->radius = rule.radius;
+  W->min_step = rule.min_step;
+  W->max_length = rule.max_length;
+  W->unknown_is_free = rule.unknown_is_free;
+  W->max_samples = rule.max_samples;
+  W->counters = c->esdf_read_counters;
+  return KS_OK;
+}
+// k_path_shorten over W.n paths at DEVICE addresses: a wavefront per path, the grid bounded
+static void path_shorten_launch(ks_ctx* c, const PathShorten& W) {
+  const uint32_t blocks = (uint32_t)std::min<size_t>((W.n + 3) / 4, c->ps_blocks);
+  hipLaunchKernelGGL(k_path_shorten, dim3(blocks), dim3(256), 0, c->stream, c->table, esdf_read_view(c), W);
+}
+static int path_shorten_stats(ks_ctx* c, ks_path_shorten_stats* stats) {
+  uint64_t v[8];
+  if (int rc = esdf_read_counts(c, v, 8)) return rc;
+  stats->paths_ok = v[0];
+  stats->paths_unverified = v[1];
+  stats->paths_invalid = v[2];
+  stats->waypoints_in = v[3];
+  stats->waypoints_out = v[4];
+  stats->segments_unverified = v[5];
+  stats->sweeps = v[6];
+  stats->samples = v[7];
+  return KS_OK;
+}
+
+int ks_path_shorten_device(ks_ctx* c, const float* d_in, const uint32_t* d_n_in, size_t n, uint32_t max_waypoints, const ks_path_shorten_config* p,
+                           uint8_t* d_status, uint32_t* d_n_out, float* d_out, float* d_length, float* d_min_clearance, ks_path_shorten_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  PathShorten W{};
+  if (int rc = path_shorten_begin(c, "ks_path_shorten_device", d_in, d_n_in, n, max_waypoints, p,
+                                  d_status || d_n_out || d_out || d_length || d_min_clearance, &W))
+    return rc;
+  if (n == 0) return KS_OK;
+  W.in = d_in;
+  W.n_in = d_n_in;
+  W.status = d_status;
+  W.n_out = d_n_out;
+  W.out = d_out;
+  W.length = d_length;
+  W.min_clearance = d_min_clearance;
+  path_shorten_launch(c, W);
+  HIPCHK(c, hipGetLastError());
+  return stats ? path_shorten_stats(c, stats) : KS_OK;
+}
+
+int ks_path_shorten(ks_ctx* c, const float* in, const uint32_t* n_in, size_t n, uint32_t max_waypoints, const ks_path_shorten_config* p, uint8_t* status,
+                    uint32_t* n_out, float* out, float* length, float* min_clearance, ks_path_shorten_stats* stats) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  PathShorten W{};
+  if (int rc = path_shorten_begin(c, "ks_path_shorten", in, n_in, n, max_waypoints, p, status || n_out || out || length || min_clearance, &W)) return rc;
+  if (n == 0) return KS_OK;
+  // a chunk's waypoints stay within 64 MiB; only the rows a path has written reach the caller's array.  out == in: in place on the
+  // device as well
+  const size_t row = (size_t)max_waypoints * 3;
+  const size_t m_max = std::min(n, std::min(c->ps_chunk, std::max<size_t>(1, (size_t(64) << 20) / (row * sizeof(float)))));
+  const bool in_place = out == in;
+  int rc;
+  if ((rc = c->ps_in.reserve(c, m_max * row, m_max * row)) || (rc = c->ps_u32.reserve(c, 2 * m_max, 2 * m_max)) ||
+      (rc = c->ps_u8.reserve(c, m_max, m_max)) || (rc = c->ps_f.reserve(c, 2 * m_max, 2 * m_max)) ||
+      (out && !in_place && (rc = c->ps_out.reserve(c, m_max * row, m_max * row))))
+    return rc;
+  W.in = c->ps_in.get();
+  W.n_in = c->ps_u32.get();
+  W.status = status ? c->ps_u8.get() : nullptr;
+  W.n_out = n_out || out ? c->ps_u32.get() + m_max : nullptr;
+  W.out = out ? (in_place ? c->ps_in.get() : c->ps_out.get()) : nullptr;
+  W.length = length ? c->ps_f.get() : nullptr;
+  W.min_clearance = min_clearance ? c->ps_f.get() + m_max : nullptr;
+  std::vector<uint32_t> nw(W.n_out ? m_max : 0);
+  std::vector<float> wp(out ? m_max * row : 0);
+  hipStream_t st = c->stream;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->ps_in, in + off * row, m * row * sizeof(float), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(c->ps_u32, n_in + off, m * sizeof(uint32_t), hipMemcpyHostToDevice, st));
+    W.n = m;
+    path_shorten_launch(c, W);
+    if (status) HIPCHK(c, hipMemcpyAsync(status + off, W.status, m, hipMemcpyDeviceToHost, st));
+    if (W.n_out) HIPCHK(c, hipMemcpyAsync(nw.data(), W.n_out, m * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    if (out) HIPCHK(c, hipMemcpyAsync(wp.data(), W.out, m * row * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (length) HIPCHK(c, hipMemcpyAsync(length + off, W.length, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    if (min_clearance) HIPCHK(c, hipMemcpyAsync(min_clearance + off, W.min_clearance, m * sizeof(float), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // (the staging is reused by the next chunk)
+    for (size_t i = 0; i < m; ++i) {
+      if (n_out) n_out[off + i] = nw[i];
+      if (out && nw[i]) std::memcpy(out + (off + i) * row, wp.data() + i * row, (size_t)nw[i] * 3 * sizeof(float));
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return stats ? path_shorten_stats(c, stats) : KS_OK;
 }
 
 // ---- voxel-level host sync -------------------------------------------------------------------------------

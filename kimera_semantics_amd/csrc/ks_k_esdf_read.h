@@ -170,7 +170,9 @@ __global__ void __launch_bounds__(256) k_esdf_slice(TileTable T, EsdfReadStore S
   esdf_read_count(O.counters, live, status);
 }
 
-// grid ceil(n / 256), 256 work-items
+// grid ceil(n / 256), 256 work-items.  THE WALK BELOW HAS A SECOND COPY: path_sweep of ks_k_path.h restates it operation for operation
+// (without t_stop and t_min) for k_path_shorten, because factoring it out changed this kernel's instruction stream.  Both are compared
+// bit for bit with the one sweep of tests/esdf_read_model.py; a change to the walk goes into both.
 __global__ void __launch_bounds__(256) k_esdf_sweep(TileTable T, EsdfReadStore S, EsdfSweep W) {
   const size_t i = (size_t)blockIdx.x * 256u + threadIdx.x;
   const bool live = i < W.n;

@@ -411,6 +411,35 @@ int main(int argc, char** argv) {
                 ms, (unsigned long long)st.voxels_reached, (unsigned long long)st.voxels_traversable, (unsigned long long)st.rounds, ns,
                 (unsigned long long)ps.paths_reached, (unsigned long long)ps.paths_unreachable, (unsigned long long)ps.paths_blocked,
                 (unsigned long long)ps.waypoints);
+    // ... and KS_DEMO_SHORTEN=<file>: those paths pulled taut by line of sight (shortenPaths, the same radius, lookahead 48), written
+    // as { u32 paths, u32 lookahead; u8 status[paths]; u32 n_waypoints[paths]; f32 length[paths]; f32 min_clearance[paths]; the
+    // waypoints of every path in turn, n_waypoints x f32[3] each }; the paths that went in are those of the KS_DEMO_NAV file
+    if (const char* shorten_path = std::getenv("KS_DEMO_SHORTEN")) {
+      kimera::HipSemanticTsdfIntegrator::ShortenOptions so;
+      so.radius_m = no.radius_m;
+      so.lookahead = 48;
+      kimera::HipSemanticTsdfIntegrator::ShortPaths taut;
+      const auto t1 = std::chrono::steady_clock::now();
+      hip->shortenPaths(paths.waypoints, so, &taut);
+      const double ms1 = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t1).count();
+      FILE* sf = std::fopen(shorten_path, "wb");
+      if (!sf) return 9;
+      std::fwrite(&ns, 4, 1, sf);
+      std::fwrite(&so.lookahead, 4, 1, sf);
+      std::fwrite(taut.status.data(), 1, ns, sf);
+      for (const auto& w : taut.waypoints) {
+        const uint32_t nw = w.size();
+        std::fwrite(&nw, 4, 1, sf);
+      }
+      std::fwrite(taut.length.data(), 4, ns, sf);
+      std::fwrite(taut.min_clearance.data(), 4, ns, sf);
+      for (const auto& w : taut.waypoints) std::fwrite(w.data(), 12, w.size(), sf);
+      std::fclose(sf);
+      const ks_path_shorten_stats& hs = hip->lastPathShortenStats();
+      std::printf("adapter_demo: shortenPaths %.3f ms, %llu -> %llu waypoints in %llu paths (%llu unverified, %llu invalid), %llu sweeps, %llu samples\n", ms1,
+                  (unsigned long long)hs.waypoints_in, (unsigned long long)hs.waypoints_out, (unsigned long long)(hs.paths_ok + hs.paths_unverified),
+                  (unsigned long long)hs.paths_unverified, (unsigned long long)hs.paths_invalid, (unsigned long long)hs.sweeps, (unsigned long long)hs.samples);
+    }
   }
 
   // KS_DEMO_FRONTIERS=<file>: where an explorer may go next, on the device without any layer sync — updateEsdf (min_distance_m 0.1,

@@ -454,6 +454,60 @@ bool HipSemanticTsdfIntegrator::planPaths(const vxb::Pointcloud& starts_G, uint3
   return last_nav_path_stats_.paths_reached == n;
 }
 
+bool HipSemanticTsdfIntegrator::shortenPaths(const std::vector<vxb::Pointcloud>& paths, const ShortenOptions& options, ShortPaths* out) {
+  CHECK_NOTNULL(out);
+  static_assert(sizeof(vxb::Point) == 12, "point layout");
+  ks_path_shorten_config pc;
+  ks_path_shorten_default_config(&pc);
+  pc.radius_m = options.radius_m;
+  pc.min_step_m = options.min_step_m;
+  pc.unknown_is_free = options.unknown_is_free ? 1 : 0;
+  pc.max_samples = options.max_samples;
+  pc.lookahead = options.lookahead;
+  const size_t n = paths.size();
+  out->status.assign(n, 0);
+  out->waypoints.assign(n, vxb::Pointcloud());
+  out->length.assign(n, 0.0f);
+  out->min_clearance.assign(n, 0.0f);
+  last_path_shorten_stats_ = ks_path_shorten_stats{};
+  // a path of more than 65536 waypoints (the library's largest max_waypoints) goes in with its true count and no rows: m > max_waypoints,
+  // which the contract makes KS_SHORTEN_INVALID; the other paths of the call are shortened as usual
+  const size_t kMaxWaypoints = 65536;
+  size_t longest = 1;
+  for (const auto& p : paths)
+    if (p.size() <= kMaxWaypoints) longest = std::max(longest, p.size());
+  // chunks of paths whose rows of `longest` waypoints stay within 16 MiB; in place
+  const size_t row = longest * 3;
+  const size_t chunk = std::max<size_t>(1, (size_t(16) << 20) / (row * sizeof(float)));
+  std::vector<float> wp(std::min(chunk, n) * row);
+  std::vector<uint32_t> count(std::min(chunk, n)), kept(std::min(chunk, n));
+  for (size_t off = 0; off < n; off += chunk) {
+    const size_t m = std::min(chunk, n - off);
+    for (size_t i = 0; i < m; ++i) {
+      const vxb::Pointcloud& p = paths[off + i];
+      count[i] = (uint32_t)std::min<size_t>(p.size(), 0xffffffffu);
+      if (!p.empty() && p.size() <= kMaxWaypoints) std::memcpy(wp.data() + i * row, p.data(), p.size() * 12);
+    }
+    ks_path_shorten_stats st{};
+    check(ks_path_shorten(ctx_, wp.data(), count.data(), m, (uint32_t)longest, &pc, out->status.data() + off, kept.data(),
+                          wp.data(), out->length.data() + off, out->min_clearance.data() + off, &st),
+          "ks_path_shorten");
+    last_path_shorten_stats_.paths_ok += st.paths_ok;
+    last_path_shorten_stats_.paths_unverified += st.paths_unverified;
+    last_path_shorten_stats_.paths_invalid += st.paths_invalid;
+    last_path_shorten_stats_.waypoints_in += st.waypoints_in;
+    last_path_shorten_stats_.waypoints_out += st.waypoints_out;
+    last_path_shorten_stats_.segments_unverified += st.segments_unverified;
+    last_path_shorten_stats_.sweeps += st.sweeps;
+    last_path_shorten_stats_.samples += st.samples;
+    for (size_t i = 0; i < m; ++i) {
+      const float* p = wp.data() + i * row;
+      for (uint32_t k = 0; k < kept[i]; ++k) out->waypoints[off + i].push_back(vxb::Point(p[3 * k], p[3 * k + 1], p[3 * k + 2]));
+    }
+  }
+  return last_path_shorten_stats_.paths_ok == n;
+}
+
 void HipSemanticTsdfIntegrator::downloadEsdfBlocks(const std::vector<int32_t>& idx, std::vector<EsdfBlock>* out) {
   const size_t n = idx.size() / 3, vps = semantic_layer_ptr_->voxels_per_side(), nv = vps * vps * vps;
   std::vector<EsdfVoxel> all(n * nv);

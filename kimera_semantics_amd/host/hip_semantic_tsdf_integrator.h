@@ -229,6 +229,26 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   };
   bool planPaths(const vxb::Pointcloud& starts_G, uint32_t max_waypoints, NavPaths* out);
   const ks_nav_path_stats& lastNavPathStats() const { return last_nav_path_stats_; }
+  /// Polylines pulled taut by line of sight over the STORED ESDF (ks_path_shorten; the contract is DESIGN.md, "Path shortening"):
+  /// of each path only the waypoints stay from which the next kept one is reachable in a straight line with the clearance
+  /// radius_m, looking at most `lookahead` waypoints ahead.  The paths need not come from planPaths(), and no navigation field
+  /// is needed.  status is KS_SHORTEN_*: a segment that no sweep could verify is kept as the input has it (UNVERIFIED); an empty
+  /// path, one with a non-finite coordinate or one of more than 65536 waypoints (the library's largest max_waypoints) is INVALID and
+  /// comes back empty; the other paths of the call are not affected.  Returns true when every path is KS_SHORTEN_OK.
+  struct ShortenOptions {
+    float radius_m = 0.3f;
+    float min_step_m = 0.0f;     ///< 0: half a voxel
+    bool unknown_is_free = false;
+    int32_t max_samples = 4096;
+    uint32_t lookahead = 64;     ///< 1..4096
+  };
+  struct ShortPaths {
+    std::vector<uint8_t> status;
+    std::vector<vxb::Pointcloud> waypoints;
+    std::vector<float> length, min_clearance;
+  };
+  bool shortenPaths(const std::vector<vxb::Pointcloud>& paths, const ShortenOptions& options, ShortPaths* out);
+  const ks_path_shorten_stats& lastPathShortenStats() const { return last_path_shorten_stats_; }
   /// What the map looks like from a camera pose (ks_render_view; the contract is DESIGN.md, "View rendering"): one ray per
   /// pixel through the resident tiles ON THE DEVICE, as the map is after the frames in flight.  Needs NO syncLayers(): the
   /// voxels stay in HBM, only the images travel.  depth is z-depth in the camera frame, NaN where the ray found no surface
@@ -343,6 +363,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_esdf_sweep_stats last_esdf_sweep_stats_{};
   ks_nav_stats last_nav_stats_{};
   ks_nav_path_stats last_nav_path_stats_{};
+  ks_path_shorten_stats last_path_shorten_stats_{};
   ks_esdf_refresh_stats last_esdf_refresh_stats_{};
   ks_render_stats last_render_stats_{};
   ks_align_stats last_align_stats_{};

@@ -17,7 +17,7 @@ into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and 
 writes the cost-to-go field of the final ESDF to that goal for a robot of --nav-radius, made on the device (ks_nav_update), with the
 path from the last camera position; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] [--view-gain out.npz] \\
+      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz [--nav-shorten]] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] [--view-gain out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
@@ -63,6 +63,9 @@ def main():
     ap.add_argument("--esdf-min-distance", type=float, default=0.2, metavar="M")
     ap.add_argument("--nav-goal", metavar="X,Y,Z", help="with --nav-out: the goal of the navigation field, a world point in metres")
     ap.add_argument("--nav-radius", type=float, default=0.3, metavar="R", help="the robot radius the field is made for")
+    ap.add_argument("--nav-shorten", action="store_true", help="with --nav-out: also pull that path taut by line of sight over the ESDF on the device "
+                    "(ks_path_shorten, the radius of --nav-radius) and write both path sets (path_short, path_short_status, path_short_length_m, "
+                    "path_short_min_clearance_m beside path)")
     ap.add_argument("--nav-out", metavar="OUT.npz", help="compute the cost-to-go field of the final ESDF to --nav-goal on the device (ks_nav_update) and "
                     "write it per block with the path from the last camera position (ks_nav_paths); needs --esdf, --esdf-every or --esdf-slice")
     ap.add_argument("--render-every", type=int, default=0, metavar="N", help="render the map on the device from the frame's own pose and intrinsics "
@@ -98,6 +101,8 @@ def main():
         ap.error("--render-every needs --render-out")
     if bool(a.nav_out) != bool(a.nav_goal):
         ap.error("--nav-out and --nav-goal go together")
+    if a.nav_shorten and not a.nav_out:
+        ap.error("--nav-shorten goes with --nav-out")
     if a.nav_out and not (a.esdf or a.esdf_every or a.esdf_slice):
         ap.error("--nav-out plans over the stored ESDF: give --esdf, --esdf-every or --esdf-slice as well")
     if a.frontiers and not a.esdf:
@@ -307,15 +312,27 @@ def main():
         path = integ.nav_paths(last_position[None], 65536, outputs=("status", "cost", "n_waypoints", "waypoints"))
         t_nav = time.perf_counter() - t1
         n_wp = int(path["n_waypoints"][0])
+        short = {}
+        if a.nav_shorten:
+            t1 = time.perf_counter()
+            taut = integ.shorten_paths(path["waypoints"][:, :max(n_wp, 1)], path["n_waypoints"], radius_m=a.nav_radius)
+            t_short = time.perf_counter() - t1
+            n_short = int(taut["n_waypoints"][0])
+            short = dict(path_short=taut["waypoints"][0, :n_short], path_short_status=taut["status"][0], path_short_length_m=taut["length"][0],
+                         path_short_min_clearance_m=taut["min_clearance"][0])
         np.savez_compressed(a.nav_out, block_indices=idx, cost=field, goal=nav_goal, radius_m=np.float32(a.nav_radius), start=last_position,
                             path_status=path["status"][0], path_cost=path["cost"][0], path=path["waypoints"][0, :n_wp],
-                            voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+                            voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps), **short)
         what = {B.KS_NAV_PATH_REACHED: "reaches the goal", B.KS_NAV_PATH_UNREACHABLE: "cannot reach the goal", B.KS_NAV_PATH_BLOCKED: "starts in a voxel "
                 "that is not traversable", B.KS_NAV_PATH_TRUNCATED: "was cut at 65536 waypoints"}.get(int(path["status"][0]), "is invalid")
         print(f"nav: {st['voxels_reached']} of {st['voxels_traversable']} traversable voxels reached for radius {a.nav_radius} m ({st['goals_used']} of 1 goals "
               f"usable), largest cost {st['largest_cost']}, {st['rounds']} rounds, {st['tile_relaxations']} tile relaxations; the path from the last camera "
               f"position {what}: {n_wp} waypoints, about {int(path['cost'][0]) * a.voxel_size / 10 if n_wp else 0:.2f} m; {t_nav * 1e3:.2f} ms "
               f"(field + download + path) -> {a.nav_out}")
+        if a.nav_shorten:
+            what = {B.KS_SHORTEN_OK: "every segment verified", B.KS_SHORTEN_UNVERIFIED: "with segments no sweep verified"}.get(int(taut["status"][0]), "invalid: no path")
+            print(f"nav shorten: {n_wp} -> {n_short} waypoints ({what}), {float(taut['length'][0]):.2f} m, smallest clearance "
+                  f"{float(taut['min_clearance'][0]):.3f} m, {taut['stats']['sweeps']} sweeps of {taut['stats']['samples']} samples; {t_short * 1e3:.2f} ms")
     if a.frontiers:   # (after --nav-out: a stored field fills the join)
         t1 = time.perf_counter()
         rec, st = integ.frontiers(radius_m=a.nav_radius, min_voxels=a.frontiers_min_voxels)
