@@ -267,7 +267,13 @@ for _field in ("sphere", "holes", "no_sites"):
     for _vps in (8, 16):
         for _r, _d in ((8, 0.4), (11, 0.55)):
             SPECS["upload_%s_vps%d_r%d" % (_field, _vps, _r)] = dict(case="upload", field=_field, vps=_vps, max_distance_m=_d)
+# 4^3 tiles per block at the existing windows; 8^3 tiles per block with the surface across the seam of its two blocks
+for _field in ("sphere", "holes"):
+    for _r, _d in ((8, 0.4), (11, 0.55)):
+        SPECS["upload_%s_vps32_r%d" % (_field, _r)] = dict(case="upload", field=_field, vps=32, max_distance_m=_d)
 SPECS.update({
+    "random_ties_vps32": dict(case="upload", field="random", vps=32, max_distance_m=0.4),
+    "upload_sphere_vps64": dict(case="upload", field="sphere", vps=64, max_distance_m=0.4, form="separable"),
     "random_ties": dict(case="upload", field="random", vps=8, max_distance_m=0.4),
     "slab": dict(case="upload", field="slab", vps=16, max_distance_m=0.55),
     "integrated_fast": dict(case="integrated", method=0, max_distance_m=0.4),

@@ -88,7 +88,7 @@ def refused(code, call):
 
 
 def _field(vps):
-    return esdf_case.sphere_blocks(vps, 8 if vps == 8 else 4)   # 64^3 voxels, 512 tiles either way
+    return esdf_case.sphere_blocks(vps, 64 // vps)   # 64^3 voxels, 512 tiles at every block size
 
 
 def _sphere(vps):
@@ -117,7 +117,7 @@ def case_mutate(spec):
     lo = int(g.block_indices().min())
     steps = [("interior, another random field", (0, 0, 0), lambda b: esdf_case.random_field([b], vps, 23)),
              ("corner, weight 0", (lo, lo, lo), lambda b: _zero_weight(g, b)),
-             ("signs flipped", (1, -2, 0), lambda b: _flipped(g, b))]
+             ("signs flipped", (1, -2, 0) if vps <= 16 else (0, -1, 0), lambda b: _flipped(g, b))]
     out = {}
     for what, block, make in steps:
         g.upload(*make(block))
@@ -200,6 +200,33 @@ def case_clusters(spec):
     e = refused(B.KS_ERR_UNSUPPORTED, lambda: g.esdf_update(max_workspace_bytes=room, **cfg_of(spec)))   # a box of 1004 x 904 x 804 tiles
     assert e.stats["workspace_bytes"] > (1 << 40), e.stats
     M.assert_same(g.esdf_blocks(both), before, "after the refused update")
+    g.close()
+    return dict(st)
+
+
+def case_region_blocks(spec):
+    """A region given in blocks of vps^3 voxels: the stored ESDF of an update over half of the map's blocks, and its refresh after a
+    block inside and a block outside the region changed, against the model (the region's box is region * vps / 8 tiles)."""
+    vps = spec["vps"]
+    g = _sphere(vps)
+    n = 64 // vps // 2
+    region = ([-n, 0, -n], [n - 1, n - 1, n - 1])          # the half y >= 0
+    g.esdf_update(region=region, **cfg_of(spec))
+    idx = g.block_indices()
+    model = M.model_of(g, cfg_of(spec))
+    M.assert_same(g.esdf_blocks(idx), model.blocks(idx, region=region), "region update")
+    inside = np.array([all(region[0][a] <= b[a] <= region[1][a] for a in range(3)) for b in idx])
+    assert inside.sum() * 2 == len(idx) and (g.esdf_blocks(idx[inside])["flags"] != 0).any()
+    assert g.esdf_blocks(idx[~inside]).tobytes() == M.default_records((int((~inside).sum()), vps ** 3)).tobytes()
+    changed = [(0, 0, 0), (-1, -1, 0)]
+    fresh = esdf_case.random_field([changed[0]], vps, 41)
+    g.upload(*fresh)
+    g.upload(*_flipped(g, changed[1]))
+    st = g.esdf_refresh()
+    check_map(g, st, spec, "region refresh", region=region)
+    A = check_counts(g, st, changed, spec, region=region)
+    assert 0 < len(A) < st["tiles_total"] // 2 + 1 and st["tiles_stale"] == 2 * (vps // 8) ** 3, st
+    assert st["voxels_observed"] == inside.sum() * vps ** 3 - int((fresh[1]["weight"] == 0).sum()), st   # (the random block leaves a tenth unobserved)
     g.close()
     return dict(st)
 
@@ -292,7 +319,7 @@ def case_errors(spec):
     return {}
 
 
-CASES = {"mutate": case_mutate, "integrated": case_integrated, "clusters": case_clusters, "region": case_region,
+CASES = {"region_blocks": case_region_blocks, "mutate": case_mutate, "integrated": case_integrated, "clusters": case_clusters, "region": case_region,
          "independent": case_independent, "errors": case_errors}
 
 # max_distance_m 0.4: R = 8, g = 1, the window ends exactly on a tile edge; 0.55: R = 11, g = 2, it ends mid-tile
@@ -301,6 +328,10 @@ for _r, _d in ((8, 0.4), (11, 0.55)):
     for _vps in (8, 16):
         SPECS["mutate_vps%d_r%d" % (_vps, _r)] = dict(case="mutate", vps=_vps, max_distance_m=_d)
 SPECS.update({
+    "mutate_vps32_r8": dict(case="mutate", vps=32, max_distance_m=0.4),
+    "mutate_vps32_r11": dict(case="mutate", vps=32, max_distance_m=0.55),
+    "region_blocks_vps16": dict(case="region_blocks", vps=16, max_distance_m=0.55),
+    "region_blocks_vps32": dict(case="region_blocks", vps=32, max_distance_m=0.55),
     "integrated_fast": dict(case="integrated", method=0, max_distance_m=0.4),
     "integrated_merged": dict(case="integrated", method=1, max_distance_m=0.4),
     "integrated_pool_doubles": dict(case="integrated", method=0, max_distance_m=0.4, max_tiles=1024, frames_before=2),

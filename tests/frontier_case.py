@@ -568,15 +568,28 @@ def case_errors(spec):
     return {}
 
 
-CASES = {"cube": case_cube, "room": case_room, "faces": case_faces, "random": case_random, "order": case_order, "bounds": case_bounds,
+def case_planted(spec):
+    """A handful of free voxels at the ends of the linear index range of two blocks: the per-voxel ids of the block export against
+    the model ((-1, 0, 0) and (0, 0, 0) touch across the seam and make one frontier of two)."""
+    vox = mesh_case.planted_voxels(spec["vps"])
+    g = _stored({v: FREE for v in vox}, spec["vps"])
+    rec, stats, idx, ids, model = check(g, "planted", radius_m=SMALL, min_voxels=1)
+    assert len(g.block_indices()) == 2 and stats["voxels_frontier"] == stats["voxels_in_frontiers"] == (ids != NONE).sum() == len(vox), stats
+    assert stats["frontiers"] == len(vox) - 1 and stats["largest_frontier_voxels"] == 2, stats
+    g.close()
+    return dict(stats)
+
+
+CASES = {"planted": case_planted, "cube": case_cube, "room": case_room, "faces": case_faces, "random": case_random, "order": case_order, "bounds": case_bounds,
          "nav": case_nav, "lifetime": case_lifetime, "reads_only": case_reads_only, "integrated": case_integrated, "errors": case_errors}
 
 # name -> spec: the same cases in both tiers
 SPECS = {}
-for _vps in (8, 16):
+for _vps in (8, 16, 32):
     for _case in ("cube", "room", "faces", "random", "order", "bounds", "nav"):
         SPECS["%s_vps%d" % (_case, _vps)] = dict(case=_case, vps=_vps)
 SPECS.update({
+    "planted_vps64": dict(case="planted", vps=64),
     "lifetime": dict(case="lifetime"),
     "reads_only_vps8": dict(case="reads_only", vps=8),
     "reads_only_vps16": dict(case="reads_only", vps=16),

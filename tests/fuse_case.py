@@ -436,6 +436,8 @@ SPECS = {
     "yaw90": dict(case="pose", pose="yaw90"),
     "generic_empty": dict(case="pose", pose="generic"),
     "generic_vps": dict(case="pose", pose="generic", src_vps=8, dst_vps=16),
+    # blocks of 4^3 tiles on both sides, {-1, 0}^3 each: a block expands to 64 tile keys, negative ones among them
+    "generic_vps32": dict(case="pose", pose="generic", src_vps=32, dst_vps=32),
     "overlap_color": dict(case="pose", pose="generic", dst_field="random", color_mode=0),
     "overlap_prob": dict(case="pose", pose="generic", dst_field="random", color_mode=2),
     "holes": dict(case="holes"),

@@ -14,14 +14,28 @@ SPHERE_CENTRE = (0.0137, -0.0221, 0.0319)   # off the voxel grid (tests/test_mes
 SPHERE_RADIUS = 0.6
 
 
+# vps -> the blocks make_field covers, per axis (a fixed voxel extent, not a rounded length)
+FIELD_BLOCKS = {8: (range(-2, 2),) * 3, 16: (range(-1, 1),) * 3, 32: (range(-1, 1),) * 3, 64: (range(-1, 1), range(0, 1), range(0, 1))}
+
+
+def field_centre(vps):
+    """Where make_field puts the sphere's centre (and the plane's foot) at this block size: the middle of its box."""
+    off = np.array([0.0, 0.5 * vps * VOXEL, 0.5 * vps * VOXEL]) if vps == 64 else np.zeros(3)
+    return np.array(SPHERE_CENTRE) + off
+
+
 def make_field(kind, vps, seed=1):
-    """Host-layout blocks (indices, tsdf, sem) of an analytic field over [-0.8 m, 0.8 m)^3, to upload()."""
+    """Host-layout blocks (indices, tsdf, sem) of an analytic field, to upload().  What each block size covers:
+      vps 8:  blocks {-2..1}^3 = [-0.8 m, 0.8 m)^3, 32^3 voxels, 64 one-tile blocks;
+      vps 16: blocks {-1,0}^3  = the same 32^3 voxels, 8 blocks of 2^3 tiles;
+      vps 32: blocks {-1,0}^3  = [-1.6 m, 1.6 m)^3, 64^3 voxels, 8 blocks of 4^3 tiles: the same surfaces, seams through the origin;
+      vps 64: blocks {-1,0} x {0} x {0} = [-3.2 m, 3.2 m) x [0, 3.2 m)^2, two blocks of 8^3 tiles, the sphere and the plane moved by
+              (0, 1.6 m, 1.6 m) to the middle of that box, so that the surface crosses the block seam x = 0.
+    At 8 and 16 the bytes are those of every earlier version of this function (tests/test_mesh_cpu.py holds their hashes)."""
     from kimera_semantics_amd import binding as B
     from kimera_semantics_amd import synth
-    side = vps * VOXEL
-    lo = -int(round(0.8 / side))
-    rng_b = range(lo, -lo)
-    idx = np.array([(x, y, z) for x in rng_b for y in rng_b for z in rng_b], dtype=np.int32)
+    rx, ry, rz = FIELD_BLOCKS[vps]
+    idx = np.array([(x, y, z) for x in rx for y in ry for z in rz], dtype=np.int32)
     nv = vps ** 3
     lin = np.arange(nv)
     local = np.stack([lin % vps, (lin // vps) % vps, lin // (vps * vps)], axis=1)
@@ -29,10 +43,10 @@ def make_field(kind, vps, seed=1):
     t = np.zeros((len(idx), nv), dtype=B.TSDF_DTYPE)
     s = np.zeros((len(idx), nv), dtype=B.SEM_DTYPE)
     if kind in ("sphere", "holes", "two_label"):
-        dist = np.linalg.norm(centre - np.array(SPHERE_CENTRE), axis=-1) - SPHERE_RADIUS
+        dist = np.linalg.norm(centre - field_centre(vps), axis=-1) - SPHERE_RADIUS
     elif kind == "plane":
         n = np.array([0.31, -0.52, 0.79])
-        dist = centre @ (n / np.linalg.norm(n)) - 0.0613
+        dist = (centre - (field_centre(vps) - np.array(SPHERE_CENTRE))) @ (n / np.linalg.norm(n)) - 0.0613
     else:
         raise ValueError(kind)
     t["distance"] = dist.astype(np.float32)
@@ -51,7 +65,94 @@ def make_field(kind, vps, seed=1):
         rng = np.random.default_rng(seed)
         t["weight"][rng.random(t["weight"].shape) < 0.10] = 0.0
         keep = rng.random(len(idx)) >= 0.15   # some blocks absent
+        if keep.all():                        # (the draw for the 8 blocks of vps 32 keeps them all: one block with three lower neighbours goes)
+            keep[len(idx) - 1] = False
     return idx[keep], t[keep], s[keep]
+
+
+SAME_MAP_BOX = ((-64, 64), (0, 64), (0, 64))     # global voxels [lo, hi) per axis: 16 x 8 x 8 tiles
+SAME_MAP_TILES = 1024
+SAME_MAP_CENTRE = (0.0137, 1.5779, 1.6319)       # off the voxel grid, on the seam x = 0 of every block size
+SAME_MAP_RADIUS = 1.0
+SAME_MAP_POCKET = ((26, 58), (6, 58), (6, 58))   # global voxels [lo, hi): outside the sphere, every voxel observed and free
+_SAME_MAP = {}
+
+
+def same_map_voxels():
+    """The one voxel content of same_map(), in global voxel coordinates: (origin, tsdf[z, y, x], sem[z, y, x]) over SAME_MAP_BOX.
+    A sphere surface (truncated at 4 voxels) with the labels 3 / 7 split at the plane y + z = 3.2 m, 10 % of the voxels with
+    weight 0, except in SAME_MAP_POCKET (free, fully observed: room for the planner kernels)."""
+    if "voxels" not in _SAME_MAP:
+        from kimera_semantics_amd import binding as B
+        from kimera_semantics_amd import synth
+        (x0, x1), (y0, y1), (z0, z1) = SAME_MAP_BOX
+        gz, gy, gx = np.meshgrid(np.arange(z0, z1), np.arange(y0, y1), np.arange(x0, x1), indexing="ij")
+        centre = (np.stack([gx, gy, gz], axis=-1).astype(np.float64) + 0.5) * VOXEL
+        t, s = np.zeros(gx.shape, B.TSDF_DTYPE), np.zeros(gx.shape, B.SEM_DTYPE)
+        dist = np.linalg.norm(centre - np.array(SAME_MAP_CENTRE), axis=-1) - SAME_MAP_RADIUS
+        t["distance"] = np.clip(dist, -4 * VOXEL, 4 * VOXEL).astype(np.float32)
+        weight = np.where(np.random.default_rng(21).random(gx.shape) < 0.10, 0.0, 1.0).astype(np.float32)
+        (px0, px1), (py0, py1), (pz0, pz1) = SAME_MAP_POCKET
+        pocket = (gx >= px0) & (gx < px1) & (gy >= py0) & (gy < py1) & (gz >= pz0) & (gz < pz1)
+        assert (dist[pocket] > 0.1).all()
+        weight[pocket] = 1.0
+        t["weight"] = weight
+        label = np.where(centre[..., 1] + centre[..., 2] < 3.2, 3, 7).astype(np.uint8)
+        lut = synth.default_label_colors()
+        t["color"] = lut[label]
+        s["label"], s["color"] = label, lut[label]
+        s["priors"] = np.float32(-0.60205999132)
+        np.put_along_axis(s["priors"], label[..., None].astype(np.int64), np.float32(-0.1), axis=-1)
+        _SAME_MAP["voxels"] = (np.array([x0, y0, z0]), t, s)
+    return _SAME_MAP["voxels"]
+
+
+def to_blocks(origin, field, vps):
+    """field[z, y, x] over a box of whole blocks starting at the global voxel `origin` -> (block indices ascending by (x, y, z),
+    rows of vps^3 voxels in x + vps * (y + vps * z) order)."""
+    nz, ny, nx = field.shape
+    assert nx % vps == 0 and ny % vps == 0 and nz % vps == 0 and (np.asarray(origin) % vps == 0).all()
+    bz, by, bx = nz // vps, ny // vps, nx // vps
+    rows = field.reshape(bz, vps, by, vps, bx, vps).transpose(4, 2, 0, 1, 3, 5).reshape(bx * by * bz, vps ** 3)
+    o = np.asarray(origin) // vps
+    idx = np.array([(o[0] + x, o[1] + y, o[2] + z) for x in range(bx) for y in range(by) for z in range(bz)], dtype=np.int32)
+    return idx, np.ascontiguousarray(rows)
+
+
+def from_blocks(idx, rows, vps, box=SAME_MAP_BOX):
+    """The inverse of to_blocks for blocks in any order: rows -> field[z, y, x] over `box` (every block of the box must be there)."""
+    (x0, x1), (y0, y1), (z0, z1) = box
+    out = np.zeros((z1 - z0, y1 - y0, x1 - x0), rows.dtype)
+    seen = np.zeros(out.shape, bool)
+    for b, row in zip(np.asarray(idx).reshape(-1, 3), rows):
+        x, y, z = (int(b[0]) * vps - x0, int(b[1]) * vps - y0, int(b[2]) * vps - z0)
+        out[z:z + vps, y:y + vps, x:x + vps] = row.reshape(vps, vps, vps)
+        seen[z:z + vps, y:y + vps, x:x + vps] = True
+    assert seen.all() and len(idx) * vps ** 3 == out.size, (len(idx), vps)
+    return out
+
+
+def same_map(vps):
+    """Host-layout blocks (indices, tsdf, sem) of ONE voxel content over the voxel box [-64, 64) x [0, 64) x [0, 64), cut into
+    blocks of vps^3: 1024 blocks at 8, 128 at 16, 16 at 32, 2 at 64 — the same 1024 resident tiles, block layout the only difference."""
+    origin, t, s = same_map_voxels()
+    idx, tb = to_blocks(origin, t, vps)
+    return idx, tb, to_blocks(origin, s, vps)[1]
+
+
+def planted_voxels(vps, blocks=((-1, 0, 0), (0, 0, 0))):
+    """Global voxels at the local indices 0, vps - 1, vps (vps - 1) and vps^3 - 1 of each block: the four corners of the linear
+    index range whose decoding l -> (l % vps, l / vps % vps, l / vps^2) a block export has to get right."""
+    out = []
+    for b in blocks:
+        for l in (0, vps - 1, vps * (vps - 1), vps ** 3 - 1):
+            out.append(tuple(int(b[a]) * vps + (l // vps ** a) % vps for a in range(3)))
+    return out
+
+
+def _label_colors():
+    from kimera_semantics_amd import synth
+    return synth.default_label_colors()
 
 
 def _integrator(method, w, h, vps=16, pipeline=0, max_tiles=4096, **extra):
@@ -235,6 +336,12 @@ SPECS = {
     "upload_two_label_vps16": dict(case="upload", field="two_label", vps=16),
     "upload_holes_vps8": dict(case="upload", field="holes", vps=8),
     "upload_holes_vps16": dict(case="upload", field="holes", vps=16),
+    # 4^3 and 8^3 tiles per block: 32 and 256 passes of the count scan, cube addresses of 15 and 18 bits per block
+    "upload_sphere_vps32": dict(case="upload", field="sphere", vps=32),
+    "upload_holes_vps32": dict(case="upload", field="holes", vps=32),
+    "upload_two_label_vps32": dict(case="upload", field="two_label", vps=32),
+    "upload_sphere_vps64": dict(case="upload", field="sphere", vps=64),
+    "integrated_fast_vps32": dict(case="integrated", method=0, cfg=dict(vps=32)),
     "integrated_fast": dict(case="integrated", method=0),
     "integrated_merged": dict(case="integrated", method=1),
     "incremental_equals_from_scratch": dict(case="incremental"),

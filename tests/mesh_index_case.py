@@ -300,6 +300,9 @@ CASES = {"upload": case_upload, "grid": case_grid, "integrated": case_integrated
 
 # name -> spec: the same cases in both tiers
 SPECS = {"upload_%s_vps%d" % (f, v): dict(case="upload", field=f, vps=v) for f in ("sphere", "plane", "two_label", "holes") for v in (8, 16)}
+# vertices shared across the seams of 32^3 blocks ({-1,0}^3) and across the seam x = 0 of two 64^3 blocks
+SPECS["upload_two_label_vps32"] = dict(case="upload", field="two_label", vps=32)
+SPECS["upload_sphere_vps64"] = dict(case="upload", field="sphere", vps=64)
 SPECS.update({
     "exact_zeros_on_voxel_centres": dict(case="grid", field="exact_zeros"),
     "coordinate_of_plus_zero": dict(case="grid", field="plus_zero"),

@@ -180,7 +180,9 @@ def case_serpentine(spec):
     stats, idx, blocks, model = check(g, near, "serpentine, one goal", radius_m=RADIUS)
     assert stats["voxels_reached"] == stats["voxels_traversable"] == len(path) and stats["largest_cost"] == model.stats["largest_cost"] > 3000
     assert cost_at(g, *path[-1]) == stats["largest_cost"]
-    assert stats["rounds"] >= 16 and stats["tile_relaxations"] > len(g.tile_keys()) / 2, stats
+    # (from 32 voxels per side on most resident tiles hold no voxel of the path: the floor counts the tiles the path visits)
+    n_tiles = len(g.tile_keys()) if spec["vps"] <= 16 else len({tuple(c >> 3 for c in v) for v in path})
+    assert stats["rounds"] >= 16 and stats["tile_relaxations"] > n_tiles / 2, stats
     walk = g.nav_paths(far, 1024)
     M.assert_paths(walk, M.paths(model, far, 1024), "the walk back")
     assert walk["status"][0] == M.REACHED and walk["cost"][0] == stats["largest_cost"]
@@ -545,17 +547,38 @@ def case_errors(spec):
     return {}
 
 
-CASES = {"open_box": case_open_box, "seams": case_seams, "serpentine": case_serpentine, "random": case_random, "radius": case_radius,
+def case_planted(spec):
+    """A handful of free voxels at the ends of the linear index range of two blocks: nav_blocks against the model (goal voxels
+    0, the other planted voxels unreached, everything else blocked)."""
+    vps = spec["vps"]
+    vox = mesh_case.planted_voxels(vps)
+    g = mesh_case._integrator(0, 64, 48, vps=vps)
+    g.upload(*field_blocks(vox, vps))
+    g.esdf_update(**ECFG)
+    goals = np.array([centre(*v) for v in vox[::2]], F)
+    stats, idx, blocks, model = check(g, goals, "planted", radius_m=RADIUS)
+    # ((-1, 0, 0) and (0, 0, 0) touch across the seam: one planted voxel that is no goal is reached, at the cost of a face step)
+    assert len(idx) == 2 and stats["voxels_traversable"] == len(vox) and stats["goals_used"] == len(goals), stats
+    assert (blocks == 0).sum() == len(goals) and stats["voxels_reached"] == len(goals) + 1 and (blocks == M.UNREACHED).sum() == len(vox) - len(goals) - 1
+    assert (blocks != M.BLOCKED).sum() == len(vox)
+    g.close()
+    return dict(stats)
+
+
+CASES = {"planted": case_planted, "open_box": case_open_box, "seams": case_seams, "serpentine": case_serpentine, "random": case_random, "radius": case_radius,
          "max_cost": case_max_cost, "paths": case_paths, "lifetime": case_lifetime, "reads_only": case_reads_only, "errors": case_errors}
 
 # name -> (spec, extra environment): the same cases in both tiers
 SPECS = {}
-for _vps in (8, 16):
+for _vps in (8, 16, 32):
     for _case in ("open_box", "seams", "random"):
         SPECS["%s_vps%d" % (_case, _vps)] = (dict(case=_case, vps=_vps), {})
 SPECS.update({
     "serpentine_vps8": (dict(case="serpentine", vps=8), {}),
     "serpentine_vps16": (dict(case="serpentine", vps=16), {}),
+    "serpentine_vps32": (dict(case="serpentine", vps=32), {}),
+    "paths_vps32": (dict(case="paths", vps=32), {}),
+    "planted_vps64": (dict(case="planted", vps=64), {}),
     "radius_vps8": (dict(case="radius", vps=8), {}),
     "max_cost_vps8": (dict(case="max_cost", vps=8), {}),
     "paths_vps8": (dict(case="paths", vps=8), {}),

@@ -67,7 +67,8 @@ def seams_field(vps):
            (14, 12, 3): on(13), (15, 12, 3): (13, 1.0, -JUST_ABOVE), (16, 12, 3): (13, 1.0, -VOXEL),
            (31, 3, 3): on(14), (3, 3, 6): (5, 1.0, float("nan"))}
     idx, t, s = voxel_field(vox, vps, resident=[(8, 0, 0), (0, 8, 0)])
-    assert not any(tuple(b) == (32 // vps, 0, 0) for b in idx)   # (the tile beside (31,3,3) stays absent)
+    # (the tile beside (31,3,3) stays absent; in a block of 64 it is resident and empty, which joins nothing either)
+    assert vps == 64 or not any(tuple(b) == (32 // vps, 0, 0) for b in idx)
     return idx, t, s
 
 
@@ -97,9 +98,22 @@ SERPENTINE_VOXELS = 4 * (16 * 32 + 15) + 3 * 3
 
 def random_field(vps, seed=RANDOM_SEED):
     """4 x 4 x 4 tiles from (-16, -16, -16): 40 % surface voxels, of the others half never observed and half far from the surface;
-    three labels uniformly."""
+    three labels uniformly.  At 32 and 64 voxels per side: the voxels of the vps-16 field, in the blocks {-1, 0}^3 that hold them, and
+    every other voxel of those blocks never observed."""
     from kimera_semantics_amd import binding as B
     from kimera_semantics_amd import synth
+    if vps > 16:
+        idx16, t16, s16 = random_field(16, seed)
+        box = ((-vps, vps),) * 3
+        out = []
+        for rows in (t16, s16):
+            big = np.zeros((2 * vps,) * 3, rows.dtype)
+            if rows.dtype == B.SEM_DTYPE:
+                big["priors"] = np.float32(-0.60205999132)
+            big[vps - 16:vps + 16, vps - 16:vps + 16, vps - 16:vps + 16] = mesh_case.from_blocks(idx16, rows, 16, ((-16, 16),) * 3)
+            idx, blocked = mesh_case.to_blocks([b[0] for b in box], big, vps)
+            out.append(blocked)
+        return idx, out[0], out[1]
     rng = np.random.default_rng(seed)
     n = 32 // vps
     idx = np.array([(x, y, z) for x in range(-n // 2, n // 2) for y in range(-n // 2, n // 2) for z in range(-n // 2, n // 2)], np.int32)
@@ -389,15 +403,29 @@ def case_query(spec):
     return {}
 
 
-CASES = {"seams": case_seams, "serpentine": case_serpentine, "random": case_random, "order": case_order, "integrated": case_integrated,
+def case_planted(spec):
+    """A handful of surface voxels at the ends of the linear index range of two blocks: the per-voxel ids of the block export against
+    the model ((-1, 0, 0) and (0, 0, 0) touch across the seam and make one object of two)."""
+    vox = mesh_case.planted_voxels(spec["vps"])
+    g = mesh_case._integrator(0, 64, 48, vps=spec["vps"])
+    g.upload(*voxel_field({v: (5, 1.0, 0.0) for v in vox}, spec["vps"]))
+    rec, stats, idx, ids, model = check(g, dict(min_voxels=1), "planted")
+    assert len(idx) == 2 and stats["voxels_surface"] == stats["voxels_in_objects"] == (ids != NONE).sum() == len(vox), stats
+    assert stats["objects"] == len(vox) - 1 and stats["largest_object_voxels"] == 2, stats
+    g.close()
+    return dict(stats)
+
+
+CASES = {"planted": case_planted, "seams": case_seams, "serpentine": case_serpentine, "random": case_random, "order": case_order, "integrated": case_integrated,
          "lifetime": case_lifetime, "errors": case_errors, "query": case_query}
 
 # name -> spec: the same cases in both tiers
 SPECS = {}
-for _vps in (8, 16):
+for _vps in (8, 16, 32):
     for _case in ("seams", "serpentine", "random", "order", "query"):
         SPECS["%s_vps%d" % (_case, _vps)] = dict(case=_case, vps=_vps)
 SPECS.update({
+    "planted_vps64": dict(case="planted", vps=64),
     "integrated_fast": dict(case="integrated", method=0),
     "integrated_merged": dict(case="integrated", method=1),
     "lifetime": dict(case="lifetime"),

@@ -91,8 +91,9 @@ def g_capacity(g):
     return g.remove_blocks(np.zeros((0, 3), np.int32))["pool_capacity_tiles"]
 
 
-def remove_and_check(make, field, pick, what, by_distance=None):
-    """One context, one removal: pick(blocks_by_slot) -> the block list to pass (or by_distance = (centre, radius))."""
+def remove_and_check(make, field, pick, what, by_distance=None, on_the_radius=False):
+    """One context, one removal: pick(blocks_by_slot) -> the block list to pass (or by_distance = (centre, radius)).  on_the_radius: the
+    case is ABOUT blocks whose d2 equals max_distance^2 bit for bit, so the float32 rule alone decides."""
     g = make()
     g.upload(*field)
     before = g.download()
@@ -104,7 +105,8 @@ def remove_and_check(make, field, pick, what, by_distance=None):
         stats = g.remove_blocks(listed)
     else:
         centre, radius = by_distance
-        M.assert_away_from_threshold(before[0], centre, radius, VOXEL, g.vps)
+        if not on_the_radius:
+            M.assert_away_from_threshold(before[0], centre, radius, VOXEL, g.vps)
         removed = M.removed_of_distance(before[0], centre, radius, VOXEL, g.vps)
         stats = g.remove_distant(centre, radius)
     f = fresh_with(make, *before, removed)
@@ -237,6 +239,29 @@ def case_distance(spec):
     kinds = [v["blocks_removed"] for v in out.values()]
     assert min(kinds) == 0 and max(kinds) > 0, kinds        # (one query removes nothing, the others something)
     return out
+
+
+def case_distance_on_the_radius(spec):
+    """Blocks whose origin lies on the radius exactly stay (the rule is d2 > r^2): the centre at the origin and r = 2 block sizes in
+    float32, so that d2 and r^2 of the blocks (+-2, 0, 0), (0, +-2, 0), (0, 0, 2) are the same float32 product.  The block size is
+    voxel_size * vps: with any other factor these blocks fall on one side of the radius."""
+    vps = spec["vps"]
+    blocks = [(-2, 0, 0), (0, 0, 0), (2, 0, 0), (3, 0, 0)]
+    if vps < 64:
+        blocks += [(-3, 0, 0), (-1, 0, 0), (1, 0, 0), (0, 2, 0), (0, -2, 0), (0, 0, 2), (2, 1, 0), (0, -3, 0), (1, 1, 1)]
+    idx = np.array(sorted(blocks), np.int32)
+    tiles = len(idx) * (vps // 8) ** 3
+    make = lambda: _ctx(vps=vps, max_tiles=max(512, 2 * tiles))
+    radius = float(np.float32(2) * (np.float32(VOXEL) * np.float32(vps)))
+    far = M.distant_f32(idx, [0, 0, 0], radius, VOXEL, vps)
+    on = np.abs(M.distance_f64(idx, [0, 0, 0], VOXEL, vps) - radius) == 0
+    assert on.sum() == (2 if vps == 64 else 5) and not far[on].any() and far.sum() == (1 if vps == 64 else 4), (on, far)
+    g, f, before, removed, stats = remove_and_check(make, esdf_case.random_field(idx, vps, 5), None, "on the radius", by_distance=([0, 0, 0], radius),
+                                                    on_the_radius=True)
+    assert _same(removed, idx[far]) and stats["blocks_removed"] == far.sum() and stats["tiles_removed"] == far.sum() * (vps // 8) ** 3, stats
+    g.close()
+    f.close()
+    return dict(stats)
 
 
 # ---- flags and syncs -------------------------------------------------------------------------------------------------------------
@@ -692,7 +717,7 @@ def case_errors(spec):
     return {}
 
 
-CASES = {"pattern": case_pattern, "scattered": case_scattered, "distance": case_distance, "flags": case_flags, "grow": case_grow,
+CASES = {"pattern": case_pattern, "scattered": case_scattered, "distance": case_distance, "distance_on_the_radius": case_distance_on_the_radius, "flags": case_flags, "grow": case_grow,
          "integrate": case_integrate, "mesh": case_mesh, "esdf": case_esdf, "objects": case_objects, "render_align": case_render_align,
          "locality": case_locality, "sliding": case_sliding, "errors": case_errors}
 
@@ -704,6 +729,9 @@ SPECS = {
     "scattered_block_vps16": dict(case="scattered"),
     "distance_vps8": dict(case="distance", vps=8, queries=[[[0.1, 0.1, 0.3], 5.0], [[0.1, 0.1, 0.3], 0.71], [[-0.9, 0.4, 0.0], 0.33]]),
     "distance_vps16": dict(case="distance", vps=16, queries=[[[0.1, 0.1, 0.3], 5.0], [[0.3, 0.2, 0.1], 0.93]]),
+    "distance_vps32": dict(case="distance", vps=32, queries=[[[0.1, 0.1, 0.3], 9.0], [[0.3, 0.2, 0.1], 1.93]]),
+    "distance_on_the_radius_vps32": dict(case="distance_on_the_radius", vps=32),
+    "distance_on_the_radius_vps64": dict(case="distance_on_the_radius", vps=64),
     "flags_travel": dict(case="flags"),
     "grow_and_reupload": dict(case="grow"),
     "integrate_merged": dict(case="integrate"),

@@ -44,6 +44,21 @@ def test_separable_tie_count_equals_brute_force_tie_count():
     assert found.sum() > 5000 and d2[found].min() >= 1 and d2[found].max() <= 3 * R * R and (d2[~found] == 0).all()
 
 
+def test_conditions_that_keep_the_cases_at_32_and_64_voxels_per_side_from_being_empty():
+    """What case_upload asserts beside the comparison, with the model alone (separable form) on the fields of the new cases."""
+    for name, spec in esdf_case.SPECS.items():
+        if spec["case"] != "upload" or spec["vps"] < 32 or spec.get("max_distance_m") != 0.4:
+            continue
+        idx, t, s = esdf_case.make_field(spec["field"], spec["vps"])
+        m = esdf_model.esdf_from_blocks(idx, t, s["label"], spec["vps"], esdf_case.VOXEL, form="separable", keep_keys=(spec["field"] == "random"),
+                                        min_distance_m=esdf_case.MIN_DISTANCE, max_distance_m=0.4)
+        assert m.stats["voxels_observed"] > 1000 and m.stats["voxels_fixed"] > 500, (name, m.stats)
+        if spec["field"] == "sphere":
+            assert m.stats["voxels_clamped"] > 0 and m.blocks(idx)["distance"].min() == -np.float32(0.4), name
+        if spec["field"] == "random":
+            assert esdf_model.tied_voxels(m, 8, form="separable") >= 1000, name
+
+
 def test_model_on_an_analytic_sphere_is_the_distance_to_the_sphere():
     vps = 8
     idx, t, s = esdf_case.make_field("sphere", vps)

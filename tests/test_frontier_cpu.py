@@ -87,7 +87,7 @@ def test_model_gives_the_hand_table_of_the_faces_field(vps):
 
 
 def test_random_field_holds_what_its_seed_is_chosen_for():
-    for vps in (8, 16):
+    for vps in (8, 16, 32):
         m = M.frontiers(C.hand_store(C.random_voxels(), vps), radius_m=C.SMALL, min_voxels=1, vps=vps)
         n = m.records["n_voxels"]
         assert m.stats["components"] >= 100 and (n == 1).sum() >= 5 and n.max() >= 300 and C.crossing_a_seam(m.records) >= 20

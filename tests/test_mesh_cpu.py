@@ -5,6 +5,7 @@
 3. the DEVICE CODE on the host functional model (tools/emu) against the model, bit for bit: one child process per case
    (tests/mesh_case.py), started side by side like those of tests/test_emu_parity.py;
 4. the PLY round trip."""
+import hashlib
 import itertools
 import json
 import os
@@ -161,6 +162,50 @@ def test_model_two_label_field_carries_both_labels_and_their_colours():
     assert (m["rgba"] == lut[m["labels"]]).all()
     left = m["xyz"][:, 0] < -mesh_case.VOXEL
     assert (m["labels"][left] == 3).all() and (m["labels"][m["xyz"][:, 0] > mesh_case.VOXEL] == 7).all()
+
+
+# sha256 over indices, tsdf and sem of make_field(kind, vps), recorded before the block range was derived from a voxel extent
+FIELD_HASHES = {
+    ("sphere", 8): "088be9c594e903ad36df42ce937f42a9634855ea3b8dec1e874482147a1b7d7f",
+    ("sphere", 16): "6316d5cc1630fe5b98102d3a1be7ef4c28994013eab022e7a7250df3af1bd932",
+    ("plane", 8): "9af4fe57504fb09949a847da241cd887b4815291ed55364d6240c96e29340c54",
+    ("plane", 16): "a434d11f466736490d558ce6f1f3e77c53e71db8d0ad963d1749a49210e61fc7",
+    ("two_label", 8): "1965ef22f02628f8e231dcb2fd851e2b1b6154adaa935f85895b106bed7139d2",
+    ("two_label", 16): "20fb8790fc3d1e3d48f9f1a43d79150709de3a24b52e2a0616cd5e9293130664",
+    ("holes", 8): "7776be22da8ec57204b5ea7829e9d69b2ec073c5d8d6f30d22b6418b10ec7dd8",
+    ("holes", 16): "19ac8415fca43d4aac0b1261a7c4b3d0c5783e01a2624dd338074b9c0bb71c60",
+}
+
+
+def test_fields_at_8_and_16_voxels_per_side_are_the_bytes_they_always_were():
+    for (kind, vps), want in FIELD_HASHES.items():
+        idx, t, s = mesh_case.make_field(kind, vps)
+        assert hashlib.sha256(idx.tobytes() + t.tobytes() + s.tobytes()).hexdigest() == want, (kind, vps)
+
+
+def test_fields_at_32_and_64_voxels_per_side_cover_whole_blocks_across_a_seam():
+    for vps, blocks in ((32, 8), (64, 2)):
+        for kind in ("sphere", "plane", "two_label"):
+            idx, t, s = mesh_case.make_field(kind, vps)
+            assert len(idx) == blocks and t.shape == s.shape == (blocks, vps ** 3), (kind, vps)
+            inside = (t["distance"] < 0).any(axis=1)
+            assert inside[(idx[:, 0] == -1)].any() and inside[(idx[:, 0] == 0)].any(), (kind, vps)   # the surface on both sides of x = 0
+    idx, t, _ = mesh_case.make_field("holes", 32)
+    assert len(idx) == 7 and 0.08 < (t["weight"] == 0).mean() < 0.12      # one block absent, a tenth of the voxels unobserved
+
+
+def test_conditions_that_keep_the_upload_cases_from_being_empty_hold_for_the_model_alone():
+    """The triangle floor of every upload case, with the model on the field (no library involved)."""
+    for name, spec in mesh_case.SPECS.items():
+        if spec["case"] != "upload" or spec["vps"] < 32:
+            continue
+        idx, t, s = mesh_case.make_field(spec["field"], spec["vps"])
+        m = mesh_model.mesh_from_blocks(idx, t, spec["vps"], mesh_case.VOXEL, labels=s["label"])
+        assert len(m["xyz"]) // 3 >= spec.get("triangles_at_least", 500), (name, len(m["xyz"]) // 3)
+        if spec["field"] == "two_label":
+            assert set(np.unique(m["labels"])) == {3, 7}
+        if spec["field"] == "sphere":   # the same sphere at every block size: the same number of triangles
+            assert len(m["xyz"]) // 3 == 5424, (name, len(m["xyz"]) // 3)
 
 
 # ---- 3. the device code on the functional model: one child per case, started together by test_emu_parity's fixture ----

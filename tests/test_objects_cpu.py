@@ -59,7 +59,7 @@ def test_model_on_the_analytic_sphere_is_one_object_centred_on_it():
 
 
 def test_fields_hold_what_the_cases_are_chosen_for():
-    for vps in (8, 16):
+    for vps in (8, 16, 32):
         m, _ = _model("seams", vps, min_voxels=1)
         assert objects_case._by_first(m.records) == objects_case.SEAMS_EXPECTED
         m, _ = _model("serpentine", vps)
