@@ -694,6 +694,94 @@ int ks_frontiers_download(ks_ctx* ctx, ks_frontier* out, size_t cap, size_t* n);
 int ks_frontiers_download_blocks(ks_ctx* ctx, const int32_t* block_idx_xyz, size_t n, uint32_t* out /* n * vps^3 ids, host block layout */);
 int ks_frontiers_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* id);
 
+/* ---- rooms over the stored ESDF: free space cut where it gets narrow, the pieces named, every free voxel and every object
+ * attached to its piece, and which pieces touch where (new: the layer the scene-graph work downstream of this map builds next
+ * after the objects, on the host: connected components of a truncated ESDF, a multi-source Dijkstra, a join by hand) ----
+ * The contract is DESIGN.md, section "Rooms"; it is this library's own.  The input is the ESDF STORE exactly as ks_nav_update and
+ * ks_frontiers_update read it, with nothing refreshed; a voxel outside the store's tiles reads the default record.
+ * A voxel is OBSERVED iff bit 0 of its flags is set, FREE iff it is observed, distance >= free_distance_m (an f32 compare: a NaN is
+ * not free) and, with use_bounds, its global index lies inside the inclusive box bounds_min..bounds_max; CORE iff it is free and
+ * distance >= core_distance_m.  Core voxels are adjacent iff their global indices differ by at most 1 on every axis (26-connectivity,
+ * across tile seams); a COMPONENT is a class of the closure, a ROOM a component of at least min_core_voxels voxels.  Order (part of
+ * the ABI): rooms ascend by pack_coord3 of their smallest core voxel.
+ * GROWTH: the graph is the free voxels, 26-connected, with steps of KS_NAV_COST_FACE / _EDGE / _CORNER (the graph of the navigation
+ * field with free_distance_m in the place of the radius).  cost(v) is the smallest sum of step costs from v to a core voxel of any
+ * room (0 on those cores); a free voxel without such a path, or with a cost above max_cost, is UNASSIGNED.  room(v) is the smallest
+ * room index among the rooms that have a core voxel at exactly cost(v) from v: the lexicographic minimum of (path cost, room of the
+ * path's start) over all paths.  Core voxels of components below min_core_voxels are ordinary free voxels here.
+ * Per voxel of the store's tiles two uint32 are stored: the room index (KS_ROOM_NONE where the voxel is not free or unassigned) and
+ * the cost (KS_NAV_BLOCKED where not free, KS_NAV_UNREACHED where unassigned).
+ * ks_room: everything is an integer; bb and sum run over the ASSIGNED voxels (cores included), centroid as for ks_object;
+ * clearance_bits is the bit pattern of the largest stored distance among its core voxels (a non-negative finite f32: unsigned order
+ * is numeric order) and centre_voxel the smallest core voxel in (x, y, z) order attaining it: always free, and its centre
+ * ((float)v + 0.5f) * voxel_size is a valid goal for ks_nav_update.
+ * LINKS: an assigned voxel v of room r is a CONTACT of the link {r, q} for every q != r such that some 26-neighbour of v is assigned
+ * to q (a voxel touching two other rooms counts in two links).  n_contacts counts the contacts of both sides, clearance_bits is the
+ * largest stored distance among them (half the width of the passage), door_voxel the smallest contact in (x, y, z) order attaining
+ * it and door_room the room that voxel is assigned to.  Links ascend by (room_a, room_b), room_a < room_b.
+ * JOIN with the objects: if ks_objects_update has a stored result when ks_rooms_update runs, object i's room is the room of the
+ * minimum of (cost, room) over the voxels whose stored object id is i (in slots both stores cover) that are assigned to a room, or
+ * KS_ROOM_NONE; n_objects of a room counts the objects joined to it.  The objects are read at the call: a later ks_objects_update
+ * leaves the rooms as they were.  Without stored objects the list is empty (no error).
+ * ks_rooms_update   completes the frames in flight (their statistics stay owed) and stores the records, the links, the room of every
+ *                   object and the two per-voxel planes.  The result is a snapshot of the ESDF store with the lifetime of the frontiers:
+ *                   later integrate, upload, merge and fuse calls leave it; a successful ks_esdf_update or ks_esdf_refresh, a
+ *                   ks_remove_blocks* call that takes tiles out, ks_clear, ks_clear_voxels and a ks_rooms_update that fails drop it.
+ *                   It only READS: the map, the flags, both stale bits, the mesh and its index, the ESDF, the objects, the
+ *                   navigation field and the frontiers stay as they were.  Two calls give the same bytes, and so do the same voxels
+ *                   uploaded in another block order.  stats: rounds and tile_relaxations are diagnostics that may differ from run
+ *                   to run; every other field is contractual (workspace_bytes: DESIGN.md §25.2).
+ * ks_rooms_size / ks_rooms_download / ks_rooms_links_download   the numbers of records and links / the records / the links.
+ * ks_rooms_objects  the room index per object of the join (cap >= their number, *n receives it).
+ * ks_rooms_download_blocks   vps^3 values per host-layout block and plane; either output may be NULL, not both; absent blocks read
+ *                   KS_ROOM_NONE and KS_NAV_BLOCKED.
+ * ks_rooms_query    the room of the voxel that contains each point (the point-to-voxel rule of ks_esdf_query).
+ * Errors: KS_ERR_INVALID_ARG (NULL ctx or cfg; a threshold negative or not finite; core_distance_m < free_distance_m;
+ * min_core_voxels < 1; max_cost above KS_NAV_MAX_COST; use_bounds with a bounds_min above its bounds_max; no stored ESDF; reads
+ * without a stored result; capacity too small; NULL input or output with n > 0; a context in a failed state), KS_ERR_UNSUPPORTED (a
+ * marcher context; a store of 2^23 tiles or more; a relaxation still active after max_rounds rounds: nothing stays stored),
+ * KS_ERR_HIP (nothing stays stored).  A store with no room is no error: zero records, every free voxel unassigned. */
+typedef struct ks_rooms_config {
+  float free_distance_m;    /* 0.0 */
+  float core_distance_m;    /* 0.5 */
+  uint32_t min_core_voxels; /* 64 */
+  uint32_t max_cost;        /* 0: KS_NAV_MAX_COST */
+  uint32_t max_rounds;      /* 0: 1 << 20, for each of the two relaxations */
+  int32_t use_bounds;       /* 0 */
+  int32_t bounds_min[3], bounds_max[3]; /* inclusive, global voxel indices; read only with use_bounds */
+} ks_rooms_config; /* 48 bytes */
+typedef struct ks_rooms_stats {
+  uint64_t voxels_free, voxels_core, components, rooms, voxels_assigned, voxels_unassigned, largest_room_voxels, largest_cost, links,
+      contacts, objects_seen, objects_joined, rounds, tile_relaxations, workspace_bytes;
+} ks_rooms_stats; /* 120 bytes */
+typedef struct ks_room {
+  int32_t first_voxel[3]; /* the room's smallest core voxel in (x, y, z) order: its identity */
+  uint32_t n_core_voxels;
+  int32_t bb_min[3], bb_max[3]; /* inclusive, over the assigned voxels (cores included) */
+  int64_t sum[3];               /* index sums over the assigned voxels */
+  uint32_t n_voxels;            /* assigned voxels */
+  uint32_t largest_cost;        /* over its assigned voxels */
+  uint32_t clearance_bits;      /* bit pattern of the largest stored distance among its core voxels */
+  int32_t centre_voxel[3];      /* the smallest core voxel in (x, y, z) order attaining it */
+  uint32_t n_links, n_objects;
+} ks_room; /* 96 bytes */
+typedef struct ks_room_link {
+  uint32_t room_a, room_b;  /* a < b */
+  uint32_t n_contacts;      /* contacts of both sides */
+  uint32_t clearance_bits;  /* largest stored distance among the contacts: half the width of the passage */
+  int32_t door_voxel[3];    /* the smallest contact in (x, y, z) order attaining it */
+  uint32_t door_room;       /* the room door_voxel is assigned to */
+} ks_room_link; /* 32 bytes */
+#define KS_ROOM_NONE 0xffffffffu
+int ks_rooms_default_config(ks_rooms_config* cfg);
+int ks_rooms_update(ks_ctx* ctx, const ks_rooms_config* cfg, ks_rooms_stats* stats /* may be NULL */);
+int ks_rooms_size(ks_ctx* ctx, size_t* n_rooms, size_t* n_links /* either may be NULL, not both */);
+int ks_rooms_download(ks_ctx* ctx, ks_room* out, size_t cap, size_t* n);
+int ks_rooms_links_download(ks_ctx* ctx, ks_room_link* out, size_t cap, size_t* n);
+int ks_rooms_objects(ks_ctx* ctx, uint32_t* room_of_object, size_t cap, size_t* n);
+int ks_rooms_download_blocks(ks_ctx* ctx, const int32_t* block_idx_xyz, size_t n, uint32_t* room, uint32_t* cost /* n * vps^3 each */);
+int ks_rooms_query(ks_ctx* ctx, const float* xyz /* host, world frame */, size_t n, uint32_t* room);
+
 /* ---- view information gain over the stored ESDF: how much unobserved space each of n candidate camera poses would see (new: the
  * hot loop of a next-best-view explorer, a ray caster on the host over a downloaded layer) ----
  * The contract is DESIGN.md, section "View information gain"; it is this library's own.  The input is the ESDF STORE exactly as

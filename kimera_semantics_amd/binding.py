@@ -51,6 +51,8 @@ ABI_SYMBOLS = [
     "ks_mesh_index", "ks_mesh_index_size", "ks_mesh_index_download",
     "ks_nav_default_config", "ks_nav_update", "ks_nav_query", "ks_nav_query_device", "ks_nav_download_blocks", "ks_nav_paths", "ks_nav_paths_device",
     "ks_frontiers_default_config", "ks_frontiers_update", "ks_frontiers_size", "ks_frontiers_download", "ks_frontiers_download_blocks", "ks_frontiers_query",
+    "ks_rooms_default_config", "ks_rooms_update", "ks_rooms_size", "ks_rooms_download", "ks_rooms_links_download", "ks_rooms_objects",
+    "ks_rooms_download_blocks", "ks_rooms_query",
     "ks_view_gain_default_config", "ks_view_gain", "ks_view_gain_device",
     "ks_path_shorten_default_config", "ks_path_shorten", "ks_path_shorten_device",
 ]
@@ -266,6 +268,38 @@ def frontier_bounds(box_min_m, box_max_m, voxel_size):
     return lo, hi
 
 
+class KsRoomsConfig(C.Structure):
+    _fields_ = [("free_distance_m", C.c_float), ("core_distance_m", C.c_float), ("min_core_voxels", C.c_uint32), ("max_cost", C.c_uint32),
+                ("max_rounds", C.c_uint32), ("use_bounds", C.c_int32), ("bounds_min", C.c_int32 * 3), ("bounds_max", C.c_int32 * 3)]
+
+
+class KsRoomsStats(C.Structure):
+    _fields_ = [(k, C.c_uint64) for k in ("voxels_free", "voxels_core", "components", "rooms", "voxels_assigned", "voxels_unassigned",
+                                          "largest_room_voxels", "largest_cost", "links", "contacts", "objects_seen", "objects_joined",
+                                          "rounds", "tile_relaxations", "workspace_bytes")]
+
+
+# ks_room: 96 bytes; centroid as for ks_object (room_centroids), a goal inside the room: room_centres.  ks_room_link: 32 bytes.
+ROOM_DTYPE = np.dtype([("first_voxel", "<i4", (3,)), ("n_core_voxels", "<u4"), ("bb_min", "<i4", (3,)), ("bb_max", "<i4", (3,)),
+                       ("sum", "<i8", (3,)), ("n_voxels", "<u4"), ("largest_cost", "<u4"), ("clearance_bits", "<u4"),
+                       ("centre_voxel", "<i4", (3,)), ("n_links", "<u4"), ("n_objects", "<u4")])
+ROOM_LINK_DTYPE = np.dtype([("room_a", "<u4"), ("room_b", "<u4"), ("n_contacts", "<u4"), ("clearance_bits", "<u4"),
+                            ("door_voxel", "<i4", (3,)), ("door_room", "<u4")])
+KS_ROOM_NONE = 0xffffffff
+
+
+def room_centroids(records, voxel_size) -> np.ndarray:
+    """Centroids in metres, (n, 3) f64, of ks_room records over their assigned voxels: the host's one division.  The centroid of an
+    L-shaped room can lie inside a wall; room_centres never does."""
+    return object_centroids(records, voxel_size)
+
+
+def room_centres(records, voxel_size) -> np.ndarray:
+    """(n, 3) f32: the centres of the records' centre_voxel, ((float)v + 0.5f) * voxel_size — free, and valid goals for nav_update."""
+    v = np.asarray(records)["centre_voxel"].astype(np.float32)
+    return (v + np.float32(0.5)) * np.float32(voxel_size)
+
+
 class KsViewGainConfig(C.Structure):
     _fields_ = [("min_range_m", C.c_float), ("max_range_m", C.c_float), ("step_m", C.c_float), ("stop_distance_m", C.c_float),
                 ("width", C.c_uint32), ("height", C.c_uint32), ("K", C.c_float * 4), ("label", C.c_uint32), ("pad", C.c_uint32),
@@ -312,7 +346,7 @@ def build(force: bool = False) -> str:
     """Compile libks_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
     src_dir = os.path.join(_HERE, "csrc")
     srcs = [os.path.join(src_dir, f) for f in ("ks_hip.hip", "ks_types.h", "ks_k_rays.h", "ks_k_bundle_order.h", "ks_k_march.h", "ks_k_exact.h", "ks_k_apply.h",
-                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_view_gain.h", "ks_k_path.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
+                                                "ks_k_apply_xl.h", "ks_k_shard.h", "ks_k_shard_merged.h", "ks_k_io.h", "ks_k_mesh.h", "ks_k_mesh_index.h", "ks_k_esdf.h", "ks_k_esdf_read.h", "ks_k_render.h", "ks_k_align.h", "ks_k_objects.h", "ks_k_nav.h", "ks_k_frontier.h", "ks_k_rooms.h", "ks_k_view_gain.h", "ks_k_path.h", "ks_k_remove.h", "ks_k_fuse.h", "ks_mc_tri_table.inc", "ks_device_math.h", "ks_radix_sort.h", "ks_owned.h")]
     srcs.append(os.path.join(_HERE, "..", "include", "ks_hip.h"))
     stale = (not os.path.exists(LIB_PATH)) or any(
         os.path.exists(s) and os.path.getmtime(s) > os.path.getmtime(LIB_PATH) for s in srcs)
@@ -425,6 +459,14 @@ def lib():
         L.ks_frontiers_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
         L.ks_frontiers_download_blocks.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_frontiers_query.argtypes = [vp, vp, C.c_size_t, vp]
+        L.ks_rooms_default_config.argtypes = [C.POINTER(KsRoomsConfig)]
+        L.ks_rooms_update.argtypes = [vp, C.POINTER(KsRoomsConfig), C.POINTER(KsRoomsStats)]
+        L.ks_rooms_size.argtypes = [vp, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t)]
+        L.ks_rooms_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_rooms_links_download.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_rooms_objects.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t)]
+        L.ks_rooms_download_blocks.argtypes = [vp, vp, C.c_size_t, vp, vp]
+        L.ks_rooms_query.argtypes = [vp, vp, C.c_size_t, vp]
         L.ks_view_gain_default_config.argtypes = [C.POINTER(KsViewGainConfig)]
         for name in ("ks_view_gain", "ks_view_gain_device"):
             getattr(L, name).argtypes = [vp, vp, C.c_size_t, C.POINTER(KsViewGainConfig), vp, C.POINTER(KsViewGainStats)]
@@ -940,6 +982,77 @@ class HipIntegrator:
         xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
         out = np.zeros(len(xyz), dtype=np.uint32)
         self._chk(lib().ks_frontiers_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
+        return out
+
+    # ---- rooms over the stored ESDF (DESIGN.md, section "Rooms") ----
+    def rooms_config(self, **cfg) -> KsRoomsConfig:
+        rc = KsRoomsConfig()
+        lib().ks_rooms_default_config(C.byref(rc))
+        for k, v in cfg.items():
+            if k not in [f for f, _ in KsRoomsConfig._fields_]:
+                raise AttributeError(k)
+            if v is None:
+                continue
+            if k in ("bounds_min", "bounds_max"):
+                v = (C.c_int32 * 3)(*[int(a) for a in v])
+            setattr(rc, k, v)
+        return rc
+
+    def rooms(self, **cfg):
+        """ks_rooms_update + the two downloads: the free voxels of the STORED ESDF whose distance reaches core_distance_m clustered
+        into rooms, every other free voxel handed to the room nearest through free space, the contacts between rooms as links, the
+        stored objects joined.  Returns (records (n,) ROOM_DTYPE ascending by first_voxel, links (m,) ROOM_LINK_DTYPE ascending by
+        (room_a, room_b), stats dict).  cfg are the fields of KsRoomsConfig.  The contract is DESIGN.md, section "Rooms";
+        room_ids() / room_costs() / room_query() / room_objects() read what it stores."""
+        rc, st = self.rooms_config(**cfg), KsRoomsStats()
+        self._chk(lib().ks_rooms_update(self._h, C.byref(rc), C.byref(st)))
+        return self.room_records(), self.room_links(), {k: int(getattr(st, k)) for k, _ in KsRoomsStats._fields_}
+
+    def room_records(self) -> np.ndarray:
+        """The records of the last rooms() call."""
+        n = C.c_size_t()
+        self._chk(lib().ks_rooms_size(self._h, C.byref(n), None))
+        out = np.zeros(n.value, dtype=ROOM_DTYPE)
+        self._chk(lib().ks_rooms_download(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def room_links(self) -> np.ndarray:
+        """The links of the last rooms() call."""
+        n = C.c_size_t()
+        self._chk(lib().ks_rooms_size(self._h, None, C.byref(n)))
+        out = np.zeros(n.value, dtype=ROOM_LINK_DTYPE)
+        self._chk(lib().ks_rooms_links_download(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def room_objects(self) -> np.ndarray:
+        """(n_objects,) u32: the room every object of the objects() result stored at the last rooms() call was joined to, or
+        KS_ROOM_NONE; empty if no objects were stored then."""
+        n = C.c_size_t()
+        lib().ks_rooms_objects(self._h, None, 0, C.byref(n))          # (the count alone: refused as too small unless it is 0)
+        out = np.zeros(n.value, dtype=np.uint32)
+        self._chk(lib().ks_rooms_objects(self._h, _ptr(out), n.value, C.byref(n)))
+        return out
+
+    def _room_plane(self, block_idx, plane) -> np.ndarray:
+        indices = np.ascontiguousarray(block_idx, dtype=np.int32).reshape(-1, 3)
+        out = np.zeros((len(indices), self.vps ** 3), dtype=np.uint32)
+        self._chk(lib().ks_rooms_download_blocks(self._h, _ptr(indices), len(indices), *((_ptr(out), None) if plane == 0 else (None, _ptr(out)))))
+        return out
+
+    def room_ids(self, block_idx) -> np.ndarray:
+        """(N, vps^3) u32 in host block layout: the index of each voxel's room in the records of the last rooms() call, or KS_ROOM_NONE."""
+        return self._room_plane(block_idx, 0)
+
+    def room_costs(self, block_idx) -> np.ndarray:
+        """(N, vps^3) u32 in host block layout: each voxel's cost to the nearest core of a room, KS_NAV_BLOCKED where the voxel is not
+        free, KS_NAV_UNREACHED where it is unassigned."""
+        return self._room_plane(block_idx, 1)
+
+    def room_query(self, xyz) -> np.ndarray:
+        """(n,) u32: the room of the voxel that contains each world point, or KS_ROOM_NONE."""
+        xyz = np.ascontiguousarray(xyz, dtype=np.float32).reshape(-1, 3)
+        out = np.zeros(len(xyz), dtype=np.uint32)
+        self._chk(lib().ks_rooms_query(self._h, _ptr(xyz), len(xyz), _ptr(out)))
         return out
 
     # ---- view information gain over the stored ESDF (DESIGN.md, section "View information gain") ----

@@ -75,6 +75,7 @@ using namespace ksd;
 #include "ks_k_objects.h"
 #include "ks_k_nav.h"
 #include "ks_k_frontier.h"
+#include "ks_k_rooms.h"
 #include "ks_k_view_gain.h"
 #include "ks_k_path.h"
 #include "ks_k_remove.h"
@@ -601,6 +602,34 @@ struct ks_ctx {
   bool fr_valid = false;
   uint32_t fr_tiles = 0;
   size_t fr_count = 0;
+  // ks_rooms_update (ks_k_rooms.h).  Two planes of 512 words per tile slot of the ESDF store they were made from, the records, the
+  // links and the room of every object: a snapshot with the lifetime of the frontiers (drop_rooms); the buffers grow only.
+  DevBuf<uint32_t> rooms_room, rooms_cost;    // [rooms_tiles][512] (rooms_room during an update: the provisional numbers of the roots)
+  DevBuf<uint32_t> rooms_parent;              // the union-find forest of an update, then the voxels' provisional numbers
+  DevBuf<uint8_t> rooms_cls;                  // the class byte of every voxel
+  DevBuf<uint32_t> rooms_lists, rooms_queued; // the work lists of both relaxations, as nav_lists and nav_queued
+  DevBuf<NavCounters> rooms_nav_counters;     // rounds and tile relaxations
+  DevBuf<ObjCounters> rooms_numbered;         // k_obj_number's and k_obj_keys' counts
+  DevBuf<RoomCounters> rooms_counters;
+  DevBuf<ObjAcc> rooms_core_acc;              // per provisional component
+  DevBuf<ks_object> rooms_cores;              // k_obj_records' records of the rooms' cores
+  DevBuf<uint32_t> rooms_final;               // provisional number -> room
+  DevBuf<RoomAcc> rooms_acc;                  // per room
+  DevBuf<uint64_t> rooms_keys[2];             // the sorts' key and payload buffers: components, then contact pairs
+  DevBuf<uint32_t> rooms_vals[2];
+  DevBuf<uint64_t> rooms_head_keys[2];        // ... and the heads of the runs
+  DevBuf<uint32_t> rooms_head_vals[2];
+  DevBuf<RoomLinkAcc> rooms_link_acc;
+  DevBuf<unsigned long long> rooms_obj_best;  // per object: the smallest cost << 32 | room of its voxels
+  DevBuf<ks_room> rooms_records;
+  DevBuf<ks_room_link> rooms_links;
+  DevBuf<uint32_t> rooms_obj_room;            // the room of every object of the join
+  DevBuf<uint32_t> rooms_out;                 // staging of download and query
+  DevBuf<int32_t> rooms_idx;
+  DevBuf<float> rooms_xyz;
+  bool rooms_valid = false;
+  uint32_t rooms_tiles = 0;
+  size_t rooms_count = 0, rooms_link_count = 0, rooms_obj_count = 0;
   // ks_view_gain (ks_k_view_gain.h): nothing is stored between calls; the buffers grow only
   DevBuf<unsigned long long> vg_planes;    // [esdf_tiles][8][observed | occupied | labelled | 0]: 256 B per tile
   DevBuf<uint32_t> vg_slabs;               // [groups][slab_words]: the visited bitmaps of the views that do not fit the LDS
@@ -646,6 +675,12 @@ struct ks_ctx {
 static void drop_frontiers(ks_ctx* c) {
   c->fr_valid = false;
   c->fr_count = 0;
+}
+
+// ... and so do the stored rooms
+static void drop_rooms(ks_ctx* c) {
+  c->rooms_valid = false;
+  c->rooms_count = c->rooms_link_count = c->rooms_obj_count = 0;
 }
 
 int ks_hip_failed(ks_ctx* ctx, const char* what, hipError_t e) {
@@ -3722,6 +3757,7 @@ int ks_esdf_update(ks_ctx* c, const ks_esdf_config* e, ks_esdf_stats* stats) {
   c->esdf_valid = false;   // (a failure below leaves no half-written snapshot readable)
   c->nav_valid = false;    // the navigation field is a snapshot of the store this call replaces
   drop_frontiers(c);       // ... and so are the frontiers (§21)
+  drop_rooms(c);           // ... and the rooms (§25)
   if ((rc = c->esdf_store.reserve(c, (size_t)nt * kTileVoxels, ((size_t)nt + nt / 2 + 64) * kTileVoxels))) return rc;
   if ((rc = c->esdf_counters.reserve(c, 3, 3))) return rc;
   HIPCHK(c, hipMemsetAsync(c->esdf_counters, 0, 3 * sizeof(unsigned long long), st));
@@ -3889,6 +3925,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
     c->esdf_changed.clear();
     c->nav_valid = false;   // the navigation field does not outlive a successful refresh, whatever it recomputed
     drop_frontiers(c);      // ... nor do the frontiers (§21)
+    drop_rooms(c);          // ... nor the rooms (§25)
     return KS_OK;
   }
   if (workspace > max_workspace_bytes) {
@@ -3912,6 +3949,7 @@ int ks_esdf_refresh(ks_ctx* c, uint64_t max_workspace_bytes, ks_esdf_refresh_sta
   c->esdf_valid = false;   // (a failure below leaves no half-written store readable)
   c->nav_valid = false;    // the navigation field is a snapshot of the store as it was
   drop_frontiers(c);       // ... and so are the frontiers (§21)
+  drop_rooms(c);           // ... and the rooms (§25)
   if (grown.get()) {
     if (nt_old) HIPCHK(c, hipMemcpyAsync(grown.get(), c->esdf_store.get(), (size_t)nt_old * kTileVoxels * sizeof(EsdfRecord), hipMemcpyDeviceToDevice, st));
     HIPCHK(c, hipStreamSynchronize(st));
@@ -5096,6 +5134,333 @@ int ks_frontiers_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* id) {
   return KS_OK;
 }
 
+// ---- rooms over the stored ESDF ("Rooms"; ks_k_rooms.h) -------
+int ks_rooms_default_config(ks_rooms_config* r) {
+  if (!r) return KS_ERR_INVALID_ARG;
+  std::memset(r, 0, sizeof(*r));
+  r->core_distance_m = 0.5f;
+  r->min_core_voxels = 64;
+  return KS_OK;
+}
+
+// the work space of an update over nt tiles that finds nc core components, np contact pairs, nl links and joins no objects
+// (DESIGN.md §25.2): per voxel the two planes, the forest and the class byte; per tile two list entries and the queued flag; per
+// component what the objects keep (accumulator, record, two keys, three words) plus the room's accumulator and record; per pair two
+// keys and two words, and as much for the heads (a pair may be one); per link its accumulator and its record; per object its key
+// and its room
+static uint64_t rooms_workspace(uint64_t nt, uint64_t nc, uint64_t np, uint64_t nl, uint64_t no) {
+  return nt * kTileVoxels * 13 + nt * 12 + 12 + sizeof(ObjCounters) + sizeof(NavCounters) + sizeof(RoomCounters) +
+         nc * (sizeof(ObjAcc) + sizeof(ks_object) + 2 * 8 + 3 * 4 + sizeof(RoomAcc) + sizeof(ks_room)) + np * 2 * (2 * 8 + 2 * 4) +
+         nl * (sizeof(RoomLinkAcc) + sizeof(ks_room_link)) + no * (8 + 4);
+}
+
+// One of the two relaxations of ks_rooms_update: list 0 holds the seeded tiles; rounds in groups as in ks_nav_update.  *active is
+// what the next round would take when the loop ends: not 0 after max_rounds rounds.
+extern "C++" template <class Launch>
+static int rooms_relax(ks_ctx* c, uint32_t* counts, uint32_t max_rounds, uint32_t* active, Launch launch) {
+  hipStream_t st = c->stream;
+  uint32_t round = 0;
+  for (;;) {
+    HIPCHK(c, hipMemcpyAsync(active, counts + round % 3u, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    if (*active == 0 || round >= max_rounds) break;
+    const uint32_t group = std::min(kNavRoundsPerRead, max_rounds - round);
+    for (uint32_t k = 0; k < group; ++k, ++round) launch(round);
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_rooms_update(ks_ctx* c, const ks_rooms_config* r, ks_rooms_stats* stats) {
+  if (!c || !r) return KS_ERR_INVALID_ARG;
+  if (stats) std::memset(stats, 0, sizeof(*stats));
+  const char* who = "ks_rooms_update";
+  if (!std::isfinite(r->free_distance_m) || r->free_distance_m < 0.0f) return nav_refuse(c, who, "free_distance_m must be finite and not negative");
+  if (!std::isfinite(r->core_distance_m) || r->core_distance_m < 0.0f) return nav_refuse(c, who, "core_distance_m must be finite and not negative");
+  if (r->core_distance_m < r->free_distance_m) return nav_refuse(c, who, "core_distance_m lies below free_distance_m");
+  if (r->min_core_voxels < 1) return nav_refuse(c, who, "min_core_voxels must be at least 1");
+  if (r->max_cost > KS_NAV_MAX_COST) return nav_refuse(c, who, "max_cost lies above KS_NAV_MAX_COST");
+  if (r->use_bounds)
+    for (int k = 0; k < 3; ++k)
+      if (r->bounds_min[k] > r->bounds_max[k]) return nav_refuse(c, who, "a bounds_min lies above its bounds_max");
+  if (int rc = nav_begin(c, who)) return rc;
+  if (int rc = esdf_ready(c, who)) return rc;
+  if (int rc = quiesce(c)) return rc;
+  hipStream_t st = c->stream;
+  const uint32_t nt = c->esdf_tiles;
+  if (nt >= (1u << 23)) {   // (a voxel's id is slot * 512 + local in 32 bits, all-ones = none)
+    c->err = std::string(who) + ": too many tiles for one call";
+    return KS_ERR_UNSUPPORTED;
+  }
+  const size_t nvox = (size_t)nt * kTileVoxels;
+  const uint32_t max_cost = r->max_cost ? r->max_cost : KS_NAV_MAX_COST, max_rounds = r->max_rounds ? r->max_rounds : 1u << 20;
+  // the objects as they are stored now: their ids in the slots both stores cover (a later ks_objects_update is not seen)
+  const uint32_t n_obj = c->obj_valid ? (uint32_t)c->obj_count : 0u;
+  const size_t obj_vox = (size_t)std::min(c->obj_tiles, nt) * kTileVoxels;
+  int rc;
+  drop_rooms(c);   // (a failure below leaves nothing stored)
+  const size_t vox_cap = ((size_t)nt + nt / 2 + 64) * kTileVoxels;
+  if ((rc = c->rooms_room.reserve(c, nvox, vox_cap)) || (rc = c->rooms_cost.reserve(c, nvox, vox_cap)) || (rc = c->rooms_parent.reserve(c, nvox, nvox + nvox / 2)) ||
+      (rc = c->rooms_cls.reserve(c, nvox, nvox + nvox / 2)) || (rc = c->rooms_lists.reserve(c, 2 * (size_t)nt, 3 * (size_t)nt + 128)) ||
+      (rc = c->rooms_queued.reserve(c, (size_t)nt + 3, (size_t)nt + nt / 2 + 64)) || (rc = c->rooms_nav_counters.reserve(c, 1, 1)) ||
+      (rc = c->rooms_numbered.reserve(c, 1, 1)) || (rc = c->rooms_counters.reserve(c, 1, 1)) || (rc = c->rooms_obj_room.reserve(c, n_obj, n_obj)) ||
+      (rc = c->rooms_obj_best.reserve(c, n_obj, n_obj)))
+    return rc;
+  uint32_t* counts = c->rooms_queued.get() + nt;
+  HIPCHK(c, hipMemsetAsync(c->rooms_nav_counters, 0, sizeof(NavCounters), st));
+  HIPCHK(c, hipMemsetAsync(c->rooms_numbered, 0, sizeof(ObjCounters), st));
+  HIPCHK(c, hipMemsetAsync(c->rooms_counters, 0, sizeof(RoomCounters), st));
+  HIPCHK(c, hipMemsetAsync(c->rooms_queued, 0, ((size_t)nt + 3) * sizeof(uint32_t), st));
+  if (n_obj) HIPCHK(c, hipMemsetAsync(c->rooms_obj_room, 0xff, (size_t)n_obj * sizeof(uint32_t), st));
+  RoomParams R{};
+  R.free_distance = r->free_distance_m;
+  R.core_distance = r->core_distance_m;
+  R.use_bounds = r->use_bounds ? 1 : 0;
+  for (int k = 0; k < 3; ++k) R.bmin[k] = r->bounds_min[k], R.bmax[k] = r->bounds_max[k];
+  R.nt = nt;
+  ObjParams O{};   // (k_obj_seams reads the tile count alone)
+  O.nt = nt;
+  ObjCounters numbered{};
+  RoomCounters counts_h{};
+  NavCounters relax_h{};
+  uint32_t nc = 0, n_rooms = 0, n_pairs = 0, n_links = 0;
+  const EsdfRecord* store = (const EsdfRecord*)c->esdf_store.get();
+  const NavField F{c->rooms_cost.get(), nt};
+  if (nt) {
+    // 1) classes, initial costs, the core components: seams, flat forest and provisional numbers as the objects do
+    hipLaunchKernelGGL(k_room_classify, dim3(nt), dim3(512), 0, st, c->table, R, store, c->rooms_cls.get(), c->rooms_parent.get(), c->rooms_cost.get(),
+                       c->rooms_counters.get());
+    hipLaunchKernelGGL(k_obj_seams, dim3(nt), dim3(512), 0, st, c->table, O, (const uint8_t*)c->rooms_cls.get(), c->rooms_parent.get());
+    hipLaunchKernelGGL(k_obj_number, dim3(nt * 2), dim3(256), 0, st, c->rooms_parent.get(), c->rooms_room.get(), c->rooms_numbered.get());
+    HIPCHK(c, hipMemcpyAsync(&numbered, c->rooms_numbered, sizeof(numbered), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the read that sizes the component buffers
+    nc = numbered.n_components;
+  }
+  if (nc) {
+    // 2) the components' sizes and smallest voxels, the filter, the order: provisional number -> room
+    const size_t cap = (size_t)nc + nc / 2;
+    if ((rc = c->rooms_core_acc.reserve(c, nc, cap)) || (rc = c->rooms_final.reserve(c, nc, cap)) || (rc = c->rooms_cores.reserve(c, nc, cap)) ||
+        (rc = c->rooms_acc.reserve(c, nc, cap)) || (rc = c->rooms_records.reserve(c, nc, cap)))
+      return rc;
+    for (int k = 0; k < 2; ++k)
+      if ((rc = c->rooms_keys[k].reserve(c, nc, cap)) || (rc = c->rooms_vals[k].reserve(c, nc, cap))) return rc;
+    const dim3 per_comp((nc + 255) / 256);
+    hipLaunchKernelGGL(k_obj_acc_init, per_comp, dim3(256), 0, st, c->rooms_core_acc.get(), nc);
+    hipLaunchKernelGGL(k_obj_reduce, dim3(nt * 2), dim3(256), 0, st, c->table, (const uint8_t*)c->rooms_cls.get(), c->rooms_parent.get(),
+                       (const uint32_t*)c->rooms_room.get(), c->rooms_core_acc.get());
+    hipLaunchKernelGGL(k_obj_keys, per_comp, dim3(256), 0, st, (const ObjAcc*)c->rooms_core_acc.get(), nc, r->min_core_voxels, c->rooms_keys[0].get(),
+                       c->rooms_vals[0].get(), c->rooms_numbered.get());
+    uint64_t* keys = nullptr;
+    uint32_t* vals = nullptr;
+    if ((rc = sort_pairs(c, c->rooms_keys[0].get(), c->rooms_keys[1].get(), c->rooms_vals[0].get(), c->rooms_vals[1].get(), nc, 64, &keys, &vals))) return rc;
+    hipLaunchKernelGGL(k_obj_records, per_comp, dim3(256), 0, st, (const ObjAcc*)c->rooms_core_acc.get(), nc, (const uint64_t*)keys, (const uint32_t*)vals,
+                       c->rooms_cores.get(), c->rooms_final.get());
+    hipLaunchKernelGGL(k_room_acc_init, per_comp, dim3(256), 0, st, c->rooms_acc.get(), nc);
+    // 3) the multi-source cost: k_nav_relax from the cores of the rooms
+    hipLaunchKernelGGL(k_room_seed, dim3(nt * 2), dim3(256), 0, st, (const uint32_t*)c->rooms_parent.get(), (const uint32_t*)c->rooms_final.get(), 1,
+                       c->rooms_room.get(), c->rooms_cost.get(), c->rooms_queued.get(), c->rooms_lists.get(), counts);
+    uint32_t active = 0;
+    if ((rc = rooms_relax(c, counts, max_rounds, &active, [&](uint32_t round) {
+           hipLaunchKernelGGL(k_nav_relax, dim3(nt), dim3(512), 0, st, c->table, F, c->rooms_queued.get(), c->rooms_lists.get(), counts, round, max_cost,
+                              c->rooms_nav_counters.get());
+         })))
+      return rc;
+    if (!active) {
+      // 4) the room of every reached voxel, down the shortest-path graph from the same seeds
+      HIPCHK(c, hipMemsetAsync(c->rooms_queued, 0, ((size_t)nt + 3) * sizeof(uint32_t), st));
+      hipLaunchKernelGGL(k_room_seed, dim3(nt * 2), dim3(256), 0, st, (const uint32_t*)c->rooms_parent.get(), (const uint32_t*)c->rooms_final.get(), 0,
+                         c->rooms_room.get(), c->rooms_cost.get(), c->rooms_queued.get(), c->rooms_lists.get(), counts);
+      if ((rc = rooms_relax(c, counts, max_rounds, &active, [&](uint32_t round) {
+             hipLaunchKernelGGL(k_room_assign, dim3(nt), dim3(512), 0, st, c->table, F, c->rooms_room.get(), c->rooms_queued.get(), c->rooms_lists.get(), counts,
+                                round, c->rooms_nav_counters.get());
+           })))
+        return rc;
+    }
+    if (active) {   // a result that has not converged depends on the schedule: none is stored
+      c->err = std::string(who) + ": a relaxation is still active after max_rounds = " + std::to_string(max_rounds) + " rounds";
+      return KS_ERR_UNSUPPORTED;
+    }
+    // 5) per room: the assigned voxels, the clearance and where it is attained
+    hipLaunchKernelGGL(k_room_reduce, dim3(nt * 2), dim3(256), 0, st, c->table, store, (const uint32_t*)c->rooms_room.get(),
+                       (const uint32_t*)c->rooms_cost.get(), c->rooms_acc.get());
+    hipLaunchKernelGGL(k_room_pick, dim3(nt * 2), dim3(256), 0, st, c->table, store, (const uint32_t*)c->rooms_room.get(), (const uint32_t*)c->rooms_cost.get(),
+                       c->rooms_acc.get());
+    // 6) the contacts: counted, emitted, sorted; the heads of the runs are the links
+    RoomCounters* C = c->rooms_counters.get();
+    hipLaunchKernelGGL(k_room_contacts, dim3(nt), dim3(512), 0, st, c->table, nt, (const uint32_t*)c->rooms_room.get(), 0, &C->n_pairs, (uint64_t*)nullptr,
+                       (uint32_t*)nullptr);
+    HIPCHK(c, hipMemcpyAsync(&numbered, c->rooms_numbered, sizeof(numbered), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(&counts_h, c->rooms_counters, sizeof(counts_h), hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));   // the read that sizes the pair buffers
+    n_rooms = numbered.n_objects;
+    n_pairs = counts_h.n_pairs;
+    if (n_pairs >= (1u << 31)) {
+      c->err = std::string(who) + ": too many contacts for one call";
+      return KS_ERR_UNSUPPORTED;
+    }
+    if (n_pairs) {
+      const size_t pcap = (size_t)n_pairs + n_pairs / 2;
+      for (int k = 0; k < 2; ++k)
+        if ((rc = c->rooms_keys[k].reserve(c, n_pairs, pcap)) || (rc = c->rooms_vals[k].reserve(c, n_pairs, pcap)) ||
+            (rc = c->rooms_head_keys[k].reserve(c, n_pairs, pcap)) || (rc = c->rooms_head_vals[k].reserve(c, n_pairs, pcap)))
+          return rc;
+      hipLaunchKernelGGL(k_room_contacts, dim3(nt), dim3(512), 0, st, c->table, nt, (const uint32_t*)c->rooms_room.get(), 1, &C->cursor, c->rooms_keys[0].get(),
+                         c->rooms_vals[0].get());
+      const unsigned key_bits = 32 + bits_for(n_rooms);
+      if ((rc = sort_pairs(c, c->rooms_keys[0].get(), c->rooms_keys[1].get(), c->rooms_vals[0].get(), c->rooms_vals[1].get(), n_pairs, key_bits, &keys, &vals))) return rc;
+      hipLaunchKernelGGL(k_room_heads, dim3((n_pairs + 255) / 256), dim3(256), 0, st, (const uint64_t*)keys, n_pairs, c->rooms_head_keys[0].get(),
+                         c->rooms_head_vals[0].get(), &C->n_links);
+      HIPCHK(c, hipMemcpyAsync(&counts_h, c->rooms_counters, sizeof(counts_h), hipMemcpyDeviceToHost, st));
+      HIPCHK(c, hipStreamSynchronize(st));   // the read that sizes the link buffers
+      n_links = counts_h.n_links;
+      uint64_t* head_keys = nullptr;
+      uint32_t* starts = nullptr;
+      if ((rc = c->rooms_link_acc.reserve(c, n_links, n_links + n_links / 2)) || (rc = c->rooms_links.reserve(c, n_links, n_links + n_links / 2)) ||
+          (rc = sort_pairs(c, c->rooms_head_keys[0].get(), c->rooms_head_keys[1].get(), c->rooms_head_vals[0].get(), c->rooms_head_vals[1].get(), n_links, key_bits,
+                           &head_keys, &starts)))
+        return rc;
+      const dim3 per_pair((n_pairs + 255) / 256), per_link((n_links + 255) / 256);
+      hipLaunchKernelGGL(k_room_link_init, per_link, dim3(256), 0, st, c->rooms_link_acc.get(), n_links);
+      hipLaunchKernelGGL(k_room_link_max, per_pair, dim3(256), 0, st, store, (const uint32_t*)vals, n_pairs, (const uint32_t*)starts, n_links,
+                         c->rooms_link_acc.get());
+      hipLaunchKernelGGL(k_room_link_pick, per_pair, dim3(256), 0, st, c->table, store, (const uint32_t*)vals, n_pairs, (const uint32_t*)starts, n_links,
+                         c->rooms_link_acc.get());
+      hipLaunchKernelGGL(k_room_links, per_link, dim3(256), 0, st, c->table, nt, (const uint32_t*)c->rooms_room.get(), (const uint64_t*)head_keys,
+                         (const uint32_t*)starts, n_links, n_pairs, (const RoomLinkAcc*)c->rooms_link_acc.get(), c->rooms_acc.get(), c->rooms_links.get());
+    }
+    // 7) the join with the stored objects
+    if (n_obj && n_rooms) {
+      HIPCHK(c, hipMemsetAsync(c->rooms_obj_best, 0xff, (size_t)n_obj * sizeof(unsigned long long), st));
+      if (obj_vox)
+        hipLaunchKernelGGL(k_room_obj_min, dim3((uint32_t)((obj_vox + 255) / 256)), dim3(256), 0, st, (const uint32_t*)c->obj_ids.get(), n_obj,
+                           (const uint32_t*)c->rooms_room.get(), (const uint32_t*)c->rooms_cost.get(), obj_vox, c->rooms_obj_best.get());
+      hipLaunchKernelGGL(k_room_obj_join, dim3((n_obj + 255) / 256), dim3(256), 0, st, (const unsigned long long*)c->rooms_obj_best.get(), n_obj,
+                         c->rooms_obj_room.get(), c->rooms_acc.get(), c->rooms_counters.get());
+    }
+    // 8) the records
+    if (n_rooms)
+      hipLaunchKernelGGL(k_room_records, dim3((n_rooms + 255) / 256), dim3(256), 0, st, (const ks_object*)c->rooms_cores.get(), (const RoomAcc*)c->rooms_acc.get(),
+                         n_rooms, c->rooms_records.get(), c->rooms_counters.get());
+  } else if (nt) {
+    HIPCHK(c, hipMemsetAsync(c->rooms_room, 0xff, nvox * sizeof(uint32_t), st));   // no core voxel: no room, nothing assigned
+  }
+  HIPCHK(c, hipMemcpyAsync(&counts_h, c->rooms_counters, sizeof(counts_h), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipMemcpyAsync(&relax_h, c->rooms_nav_counters, sizeof(relax_h), hipMemcpyDeviceToHost, st));
+  HIPCHK(c, hipStreamSynchronize(st));
+  HIPCHK(c, hipGetLastError());
+  c->rooms_valid = true;
+  c->rooms_tiles = nt;
+  c->rooms_count = n_rooms;
+  c->rooms_link_count = n_links;
+  c->rooms_obj_count = n_obj;
+  if (stats) {
+    stats->voxels_free = counts_h.free_voxels;
+    stats->voxels_core = counts_h.core_voxels;
+    stats->components = nc;
+    stats->rooms = n_rooms;
+    stats->voxels_assigned = counts_h.assigned;
+    stats->voxels_unassigned = counts_h.free_voxels - counts_h.assigned;
+    stats->largest_room_voxels = counts_h.largest_room;
+    stats->largest_cost = counts_h.largest_cost;
+    stats->links = n_links;
+    stats->contacts = n_pairs;
+    stats->objects_seen = n_obj;
+    stats->objects_joined = counts_h.objects_joined;
+    stats->rounds = relax_h.rounds;
+    stats->tile_relaxations = relax_h.relaxations;
+    stats->workspace_bytes = rooms_workspace(nt, nc, n_pairs, n_links, n_obj);
+  }
+  return KS_OK;
+}
+
+static int rooms_read_begin(ks_ctx* c, const char* who) {
+  if (int rc = nav_begin(c, who)) return rc;
+  if (!c->rooms_valid) return nav_refuse(c, who, "no rooms are stored (ks_rooms_update has not run since the ESDF store or the map last changed)");
+  return KS_OK;
+}
+
+int ks_rooms_size(ks_ctx* c, size_t* n_rooms, size_t* n_links) {
+  if (!c || (!n_rooms && !n_links)) return KS_ERR_INVALID_ARG;
+  if (int rc = rooms_read_begin(c, "ks_rooms_size")) return rc;
+  if (n_rooms) *n_rooms = c->rooms_count;
+  if (n_links) *n_links = c->rooms_link_count;
+  return KS_OK;
+}
+
+// the download of one of the three lists: *n receives the count, cap must hold it
+extern "C++" template <class T>
+static int rooms_list(ks_ctx* c, const char* who, const T* d_list, size_t count, T* out, size_t cap, size_t* n) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  if (int rc = rooms_read_begin(c, who)) return rc;
+  if (n) *n = count;
+  if (cap < count || (count && !out)) return nav_refuse(c, who, "output buffer too small");
+  if (count) HIPCHK(c, hipMemcpy(out, d_list, count * sizeof(T), hipMemcpyDeviceToHost));
+  return KS_OK;
+}
+
+int ks_rooms_download(ks_ctx* c, ks_room* out, size_t cap, size_t* n) {
+  return rooms_list(c, "ks_rooms_download", c ? (const ks_room*)c->rooms_records.get() : nullptr, c ? c->rooms_count : 0, out, cap, n);
+}
+
+int ks_rooms_links_download(ks_ctx* c, ks_room_link* out, size_t cap, size_t* n) {
+  return rooms_list(c, "ks_rooms_links_download", c ? (const ks_room_link*)c->rooms_links.get() : nullptr, c ? c->rooms_link_count : 0, out, cap, n);
+}
+
+int ks_rooms_objects(ks_ctx* c, uint32_t* room_of_object, size_t cap, size_t* n) {
+  return rooms_list(c, "ks_rooms_objects", c ? (const uint32_t*)c->rooms_obj_room.get() : nullptr, c ? c->rooms_obj_count : 0, room_of_object, cap, n);
+}
+
+int ks_rooms_download_blocks(ks_ctx* c, const int32_t* idx, size_t n, uint32_t* room, uint32_t* cost) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_rooms_download_blocks";
+  if (n && (!idx || (!room && !cost))) return nav_refuse(c, who, "block_idx_xyz is NULL, or both room and cost are");
+  if (int rc = rooms_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const int vps = c->cfg.voxels_per_side;
+  const size_t nv = (size_t)vps * vps * vps;
+  const size_t chunk = std::min<size_t>(std::max<size_t>(1, (size_t(64) << 20) / (nv * sizeof(uint32_t))), 65535);   // <= 64 MiB staged at a time
+  const size_t m_max = std::min(chunk, n);
+  int rc;
+  if ((rc = c->rooms_out.reserve(c, m_max * nv, m_max * nv)) || (rc = c->rooms_idx.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->rooms_idx, idx + 3 * off, m * 3 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (int plane = 0; plane < 2; ++plane) {
+      uint32_t* out = plane ? cost : room;
+      if (!out) continue;
+      hipLaunchKernelGGL(k_obj_download, dim3((uint32_t)((nv + 255) / 256), (uint32_t)m), dim3(256), 0, c->stream, c->table,
+                         (const uint32_t*)(plane ? c->rooms_cost.get() : c->rooms_room.get()), c->rooms_tiles, (const int32_t*)c->rooms_idx.get(), vps, c->rooms_out.get());
+      HIPCHK(c, hipMemcpyAsync(out + off * nv, c->rooms_out, m * nv * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+      HIPCHK(c, hipStreamSynchronize(c->stream));   // (the staging is reused by the next plane and the next chunk)
+    }
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
+int ks_rooms_query(ks_ctx* c, const float* xyz, size_t n, uint32_t* room) {
+  if (!c) return KS_ERR_INVALID_ARG;
+  const char* who = "ks_rooms_query";
+  if (n && (!xyz || !room)) return nav_refuse(c, who, "xyz or room is NULL");
+  if (int rc = rooms_read_begin(c, who)) return rc;
+  if (n == 0) return KS_OK;
+  if (int rc = quiesce(c)) return rc;
+  const size_t m_max = std::min(size_t(1) << 22, n);
+  int rc;
+  if ((rc = c->rooms_out.reserve(c, m_max, m_max)) || (rc = c->rooms_xyz.reserve(c, m_max * 3, m_max * 3))) return rc;
+  for (size_t off = 0; off < n; off += m_max) {
+    const size_t m = std::min(m_max, n - off);
+    HIPCHK(c, hipMemcpyAsync(c->rooms_xyz, xyz + 3 * off, m * 3 * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_obj_query, dim3((uint32_t)((m + 255) / 256)), dim3(256), 0, c->stream, c->table, (const uint32_t*)c->rooms_room.get(), c->rooms_tiles,
+                       (const float*)c->rooms_xyz.get(), m, c->voxel_size_inv, c->rooms_out.get());
+    HIPCHK(c, hipMemcpyAsync(room + off, c->rooms_out, m * sizeof(uint32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+  }
+  HIPCHK(c, hipGetLastError());
+  return KS_OK;
+}
+
 // ---- view information gain over the stored ESDF ("View information gain"; ks_k_view_gain.h) -------
 int ks_view_gain_default_config(ks_view_gain_config* g) {
   if (!g) return KS_ERR_INVALID_ARG;
@@ -6097,6 +6462,8 @@ static void mesh_reset(ks_ctx* c) {
   c->nav_tiles = 0;
   drop_frontiers(c);       // ... and the frontiers
   c->fr_tiles = 0;
+  drop_rooms(c);           // ... and the rooms
+  c->rooms_tiles = 0;
 }
 static int clear_impl(ks_ctx* c, bool keep_integrator_state) {
   if (keep_integrator_state) {
@@ -6191,6 +6558,7 @@ static int remove_tiles(ks_ctx* c, ks_remove_stats* stats) {
   if (n_removed == 0) return KS_OK;
   c->nav_valid = false;   // slots move below and the navigation field does not follow
   drop_frontiers(c);      // ... nor do the frontier ids (§21)
+  drop_rooms(c);          // ... nor the two planes of the rooms (§25)
   if ((rc = snap.fetch_keys(c))) return rc;
   // 1) what leaves: tile positions and blocks, ascending
   std::vector<uint64_t> gone_tiles;

@@ -484,6 +484,52 @@ int main(int argc, char** argv) {
                 n_frontiers, (unsigned long long)fs.components, (unsigned long long)fs.voxels_in_frontiers, (unsigned long long)fs.voxels_frontier, reached);
   }
 
+  // KS_DEMO_ROOMS=<file>: the rooms of the map, on the device without any layer sync — updateEsdf (min_distance_m 0.1, max_distance_m
+  // 0.4), extractObjects (default options), then segmentRooms (core_distance_m 0.3, min_core_voxels 8, the other options default),
+  // written as { u32 rooms, links, objects, 0; u64 stats[15] (ks_rooms_stats); the 96-byte records; the 32-byte links; u32
+  // room_of_object[objects]; per room f32 centroid[3], centre[3], clearance_m; per link f32 door[3], half_width_m }
+  if (const char* rooms_path = std::getenv("KS_DEMO_ROOMS")) {
+    auto* hip = dynamic_cast<kimera::HipSemanticTsdfIntegrator*>(integrator.get());
+    if (!hip) return 8;
+    kimera::HipSemanticTsdfIntegrator::EsdfOptions eo;
+    eo.min_distance_m = 0.1f;
+    eo.max_distance_m = 0.4f;
+    std::vector<kimera::HipSemanticTsdfIntegrator::EsdfBlock> esdf;
+    hip->updateEsdf(eo, &esdf);
+    std::vector<kimera::HipSemanticTsdfIntegrator::ObjectInstance> objects;
+    hip->extractObjects(kimera::HipSemanticTsdfIntegrator::ObjectOptions(), &objects);
+    kimera::HipSemanticTsdfIntegrator::RoomOptions ro;
+    ro.core_distance_m = 0.3f;
+    ro.min_core_voxels = 8;
+    std::vector<kimera::HipSemanticTsdfIntegrator::Room> rooms;
+    std::vector<kimera::HipSemanticTsdfIntegrator::RoomLink> links;
+    std::vector<uint32_t> room_of_object;
+    const auto t0 = std::chrono::steady_clock::now();
+    hip->segmentRooms(ro, &rooms, &links, &room_of_object);
+    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    FILE* rf = std::fopen(rooms_path, "wb");
+    if (!rf) return 9;
+    const uint32_t head[4] = {(uint32_t)rooms.size(), (uint32_t)links.size(), (uint32_t)room_of_object.size(), 0u};
+    const ks_rooms_stats& rs = hip->lastRoomsStats();
+    std::fwrite(head, 4, 4, rf);
+    std::fwrite(&rs, sizeof(rs), 1, rf);
+    for (const auto& r : rooms) std::fwrite(&r.record, sizeof(ks_room), 1, rf);
+    for (const auto& l : links) std::fwrite(&l.record, sizeof(ks_room_link), 1, rf);
+    if (!room_of_object.empty()) std::fwrite(room_of_object.data(), 4, room_of_object.size(), rf);
+    for (const auto& r : rooms) {
+      const float m[7] = {r.centroid.x(), r.centroid.y(), r.centroid.z(), r.centre.x(), r.centre.y(), r.centre.z(), r.clearance_m};
+      std::fwrite(m, 4, 7, rf);
+    }
+    for (const auto& l : links) {
+      const float m[4] = {l.door.x(), l.door.y(), l.door.z(), l.half_width_m};
+      std::fwrite(m, 4, 4, rf);
+    }
+    std::fclose(rf);
+    std::printf("adapter_demo: segmentRooms %.3f ms, %u rooms of %llu core components, %u links, %llu of %llu free voxels assigned, %llu of %llu objects joined\n",
+                ms, head[0], (unsigned long long)rs.components, head[1], (unsigned long long)rs.voxels_assigned, (unsigned long long)rs.voxels_free,
+                (unsigned long long)rs.objects_joined, (unsigned long long)rs.objects_seen);
+  }
+
   // KS_DEMO_VIEW_GAIN=<file>: how much unobserved space candidate views would see, on the device without any layer sync — updateEsdf
   // (min_distance_m 0.1, max_distance_m 0.4), then scoreViews for the last frame's pose turned about the world's z axis in 8 steps of
   // 45 degrees: 16 x 12 rays of a 90-degree image, 3 m range, label 4 counted; written as { u32 views, width, height, label; f32 K[4];

@@ -644,6 +644,64 @@ bool HipSemanticTsdfIntegrator::extractFrontiers(const FrontierOptions& options,
   return true;
 }
 
+bool HipSemanticTsdfIntegrator::segmentRooms(const RoomOptions& options, std::vector<Room>* rooms, std::vector<RoomLink>* links,
+                                             std::vector<uint32_t>* room_of_object) {
+  CHECK_NOTNULL(rooms);
+  rooms->clear();
+  if (links) links->clear();
+  if (room_of_object) room_of_object->clear();
+  ks_rooms_config rc;
+  ks_rooms_default_config(&rc);
+  rc.free_distance_m = options.free_distance_m;
+  rc.core_distance_m = options.core_distance_m;
+  rc.min_core_voxels = options.min_core_voxels;
+  rc.max_cost = options.max_cost;
+  rc.use_bounds = options.use_bounds ? 1 : 0;
+  for (int k = 0; k < 3; ++k) {
+    rc.bounds_min[k] = static_cast<int32_t>(options.bounds_min[k]);
+    rc.bounds_max[k] = static_cast<int32_t>(options.bounds_max[k]);
+  }
+  check(ks_rooms_update(ctx_, &rc, &last_rooms_stats_), "ks_rooms_update");
+  size_t n = 0, n_links = 0, n_objects = 0;
+  check(ks_rooms_size(ctx_, &n, &n_links), "ks_rooms_size");
+  const float voxel_size = semantic_layer_ptr_->voxel_size();
+  const auto metres = [](uint32_t bits) {
+    float f;
+    std::memcpy(&f, &bits, sizeof(f));
+    return f;
+  };
+  if (room_of_object) {
+    n_objects = static_cast<size_t>(last_rooms_stats_.objects_seen);
+    room_of_object->resize(n_objects);
+    check(ks_rooms_objects(ctx_, room_of_object->data(), n_objects, &n_objects), "ks_rooms_objects");
+  }
+  if (links && n_links) {
+    std::vector<ks_room_link> rec(n_links);
+    check(ks_rooms_links_download(ctx_, rec.data(), n_links, &n_links), "ks_rooms_links_download");
+    links->resize(n_links);
+    for (size_t i = 0; i < n_links; ++i) {
+      RoomLink& l = (*links)[i];
+      l.record = rec[i];
+      l.half_width_m = metres(rec[i].clearance_bits);
+      for (int k = 0; k < 3; ++k) l.door[k] = (static_cast<float>(rec[i].door_voxel[k]) + 0.5f) * voxel_size;
+    }
+  }
+  if (n == 0) return false;
+  std::vector<ks_room> rec(n);
+  check(ks_rooms_download(ctx_, rec.data(), n, &n), "ks_rooms_download");
+  rooms->resize(n);
+  for (size_t i = 0; i < n; ++i) {
+    Room& r = (*rooms)[i];
+    r.record = rec[i];
+    r.clearance_m = metres(rec[i].clearance_bits);
+    for (int k = 0; k < 3; ++k) {
+      r.centroid[k] = static_cast<float>((static_cast<double>(rec[i].sum[k]) / static_cast<double>(rec[i].n_voxels) + 0.5) * static_cast<double>(voxel_size));
+      r.centre[k] = (static_cast<float>(rec[i].centre_voxel[k]) + 0.5f) * voxel_size;
+    }
+  }
+  return true;
+}
+
 bool HipSemanticTsdfIntegrator::scoreViews(const std::vector<vxb::Transformation>& T_G_C, const ViewGainOptions& options,
                                            std::vector<ks_view_gain_record>* out) {
   CHECK_NOTNULL(out);

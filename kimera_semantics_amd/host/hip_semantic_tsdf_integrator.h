@@ -317,6 +317,32 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   /// Returns true when `out` is not empty.
   bool extractFrontiers(const FrontierOptions& options, std::vector<Frontier>* out);
   const ks_frontier_stats& lastFrontierStats() const { return last_frontier_stats_; }
+  /// The rooms of the map (ks_rooms_update; the contract is DESIGN.md, "Rooms"): the voxels of the STORED ESDF at least
+  /// core_distance_m from every surface clustered into 26-connected components ON THE DEVICE (free space falls apart at doors),
+  /// every other free voxel handed to the room nearest through free space, the contacts between rooms as links, and the objects of
+  /// the last extractObjects() joined: room_of_object[i] is the room of object i, or KS_ROOM_NONE.  Call updateEsdf() / refreshEsdf()
+  /// first.  Rooms ascend by their smallest core voxel (x, y, z), links by (room_a, room_b).  The bounds are inclusive global voxel indices.
+  struct RoomOptions {
+    float free_distance_m = 0.0f, core_distance_m = 0.5f;
+    uint32_t min_core_voxels = 64;
+    uint32_t max_cost = 0;          ///< 0: KS_NAV_MAX_COST
+    bool use_bounds = false;
+    vxb::GlobalIndex bounds_min = vxb::GlobalIndex(0, 0, 0), bounds_max = vxb::GlobalIndex(0, 0, 0);
+  };
+  struct Room {
+    vxb::Point centroid;   ///< metres, world frame, over the assigned voxels: may lie inside a wall of an L-shaped room
+    vxb::Point centre;     ///< metres: the centre of record.centre_voxel, always free: a valid goal for updateNavField()
+    float clearance_m;     ///< the largest stored distance among its core voxels
+    ks_room record;
+  };
+  struct RoomLink {
+    vxb::Point door;       ///< metres: the centre of record.door_voxel
+    float half_width_m;    ///< the largest stored distance among the contacts
+    ks_room_link record;
+  };
+  /// Returns true when `rooms` is not empty.  links and room_of_object may be nullptr.
+  bool segmentRooms(const RoomOptions& options, std::vector<Room>* rooms, std::vector<RoomLink>* links, std::vector<uint32_t>* room_of_object);
+  const ks_rooms_stats& lastRoomsStats() const { return last_rooms_stats_; }
   /// How much unobserved space each candidate camera pose would see (ks_view_gain; the contract is DESIGN.md, "View information
   /// gain"): the distinct unknown, free and surface voxels of the STORED ESDF that the rays of a small pinhole image visit before a
   /// surface stops them, counted ON THE DEVICE.  Call updateEsdf() / refreshEsdf() first.  One record per pose, in the order of the poses;
@@ -369,6 +395,7 @@ class HipSemanticTsdfIntegrator : public vxb::TsdfIntegratorBase, public Semanti
   ks_align_stats last_align_stats_{};
   ks_objects_stats last_objects_stats_{};
   ks_frontier_stats last_frontier_stats_{};
+  ks_rooms_stats last_rooms_stats_{};
   ks_view_gain_stats last_view_gain_stats_{};
   ks_remove_stats last_remove_stats_{};
   ks_fuse_stats last_fuse_stats_{};

@@ -17,7 +17,7 @@ into the map at that pose on the device (ks_fuse_map: resampled under SE(3) and 
 writes the cost-to-go field of the final ESDF to that goal for a robot of --nav-radius, made on the device (ks_nav_update), with the
 path from the last camera position; map saving stays on the host side of the drop-in boundary (out of scope).
   python tools/replay.py --synthetic 50 [--method merged] [--mesh out.ply] [--mesh-indexed out.ply] [--mesh-every 5] [--esdf out.npz] [--esdf-every 5] \\
-      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz [--nav-shorten]] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] [--view-gain out.npz] \\
+      [--nav-goal 0.5,0,0 --nav-radius 0.3 --nav-out nav.npz [--nav-shorten]] [--render-every 10 --render-out views/] [--align --align-iterations 10 --align-dof 0x3c] [--objects out.npz] [--frontiers out.npz] [--rooms out.npz] [--view-gain out.npz] \\
       [--max-block-distance 3.0] [--submap-frames 10]
   python tools/replay.py --bag demo.bag --depth-topic /tesse/depth --semantic-topic /tesse/segmentation \\
       --camera-info-topic /tesse/left_cam/camera_info --sensor-frame left_cam --label-csv cfg/tesse_multiscene_office1_segmentation_mapping.csv"""
@@ -85,6 +85,11 @@ def main():
                     "robot of --nav-radius and write them (records (n,) of 88 bytes ascending by first_voxel, centroids_m, targets_m, stats, "
                     "block_indices and the per-block ids); needs --esdf; with --nav-goal the records carry the cost-to-go from that goal")
     ap.add_argument("--frontiers-min-voxels", type=int, default=8, metavar="N")
+    ap.add_argument("--rooms", metavar="OUT.npz", help="segment the final ESDF into rooms on the device (ks_rooms_update) and write them (records (n,) of "
+                    "96 bytes ascending by first_voxel, links (m,) of 32 bytes, centroids_m, centres_m, room_of_object (with --objects), stats, "
+                    "block_indices and the per-block room and cost planes); needs --esdf")
+    ap.add_argument("--rooms-core-distance", type=float, default=0.5, metavar="M")
+    ap.add_argument("--rooms-min-core-voxels", type=int, default=64, metavar="N")
     ap.add_argument("--view-gain", metavar="OUT.npz", help="score candidate camera poses by the unknown voxels of the final ESDF they would see, on the "
                     "device (ks_view_gain): the centres of the frontiers' nav_voxel (the frontiers as --frontiers makes them), each at 8 yaws, "
                     "--view-gain-size rays of a 90-degree image, --view-gain-range metres; writes poses (n, 7), records (n,) of 32 bytes, stats; "
@@ -107,6 +112,8 @@ def main():
         ap.error("--nav-out plans over the stored ESDF: give --esdf, --esdf-every or --esdf-slice as well")
     if a.frontiers and not a.esdf:
         ap.error("--frontiers reads the stored ESDF: give --esdf as well")
+    if a.rooms and not a.esdf:
+        ap.error("--rooms reads the stored ESDF: give --esdf as well")
     if a.view_gain and not a.esdf:
         ap.error("--view-gain reads the stored ESDF: give --esdf as well")
     if a.nav_goal:
@@ -347,6 +354,21 @@ def main():
               f"({st['voxels_in_frontiers']} in frontiers, the largest {st['largest_frontier_voxels']}), {st['unknown_faces']} unknown faces, "
               f"{reached} reached by the field" + ("" if st["nav_field_used"] else " (no field stored: give --nav-goal)") +
               f", work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, {t_fr * 1e3:.2f} ms (update + records + ids) -> {a.frontiers}")
+    if a.rooms:
+        if a.objects:   # stored objects are joined to their rooms (the --objects step below makes the same ones again)
+            integ.objects(min_voxels=a.objects_min_voxels)
+        t1 = time.perf_counter()
+        rec, links, st = integ.rooms(core_distance_m=a.rooms_core_distance, min_core_voxels=a.rooms_min_core_voxels)
+        idx = integ.block_indices()
+        t_rm = time.perf_counter() - t1
+        np.savez_compressed(a.rooms, records=rec, links=links, centroids_m=B.room_centroids(rec, integ.cfg.voxel_size),
+                            centres_m=B.room_centres(rec, integ.cfg.voxel_size), room_of_object=integ.room_objects(), stats_names=np.array(list(st)),
+                            stats=np.array(list(st.values()), np.uint64), block_indices=idx, room_ids=integ.room_ids(idx), room_costs=integ.room_costs(idx),
+                            core_distance_m=np.float32(a.rooms_core_distance), voxel_size=np.float32(a.voxel_size), voxels_per_side=np.int32(integ.vps))
+        print(f"rooms: {st['rooms']} rooms of {st['components']} core components, {st['links']} links over {st['contacts']} contacts, "
+              f"{st['voxels_assigned']} of {st['voxels_free']} free voxels assigned (the largest room {st['largest_room_voxels']}), "
+              f"{st['objects_joined']} of {st['objects_seen']} objects joined, {st['rounds']} rounds, work space {st['workspace_bytes'] / 2 ** 20:.1f} MiB, "
+              f"{t_rm * 1e3:.2f} ms (update + records + links) -> {a.rooms}")
     if a.view_gain:   # (after --frontiers: the candidates stand where the frontiers are best reached)
         vw, vh = (int(v) for v in a.view_gain_size.lower().split("x"))
         frec, _ = integ.frontiers(radius_m=a.nav_radius, min_voxels=a.frontiers_min_voxels)
